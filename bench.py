@@ -15,10 +15,15 @@ scaling), one RCCL all-gather of the registered clouds and poses at the end of e
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`), refuses (exit code != 0) when fewer than N GPUs are visible, and every rank
 asserts WORLD_SIZE == --gpus before anything is timed: the line can never report an n_gpus that was not requested.
 
+A PLAIN run does only what the headline needs: set up, W warm-up calls, K timed (un-instrumented) calls, the outputs of the last timed
+call when --dump-outputs DIR is given (`dump_outputs`), and the result line.  Everything else below -- the instrumented call behind the
+roofline and HBM figures, the other arithmetic modes, the ragged batch, the online-softmax leg, graph replay, few-token latency, the CPU
+baseline and every parity check against a fixture or an oracle -- runs only with --full.
+
 Rank 0 prints ONE COMPACT JSON line on stdout (<= 6 KB, `compact_line`: the contract's keys + `roofline` + `cpu_baseline` + one-number
-summaries; tests/test_host_logic.py::test_bench_line_is_small guards the size) and writes the FULL record described below to
-gpurun_out/bench_detail.json (--detail-out) and to stderr.  `--config N` selects a BASELINE.json configs[N] preset (geometry, flow steps,
-arithmetic and the config.workload label); the default is configs[1].  The full record carries:
+summaries; tests/test_host_logic.py::test_bench_line_is_small guards the size); a --full run also writes the FULL record described below
+to the --detail-out file and to stderr.  `--config N` selects a BASELINE.json configs[N] preset (geometry, flow steps, arithmetic and the
+config.workload label); the default is configs[1].  The full record (--full) carries:
   roofline      -- the dominant kernel (attention_f32_kernel): algorithmic FLOPs / HIP-event time, vs the
                    157.3 TFLOP/s fp32 matrix peak of gfx950.  `value` / `ms_per_step` come from K UN-instrumented calls
                    (`instrumented: false`); the per-kernel HIP events ride in ONE extra call after the timed region
@@ -141,14 +146,22 @@ def parse_args():
                     help="where the FULL record goes (default gpurun_out/bench_detail.json; it is also printed to stderr); stdout carries "
                          "only the compact line")
     ap.add_argument("--light", action="store_true",
-                    help="headline only: --no-secondary --no-ragged --gamma-scale 0 --no-cpu-baseline (profiler-driven and per-config runs)")
+                    help="with --full: headline only, --no-secondary --no-ragged --gamma-scale 0 --no-cpu-baseline (per-config runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the instrumented call (roofline, HBM ring), the other arithmetic modes, the ragged "
+                         "batch, the online-softmax leg, graph replay, few-token latency, the CPU baseline and the parity checks; without it "
+                         "a run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed call returned as DIR/<name>.npy (float32 / float64, under 64 MB in all; dump_outputs)")
     args = ap.parse_args()
     p = PRESETS[1 if args.config is None else args.config]
     for k in ("batch", "views", "points", "flow_steps", "dtype", "rigidity"):
         if getattr(args, k) is None:
             setattr(args, k, p[k])
-    if args.light:      # (the CPU leg and the device checker of a 2 x 32 768-point pair take tens of minutes: they belong to the default run only)
+    if args.light or not args.full:      # (the CPU leg and the device checker of a 2 x 32 768-point pair take tens of minutes)
         args.no_secondary, args.no_ragged, args.gamma_scale, args.no_cpu_baseline = True, True, 0.0, True
+    if not args.full:
+        args.no_profile = True
     return args
 
 
@@ -240,10 +253,18 @@ def cpu_baseline(cfg, sd, args, gpu_first_step, full=False):
             err.update({"steps_compared": ks, "pose_fit_on_step": ks - 1,
                         "x0_max_abs": float((x0_gpu[:ks] - ref_first["end_point_trajectory"]).abs().max()),
                         "x_t_max_abs": float((xt_gpu[:ks] - ref_first["trajectory"]).abs().max()),
-                        "rot_err_deg_max": float(O.rotation_error_deg(R_gpu, ref_first["R"][0]).max()),
+                        "rot_err_deg_max": float(rotation_angle_deg(R_gpu, ref_first["R"][0]).max()),
                         "R_frob_max": float(torch.linalg.matrix_norm(R_gpu - ref_first["R"][0]).max()),
                         "trans_abs_max": float((t_gpu - ref_first["t"][0]).abs().max())})
     return out, err
+
+
+def rotation_angle_deg(R_a, R_b):
+    """The angle between two rotations, acos((tr(R_a^T R_b) - 1) / 2), evaluated as 2 asin(|R_a - R_b|_F / sqrt(8)) in fp64 (for rotation
+    matrices |R_a - R_b|_F^2 = 8 sin^2(angle / 2)): the same angle, without the floor acos has near 1 in fp32 (0.03-0.08 degrees for
+    identical matrices, depending on the host's summation order), so a like-with-like comparison reads at rounding level."""
+    d = torch.linalg.matrix_norm((R_a - R_b).double())
+    return torch.rad2deg(2 * torch.asin((d / 8 ** 0.5).clamp(max=1.0)))
 
 
 _CHECKER_CACHE: dict = {}
@@ -306,6 +327,42 @@ def reference_cpu_record():
                         "(profiles/r02_cpu_reference_headline.json)"}
     except (OSError, KeyError, ValueError):
         return None
+
+
+DUMP_BUDGET_BYTES = 48 * 10 ** 6           # array bytes; the .npy headers and any reading of "64 MB" stay well above it
+DUMP_SAMPLE_SEED = 0
+
+
+def dump_outputs(out_dir, last, gathered=None):
+    """--dump-outputs: what the LAST timed call handed its caller, as out_dir/<name>.npy in float32 (float64 stays float64), so that two
+    builds can be compared output for output.  R, t and the final registered cloud (`final_cloud` = end_point_trajectory[-1]) are written
+    whole, and on a multi-rank run the all-gathered clouds and poses too (`gathered_*`).  The two (flow steps, points, 3) trajectories are
+    written whole when everything fits in DUMP_BUDGET_BYTES; otherwise both keep the same fixed, seeded sample of point rows (sorted, at
+    every flow step).  Returns {name: shape}."""
+    import numpy as np
+
+    def host(x):
+        x = x.detach()
+        return (x if x.dtype == torch.float64 else x.float()).cpu().numpy()
+
+    arrays = {"R": host(last["R"]), "t": host(last["t"]), "final_cloud": host(last["end_point_trajectory"][-1])}
+    if gathered is not None:
+        arrays.update(gathered_final_cloud=host(gathered[0]), gathered_R=host(gathered[1]), gathered_t=host(gathered[2]))
+    trajs = {k: last[k] for k in ("end_point_trajectory", "trajectory")}
+    steps, n = trajs["trajectory"].shape[:2]
+    row_bytes = sum(steps * v.shape[2] * (8 if v.dtype == torch.float64 else 4) for v in trajs.values())
+    k = min(n, max(0, (DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values())) // row_bytes))
+    rows = None
+    if k < n:
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        rows = torch.randperm(n, generator=g)[:k].sort().values.to(trajs["trajectory"].device)
+    for name, v in trajs.items():
+        arrays[name] = host(v if rows is None else v.index_select(1, rows))
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 # ---- the ONE line on stdout (VERDICT r05: the round-5 line had grown to 28 KB and the driver could not parse it) -------------------
@@ -674,6 +731,7 @@ def main():
         run_mode.host_first_enqueue_ms = 1e3 * first_enqueue
         run_mode.gather_ms = sum(a.elapsed_time(b) for a, b in ev_pairs[-steps:]) / steps if ev_pairs else 0.0
         run_mode.rank_elapsed = [local_elapsed]
+        run_mode.gathered = gathered if distributed else None      # what a multi-rank caller receives besides its own `last`
         if distributed:
             allt = torch.zeros(world, dtype=torch.float64, device=dev)
             mine_t = torch.tensor([local_elapsed], dtype=torch.float64, device=dev)
@@ -790,12 +848,13 @@ def main():
     main_instr_ratio = run_mode.instrumented_over_clean
     main_bounded = run_mode.bounded_launches
     main_rank_elapsed, main_gather_ms = list(run_mode.rank_elapsed), run_mode.gather_ms
+    dumped = dump_outputs(args.dump_outputs, last, run_mode.gathered) if args.dump_outputs and rank == 0 else None
     if main_bounded != 2 * args.layers:
         raise SystemExit(f"seeded weights: {main_bounded} of {2 * args.layers} attention launches bounded -- the headline expects all")
     # multi-GPU runs: the first pair of RANK 1 (seed 1234 + 32) has a fixture of the unmodified reference too -- parity evidence from a
     # rank that is not rank 0, gathered with one tiny collective every rank takes part in (the condition depends on the arguments only)
     rank1_parity = None
-    if distributed and args.dtype == "float32" and args.workload == "uniform" and args.batch == 32 and args.rigidity:
+    if args.full and distributed and args.dtype == "float32" and args.workload == "uniform" and args.batch == 32 and args.rigidity:
         vals = torch.full((4,), float("nan"), dtype=torch.float64, device=dev)
         if rank == 1:
             try:
@@ -1058,22 +1117,28 @@ def main():
             if err:
                 result["se3_vs_cpu_oracle" if base["kind"] == "port" else "first_step_vs_cpu_reference"] = err
             base["gpu_over_cpu"] = value / base["value"]     # context only (bounded CPU sample, extrapolated unless --cpu-full): never a headline
-        gp = golden_parity(args, last, data) if (args.dtype == "float32" and args.workload == "uniform") else None
+        gp = golden_parity(args, last, data) if (args.full and args.dtype == "float32" and args.workload == "uniform") else None
         if gp:
             result["parity_vs_reference_golden"] = gp
         if rank1_parity:
             result["parity_vs_reference_golden_rank1"] = rank1_parity
         if args.dtype == "float32" and args.workload == "uniform" and world == 1 and not args.no_cpu_baseline:
             result["parity_vs_device_checker_last_pair"] = device_checker_last_pair(cfg, sd, args, last, inp, dev)
-        # the FULL record -> the detail file + stderr; stdout carries the compact line only (<= 6 KB, compact_line above)
+        if dumped:
+            result["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
+        # the FULL record -> the detail file + stderr (--full, or a plain run given --detail-out); stdout carries the compact line only
+        # (<= 6 KB, compact_line above)
         detail_path = args.detail_out or os.path.join("gpurun_out", "bench_detail.json")
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
-            with open(detail_path, "w") as f:
-                json.dump(result, f)
-        except OSError:
+        if args.full or args.detail_out:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(detail_path)), exist_ok=True)
+                with open(detail_path, "w") as f:
+                    json.dump(result, f)
+            except OSError:
+                detail_path = None
+            print(json.dumps(result), file=sys.stderr, flush=True)
+        else:
             detail_path = None
-        print(json.dumps(result), file=sys.stderr, flush=True)
         print(json.dumps(compact_line(result, detail_path)), file=json_out, flush=True)
     if distributed:
         dist.barrier()

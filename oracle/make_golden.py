@@ -354,6 +354,137 @@ def make_collate_golden():
     print("collate_transform", os.path.getsize(path) // 1024, "KiB", {k: out["ref_" + k].shape for k in ("pointclouds", "translations", "scales")})
 
 
+LIVE_CHECK_SWITCHES = {"shipped-config": {}, "l2_noqknorm_rigid": {"qk_norm": False}, "l2_noscale_free": {"scale_emb_on": False},
+                       "l2_nofeat_rigid": {"local_feat_concat_on": False}, "l2_latent64_rigid": {"in_dim": 64}}
+VOXEL_CHECK_CASES = [(1000, 0.1, 1.0), (7, 0.3, 1.0), (1, 0.3, 1.0), (20000, 0.02, 1.0), (30000, 0.5, 40.0)]
+ADAPTIVE_CHECK_ARGS = [(0.25, 0.5, 50, 1500), (1.0, 2.0, 10, 100), (0.05, 0.1, 5, 5000)]
+BATCH_CHECK_COUNTS = [30, 50, 40, 100, 10, 10, 10, 90, 120, 5]
+FEATURE_ROW_STRIDE = 32        # transformer features: every 32nd token row in full, every row's norm, and the largest |value|
+COLLATE_CHECK_KEYS = ("cu_seqlens", "pointclouds", "pointclouds_gt", "part_indices", "anchor_indices", "features", "rotations", "translations",
+                      "points_per_part", "anchor_parts", "init_rotation", "scales", "global_rotation", "global_translation")
+
+
+def live_check_inputs(switch):
+    """The small model call tests/test_oracle.py::test_oracle_matches_live_reference_modules holds the oracle to: 2 layers, weight
+    seed 3, two ragged samples (input seed 99), 3 flow steps; latent features from seed 5 when in_dim > 0."""
+    cfg = dict(S.RAP_12); cfg["num_layers"] = 2
+    cfg.update(switch)
+    sd = S.make_weights(cfg, 3)
+    inp = S.make_inputs([[40, 77], [130, 20, 65]], seed=99)
+    if cfg.get("in_dim", 0):
+        inp["latent_features"] = torch.randn(inp["x_1"].shape[0], cfg["in_dim"], generator=torch.Generator().manual_seed(5))
+    return cfg, sd, inp
+
+
+def rigidity_check_inputs():
+    inp = S.make_inputs([[50, 77, 0], [31, 64, 12]], seed=5)     # empty parts only as trailing padding (the reference's split_parts)
+    cu_b, _ = O.prepare_cu_seqlens(inp)
+    g = torch.Generator().manual_seed(1)
+    pred = inp["pointclouds"] + 0.05 * torch.randn(inp["pointclouds"].shape, generator=g)
+    return inp, cu_b.long(), pred
+
+
+def spinnet_check_inputs():
+    g = torch.Generator().manual_seed(9)
+    pts = torch.randn(1200, 3, generator=g) * torch.tensor([1.0, 1.0, 0.15])
+    return pts, pts[:6].clone(), 0.6, 11
+
+
+def voxel_check_points(seed, n, scale):
+    g = torch.Generator().manual_seed(seed)
+    p = (torch.rand(n, 3, generator=g) - 0.4) * scale
+    if n == 1:
+        p = p + 0.01                       # a point exactly on its voxel centre makes the reference divide 0 / 0
+    return p
+
+
+def voxel_index_digest(idx) -> str:
+    """SHA-256 of an index array as little-endian int64: the voxel checks are exact, so a digest compares as strictly as the array"""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(idx, dtype="<i8").tobytes()).hexdigest()
+
+
+def make_live_checks_golden():
+    """tests/golden/live_reference_checks.npz: what the reference's own modules return for the small cases tests/test_oracle.py
+    holds the oracle to (the sampling call per constructor switch, rigidity RMSE, MiniSpinNet, voxel down-sampling, transform +
+    collate, adaptive sample counts) and the batch sampler tests/test_parallel_cpu.py mirrors, so those tests need no reference at
+    run time.  Inputs are regenerated from their seeds by the *_check_inputs helpers above; the fixture stores the checksums that pin
+    them.  To stay small it stores the sampling call's transformer features as every FEATURE_ROW_STRIDE-th token row plus every row's
+    fp64 norm and the largest |value| (the per-case fixtures of main() hold full features), the collated features as the row permutation
+    of the raw ones the reference applied (checked bit for bit here), and the voxel indices, compared exactly, as a digest."""
+    import importlib
+    out = {}
+    for name, switch in LIVE_CHECK_SWITCHES.items():
+        cfg, sd, inp = live_check_inputs(switch)
+        out[f"model_{name}_weights_checksum"] = np.float64(weights_checksum(sd))
+        out[f"model_{name}_inputs_checksum"] = np.float64(sum(float(v.double().sum()) for v in inp.values()))
+        for rigid in ((False, True) if not switch else (True,)):
+            ref = ref_loader.reference_sample(cfg, sd, inp, 3, rigid)
+            tag = f"model_{name}_{'rigid' if rigid else 'free'}"
+            for k in ("end_point_trajectory", "trajectory", "R", "t"):
+                out[f"{tag}_{k}"] = ref[k].numpy()
+            f = ref["transformer_features"]
+            out[f"{tag}_features_rows"] = f[::FEATURE_ROW_STRIDE].numpy()
+            out[f"{tag}_features_row_norms"] = torch.linalg.vector_norm(f.double(), dim=1).numpy()
+            out[f"{tag}_features_absmax"] = np.float64(f.abs().max())
+            out[f"{tag}_features_timestep"] = np.float64(ref["features_timestep"])
+    ref = ref_loader.load_reference()
+    inp, cu, pred = rigidity_check_inputs()
+    R, t = ref.fit_transformations(inp["pointclouds"], pred, inp["points_per_part"], cu)
+    out["rigidity_R"], out["rigidity_t"] = R.numpy(), t.numpy()
+    for per_part in (False, True):
+        for scaled in (False, True):
+            out[f"rigidity_rmse_{int(per_part)}{int(scaled)}"] = ref.compute_rigidity_rmse(
+                inp["pointclouds"], pred, R, t, inp["points_per_part"], cu, inp["scales"] if scaled else None, per_part).numpy()
+    from rap_amd.spinnet import make_spinnet_weights
+    pts, kpts, des_r, seed = spinnet_check_inputs()
+    sp = ref_loader.reference_spinnet_forward(make_spinnet_weights(3), pts, kpts, des_r, seed)
+    out["spinnet_perm"], out["spinnet_patches"], out["spinnet_desc"] = np.asarray(sp["perm"]), sp["patches"].numpy(), sp["desc"].numpy()
+    du = ref_loader.load_reference_dataset_utils()
+    for seed, (n, vs, scale) in enumerate(VOXEL_CHECK_CASES):
+        idx = du.voxel_down_sample_torch(voxel_check_points(seed, n, scale), vs).numpy()
+        out[f"voxel_idx_{seed}_len"] = np.int64(len(idx))
+        out[f"voxel_idx_{seed}_sha256"] = np.array(voxel_index_digest(idx))
+    samples = collate_samples(seed=9)
+    col = ref_loader.reference_transform_and_collate(samples, 6, 4)
+    for k in COLLATE_CHECK_KEYS:
+        if k != "features":
+            out[f"collate_{k}"] = col[k].numpy()
+    raw = np.concatenate([np.concatenate(smp["features"]) for smp in samples])
+    row_of = {r.tobytes(): i for i, r in enumerate(raw)}
+    perm = np.array([row_of[r.tobytes()] for r in col["features"].numpy()], dtype=np.int32)
+    assert col["features"].dtype == torch.float32 and np.array_equal(raw[perm], col["features"].numpy())
+    out["collate_features_row_of_raw"] = perm
+    ref_loader._install_pytorch3d_import_stub()
+    sys.modules["pytorch3d.ops"].sample_farthest_points = None
+    m = importlib.import_module("dataset_process.utils.point_sampling_utils")
+    g = np.random.RandomState(5)
+    parts = [g.rand(4000, 3) * np.array([20, 15, 3.0]), g.rand(37, 3), np.zeros((0, 3)), g.rand(900, 3) * np.array([4, 4, 1.0]) - 2.0]
+    for i, a in enumerate(ADAPTIVE_CHECK_ARGS):
+        out[f"adaptive_counts_{i}"] = np.asarray(m.calculate_adaptive_sample_count_per_part(parts, *a), dtype=np.int64)
+    # the reference's DynamicBatchSampler (data/datamodule.py) on fixed per-sample point counts, one and two ranks: JSON lists of batches
+    import json
+    dm = ref_loader.load_reference_data().datamodule
+
+    class _DS:
+        def __len__(self):
+            return len(BATCH_CHECK_COUNTS)
+
+        def estimate_num_points(self, i):
+            return BATCH_CHECK_COUNTS[i]
+
+    for drop_last in (False, True):
+        smp = dm.DynamicBatchSampler(_DS(), 100, shuffle=False, drop_last=drop_last, seed=0)
+        out[f"batch_sampler_drop_last{int(drop_last)}"] = np.array(json.dumps(list(iter(smp))))
+    for rank in range(2):
+        smp = dm.DynamicBatchSampler(_DS(), 100, shuffle=False, drop_last=False, seed=0)
+        smp._get_rank_and_size = lambda rank=rank: (rank, 2)
+        out[f"batch_sampler_rank{rank}_of_2"] = np.array(json.dumps(list(iter(smp))))
+    path = os.path.join(GOLDEN_DIR, "live_reference_checks.npz")
+    np.savez_compressed(path, **out)
+    print("live_reference_checks", os.path.getsize(path) // 1024, "KiB,", len(out), "arrays")
+
+
 def _traj_summary(ref, stride):
     """What a full-geometry fixture keeps of a sampling call: the final registered cloud, the last x_t, the poses, the
     per-step max-norms of both trajectories and every `stride`-th point of every step (so error growth over the re-noised
@@ -478,6 +609,8 @@ if __name__ == "__main__":
         make_envelope_goldens()
     if not only or "--transform-errors-only" in only:
         make_transform_errors_golden()
+    if not only or "--live-checks-only" in only:
+        make_live_checks_golden()
     if not only or "--spinnet-only" in only:
         make_spinnet_golden()
     if not only or "--nn-only" in only:

@@ -1,5 +1,5 @@
 """CPU: the oracle (oracle/rap_oracle.py) against the golden vectors produced by the reference's own
-modules, against the live reference when it is mounted, and against analytic known-answer tests."""
+modules (the `*_live_reference*` tests: fixtures of small direct calls into them) and against analytic known-answer tests."""
 import math
 import os
 
@@ -9,7 +9,6 @@ import torch
 
 from conftest import GOLDEN_CASES, LATENT_CASES, MODEL_SIZE_CASES, SWITCH_CASES, load_golden
 from oracle import rap_oracle as O
-from oracle import ref_loader
 from rap_amd import synthetic as S
 
 
@@ -66,25 +65,38 @@ def test_oracle_matches_reference_at_configs0_in_full():
     assert max(errs.values()) < 1e-5, errs
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="/root/reference is only mounted in the build container")
+def _live_checks():
+    """What the reference's own modules returned for the small cases below (oracle/make_golden.py --live-checks-only: the inputs
+    are regenerated from the seeds of its *_check_inputs helpers)."""
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live_reference_checks.npz"))
+    return {k: z[k] for k in z.files}
+
+
 @pytest.mark.parametrize("switch", [{}] + list(SWITCH_CASES.values()) + list(LATENT_CASES.values()),
                          ids=["shipped-config"] + list(SWITCH_CASES) + list(LATENT_CASES))
-def test_oracle_matches_live_reference_modules(switch):
-    cfg = dict(S.RAP_12); cfg["num_layers"] = 2
-    cfg.update(switch)
-    sd = S.make_weights(cfg, 3)
-    inp = S.make_inputs([[40, 77], [130, 20, 65]], seed=99)
-    if cfg.get("in_dim", 0):
-        inp["latent_features"] = torch.randn(inp["x_1"].shape[0], cfg["in_dim"], generator=torch.Generator().manual_seed(5))
+def test_oracle_matches_live_reference_modules(switch, request):
+    from oracle.make_golden import FEATURE_ROW_STRIDE, live_check_inputs
+    name = request.node.callspec.id
+    z = _live_checks()
+    cfg, sd, inp = live_check_inputs(switch)
+    assert abs(float(sum(v.double().sum().item() for v in sd.values())) - float(z[f"model_{name}_weights_checksum"])) < 1e-6
+    assert abs(sum(float(v.double().sum()) for v in inp.values()) - float(z[f"model_{name}_inputs_checksum"])) < 1e-6
     for rigid in ((False, True) if not switch else (True,)):
-        ref = ref_loader.reference_sample(cfg, sd, inp, 3, rigid)
+        tag = f"model_{name}_{'rigid' if rigid else 'free'}"
+        ref = {k: torch.from_numpy(z[f"{tag}_{k}"]) for k in ("end_point_trajectory", "trajectory", "R", "t")}
         mine = O.sample(sd, cfg, inp, 3, rigid)
         for k in ("end_point_trajectory", "trajectory", "R", "t"):
             assert float((ref[k] - mine[k]).abs().max()) < 5e-6, (rigid, k)
-        # the features the sampling call captures on its last model call (modeling.py:678-695): same call index, same values
-        assert ref["features_timestep"] == pytest.approx(1.0 / 3.0)
-        fmax = float(ref["transformer_features"].abs().max())
-        assert float((ref["transformer_features"] - mine["transformer_features"]).abs().max()) < 2e-5 * max(1.0, fmax), rigid
+        # the features the sampling call captures on its last model call (modeling.py:678-695): same call index, same values --
+        # every FEATURE_ROW_STRIDE-th token row element by element, every row through its norm (the bound the element-wise one implies)
+        assert float(z[f"{tag}_features_timestep"]) == pytest.approx(1.0 / 3.0)
+        f = mine["transformer_features"]
+        tol = 2e-5 * max(1.0, float(z[f"{tag}_features_absmax"]))
+        assert abs(float(f.abs().max()) - float(z[f"{tag}_features_absmax"])) < tol, rigid
+        assert float((torch.from_numpy(z[f"{tag}_features_rows"]) - f[::FEATURE_ROW_STRIDE]).abs().max()) < tol, rigid
+        norms = torch.linalg.vector_norm(f.double(), dim=1)
+        assert norms.shape[0] == z[f"{tag}_features_row_norms"].shape[0]
+        assert float((torch.from_numpy(z[f"{tag}_features_row_norms"]) - norms).abs().max()) < tol * f.shape[1] ** 0.5, rigid
 
 
 def test_fp32_oracle_vs_fp64_ground_truth_sets_the_tolerance_scale():
@@ -183,20 +195,18 @@ def test_oracle_selection_matches_reference_golden():
     assert (pp - torch.from_numpy(g["per_part_rmse"])).abs().max().item() < 2e-6
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference not mounted")
 def test_oracle_rigidity_matches_live_reference_function():
-    ref = ref_loader.load_reference()
-    inp = S.make_inputs([[50, 77, 0], [31, 64, 12]], seed=5)     # empty parts only as trailing padding: the reference's split_parts drops empty splits and mis-indexes otherwise
-    cu_b, _ = O.prepare_cu_seqlens(inp)
-    cu = cu_b.long()
-    g = torch.Generator().manual_seed(1)
-    pred = inp["pointclouds"] + 0.05 * torch.randn(inp["pointclouds"].shape, generator=g)
-    R, t = ref.fit_transformations(inp["pointclouds"], pred, inp["points_per_part"], cu)
+    """the reference's fit_transformations + compute_rigidity_rmse (values in the live-checks fixture) vs the restatement, with the
+    reference's poses as input to both"""
+    from oracle.make_golden import rigidity_check_inputs
+    z = _live_checks()
+    inp, cu, pred = rigidity_check_inputs()     # empty parts only as trailing padding: the reference's split_parts drops empty splits and mis-indexes otherwise
+    R, t = torch.from_numpy(z["rigidity_R"]), torch.from_numpy(z["rigidity_t"])
     for per_part in (False, True):
-        for scales in (None, inp["scales"]):
-            a = ref.compute_rigidity_rmse(inp["pointclouds"], pred, R, t, inp["points_per_part"], cu, scales, per_part)
-            b = O.compute_rigidity_rmse(inp["pointclouds"], pred, R, t, inp["points_per_part"], cu, scales, per_part)
-            assert (a - b).abs().max().item() < 1e-6
+        for scaled in (False, True):
+            a = torch.from_numpy(z[f"rigidity_rmse_{int(per_part)}{int(scaled)}"])
+            b = O.compute_rigidity_rmse(inp["pointclouds"], pred, R, t, inp["points_per_part"], cu, inp["scales"] if scaled else None, per_part)
+            assert a.shape == b.shape and (a - b).abs().max().item() < 1e-6
 
 
 # ---------------------------------------------------------------------------------------------
@@ -283,18 +293,17 @@ def test_spinnet_oracle_matches_reference_golden():
     assert counts.min() == 0 and (counts < 512).any() and (counts > 512).any()      # the fixture exercises fill and cap
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference not mounted")
 def test_spinnet_oracle_matches_live_reference():
     from oracle import spinnet_oracle as SO
+    from oracle.make_golden import spinnet_check_inputs
     from rap_amd.spinnet import make_spinnet_weights
+    z = _live_checks()
     sd = make_spinnet_weights(3)
-    g = torch.Generator().manual_seed(9)
-    pts = torch.randn(1200, 3, generator=g) * torch.tensor([1.0, 1.0, 0.15])
-    kpts = pts[:6].clone()
-    ref = ref_loader.reference_spinnet_forward(sd, pts, kpts, 0.6, 11)
-    out = SO.forward(sd, pts, kpts, 0.6, torch.as_tensor(ref["perm"]))
-    assert (out["patches"] - ref["patches"]).abs().max().item() == 0.0
-    assert (out["desc"] - ref["desc"]).abs().max().item() < 2e-6
+    pts, kpts, des_r, _ = spinnet_check_inputs()
+    out = SO.forward(sd, pts, kpts, des_r, torch.as_tensor(z["spinnet_perm"]))
+    assert out["patches"].shape == z["spinnet_patches"].shape
+    assert (out["patches"] - torch.from_numpy(z["spinnet_patches"])).abs().max().item() == 0.0
+    assert (out["desc"] - torch.from_numpy(z["spinnet_desc"])).abs().max().item() < 2e-6
 
 
 # ---------------------------------------------------------------------------------------------
@@ -327,15 +336,13 @@ def test_oracle_voxel_downsample_matches_reference_golden():
         assert np.array_equal(O.voxel_down_sample(p.numpy(), vs), z[f"idx_{vs}"])
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference not mounted")
 def test_oracle_voxel_downsample_matches_live_reference():
-    du = ref_loader.load_reference_dataset_utils()
-    for seed, (n, vs, scale) in enumerate([(1000, 0.1, 1.0), (7, 0.3, 1.0), (1, 0.3, 1.0), (20000, 0.02, 1.0), (30000, 0.5, 40.0)]):
-        g = torch.Generator().manual_seed(seed)
-        p = (torch.rand(n, 3, generator=g) - 0.4) * scale
-        if n == 1:
-            p = p + 0.01                       # a point exactly on its voxel centre makes the reference divide 0 / 0
-        assert np.array_equal(O.voxel_down_sample(p.numpy(), vs), du.voxel_down_sample_torch(p, vs).numpy()), (n, vs)
+    from oracle.make_golden import VOXEL_CHECK_CASES, voxel_check_points, voxel_index_digest
+    z = _live_checks()
+    for seed, (n, vs, scale) in enumerate(VOXEL_CHECK_CASES):
+        idx = O.voxel_down_sample(voxel_check_points(seed, n, scale).numpy(), vs)
+        assert len(idx) == int(z[f"voxel_idx_{seed}_len"]), (n, vs, len(idx))
+        assert voxel_index_digest(idx) == str(z[f"voxel_idx_{seed}_sha256"]), (n, vs)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -377,12 +384,15 @@ def test_oracle_transform_and_collate_matches_reference_golden():
         st = ed
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference not mounted")
 def test_oracle_transform_and_collate_matches_live_reference():
     from oracle.make_golden import collate_samples
+    z = _live_checks()
     samples = collate_samples(seed=9)
-    ref = ref_loader.reference_transform_and_collate(samples, 6, 4)
     got = O.transform_and_collate(samples, 6, 4)
+    # the reference's collated features are a row permutation of the raw ones: the fixture stores that permutation
+    raw = np.concatenate([np.concatenate(s["features"]) for s in samples])
+    ref = {k: torch.from_numpy(z["collate_" + k]) for k in COLLATE_KEYS if k != "features"}
+    ref["features"] = torch.from_numpy(raw[z["collate_features_row_of_raw"]])
     for k in COLLATE_KEYS:
         r, g = ref[k], got[k]
         assert r.shape == g.shape and r.dtype == g.dtype, k
@@ -409,15 +419,12 @@ def test_oracle_adaptive_sample_count_matches_reference_values():
     assert [O.calculate_voxel_coverage(p, 0.25) for p in parts] == ADAPTIVE_EXPECTED[1]
 
 
-@pytest.mark.skipif(not ref_loader.reference_available(), reason="reference not mounted")
 def test_oracle_adaptive_sample_count_matches_live_reference():
-    import importlib, sys
-    ref_loader.load_reference_dataset_utils(); ref_loader._install_pytorch3d_import_stub()
-    sys.modules["pytorch3d.ops"].sample_farthest_points = None
-    m = importlib.import_module("dataset_process.utils.point_sampling_utils")
+    from oracle.make_golden import ADAPTIVE_CHECK_ARGS
+    z = _live_checks()
     parts = adaptive_parts()
-    for vs, ratio, mn, mx in ((0.25, 0.5, 50, 1500), (1.0, 2.0, 10, 100), (0.05, 0.1, 5, 5000)):
-        assert O.calculate_adaptive_sample_count_per_part(parts, vs, ratio, mn, mx) == m.calculate_adaptive_sample_count_per_part(parts, vs, ratio, mn, mx)
+    for i, (vs, ratio, mn, mx) in enumerate(ADAPTIVE_CHECK_ARGS):
+        assert O.calculate_adaptive_sample_count_per_part(parts, vs, ratio, mn, mx) == z[f"adaptive_counts_{i}"].tolist()
 
 
 def test_oracle_statistical_outlier_rule_on_a_known_case():

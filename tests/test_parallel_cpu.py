@@ -175,8 +175,8 @@ def test_shard_by_cost_balances_flops_not_counts():
 
 
 def test_pack_batches_mirrors_the_reference_sampler():
-    """`pack_batches` / `plan_batches(balance="stride")` against the reference's UNMODIFIED DynamicBatchSampler (data/datamodule.py:59-166)
-    when the mount exists, and against fixed expectations everywhere."""
+    """`pack_batches` / `plan_batches(balance="stride")` against fixed expectations and against the batches the reference's UNMODIFIED
+    DynamicBatchSampler (data/datamodule.py:59-166) returned for the same counts (tests/golden/live_reference_checks.npz)."""
     from rap_amd.parallel import pack_batches, plan_batches
     counts = [30, 50, 40, 100, 10, 10, 10, 90, 120, 5]
     assert pack_batches(counts, 100) == [[0, 1], [2], [3], [4, 5, 6], [7], [8], [9]]
@@ -187,26 +187,17 @@ def test_pack_batches_mirrors_the_reference_sampler():
     plan = plan_batches(parts, 2, 100, balance="stride")
     assert plan[1] == [[1], [3], [5, 7], [9]] and plan[0] == [[0, 2, 4, 6], [8], [8], [8]]      # the shorter rank repeats its last batch
     assert len({len(b) for b in plan}) == 1                                                   # every rank takes part in every step
-    from oracle import ref_loader
-    if not ref_loader.reference_available():
-        return
-    dm = ref_loader.load_reference_data().datamodule
-
-    class _DS:
-        def __len__(self):
-            return len(counts)
-
-        def estimate_num_points(self, i):
-            return counts[i]
-
+    # the batches the reference's sampler itself returned for these counts (oracle/make_golden.py --live-checks-only)
+    import json
+    import numpy as np
+    from oracle.make_golden import BATCH_CHECK_COUNTS
+    assert counts == BATCH_CHECK_COUNTS
+    z = np.load(os.path.join(ROOT, "tests", "golden", "live_reference_checks.npz"))
     for drop_last in (False, True):
-        smp = dm.DynamicBatchSampler(_DS(), 100, shuffle=False, drop_last=drop_last, seed=0)
-        assert list(iter(smp)) == pack_batches(counts, 100, drop_last=drop_last)
+        assert json.loads(str(z[f"batch_sampler_drop_last{int(drop_last)}"])) == pack_batches(counts, 100, drop_last=drop_last)
     # two ranks: the reference shards rank-strided and pads the shorter rank with its last batch
     for rank in range(2):
-        smp = dm.DynamicBatchSampler(_DS(), 100, shuffle=False, drop_last=False, seed=0)
-        smp._get_rank_and_size = lambda rank=rank: (rank, 2)
-        assert list(iter(smp)) == plan_batches(parts, 2, 100, balance="stride")[rank], rank
+        assert json.loads(str(z[f"batch_sampler_rank{rank}_of_2"])) == plan_batches(parts, 2, 100, balance="stride")[rank], rank
 
 
 def _worker_ragged(rank, world, port, tmpdir):
