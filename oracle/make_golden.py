@@ -37,10 +37,24 @@ CASES = [
     ("l2_nofeat_rigid", 2, [[90, 33], [45, 45, 45]], 55, 6, 3, True),
     # round 6: in_dim = 64 -- latent point features concatenated into the embedding (embedding.py:107-118,163-166; modeling.py:788)
     ("l2_latent64_rigid", 2, [[70, 51], [40, 120, 33]], 57, 7, 3, True),
+    # every other model width the native model accepts (embed_dim 256 / 768 / 1024 with num_heads = embed_dim / 64, other feature widths):
+    # full features are stored, so the token counts shrink as d grows to keep each fixture under 1 MiB.  w256_latent512 is the corner
+    # where the 16-bit modes' static feature matrix (T, 128 + 512) fp32 outgrows the 8 T d bytes of the GEGLU buffer it lives in
+    # (TP = 215 > 0.8 T at T = 256)
+    ("w256_ragged_rigid", 2, [[37, 64, 90], [50, 119]], 71, 9, 3, True),
+    ("w256_latent512_rigid", 2, [[64, 51], [40, 27, 33]], 73, 10, 3, True),
+    ("w768_emptypart_free", 2, [[40, 1, 29, 0], [33, 37]], 75, 11, 3, False),
+    ("w768_noqknorm_rigid", 2, [[60, 41], [20, 19]], 77, 12, 3, True),
+    ("w1024_ragged_rigid", 2, [[41, 23], [18, 7, 11]], 79, 13, 3, True),
 ]
 # name -> PointCloudDiT keyword overrides
 CASE_SWITCHES = {"l2_noqknorm_rigid": {"qk_norm": False}, "l2_noscale_free": {"scale_emb_on": False},
-                 "l2_nofeat_rigid": {"local_feat_concat_on": False}, "l2_latent64_rigid": {"in_dim": 64}}
+                 "l2_nofeat_rigid": {"local_feat_concat_on": False}, "l2_latent64_rigid": {"in_dim": 64},
+                 "w256_ragged_rigid": {"embed_dim": 256, "num_heads": 4, "local_feat_dim": 4},
+                 "w256_latent512_rigid": {"embed_dim": 256, "num_heads": 4, "local_feat_dim": 4, "in_dim": 512},
+                 "w768_emptypart_free": {"embed_dim": 768, "num_heads": 12, "local_feat_dim": 12},
+                 "w768_noqknorm_rigid": {"embed_dim": 768, "num_heads": 12, "local_feat_dim": 40, "qk_norm": False},
+                 "w1024_ragged_rigid": {"embed_dim": 1024, "num_heads": 16, "local_feat_dim": 40}}
 
 
 def weights_checksum(sd) -> float:
@@ -57,7 +71,7 @@ def main():
         cfg = dict(S.RAP_12); cfg["num_layers"] = L
         cfg.update(CASE_SWITCHES.get(name, {}))
         sd = S.make_weights(cfg, wseed)
-        inp = S.make_inputs(parts, seed=iseed)
+        inp = S.make_inputs(parts, seed=iseed, feat_dim=cfg["local_feat_dim"])
         if cfg.get("in_dim", 0):      # latent point features as a PTv3 encoder would hand them over: (TP, in_dim), O(1) values
             inp["latent_features"] = torch.randn(inp["x_1"].shape[0], cfg["in_dim"], generator=torch.Generator().manual_seed(1000 + iseed))
         ref = ref_loader.reference_sample(cfg, sd, inp, steps, rigid)
@@ -80,6 +94,10 @@ def main():
             # transformer_features captured by the sampling call itself (modeling.py:678-695: model call steps-1, t = dt)
             "sample_features": ref["transformer_features"].numpy(), "sample_features_timestep": np.float64(ref["features_timestep"]),
         }
+        if name.startswith("w"):      # width cases: the configuration travels with the fixture
+            out.update({"embed_dim": np.int64(cfg["embed_dim"]), "num_heads": np.int64(cfg["num_heads"]),
+                        "local_feat_dim": np.int64(cfg["local_feat_dim"]), "in_dim": np.int64(cfg.get("in_dim", 0)),
+                        "qk_norm": np.int64(int(cfg.get("qk_norm", True)))})
         for k, v in inp.items():
             out["in_" + k] = v.numpy()
         path = os.path.join(GOLDEN_DIR, name + ".npz")

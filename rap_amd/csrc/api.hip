@@ -481,7 +481,7 @@ static int eff_dtype(const rap_model* m, size_t rows) {
 struct Workspace {
   float *base, *h, *xn, *qkv, *att, *ffmid, *ax, *v, *mod, *ada_scratch, *xt, *Rc, *tc, *tgrid;
   u16* h16;                            // the residual stream when it is held in fp16 (16-bit modes with resid_dtype = fp16; h is then null)
-  float *hid1, *hid2, *astatic;        // head hidden layers (T,d), (T,d/2) and the static feature matrix (T,128): aliases
+  float *hid1, *hid2, *astatic;        // head hidden layers (T,d), (T,d/2) and the static feature matrix (T,Ks), Ks = 128 + align_up(in_dim, 32): aliases
   u16 *xnh, *qkh, *vth, *atth, *ffmidh; // reduced-precision mode: 16-bit activations (xn/qkv/att/ffmid are then unused)
   float* splitk_h;                      // reduced-precision mode, few-token calls only: fp32 partial planes of the split-K ff2 GEMM (else null)
   int splitk_planes;                    // ... and how many (T, d) planes were reserved there (2 or 4; 0 without the buffer)
@@ -528,7 +528,7 @@ static Workspace carve_workspace(const rap_model* m, int64_t TP, int B, int nseg
     w.xn = (float*)take(T * d * 4);            // also head hidden 1 (TP,d)
     w.qkv = (float*)take(T * 3 * d * 4);
     w.att = (float*)take(T * d * 4);           // also head hidden 2 (TP,d/2)
-    w.ffmid = (float*)take(T * 4 * d * 4);     // also the static feature matrix (TP,128) during prepare
+    w.ffmid = (float*)take(T * 4 * d * 4);     // also the static feature matrix (TP,Ks) during prepare (16 T d >= 4 T Ks bytes for d >= 256)
     w.hid1 = w.xn; w.hid2 = w.att; w.astatic = w.ffmid;
   } else {
     const size_t pl = x2 ? 2 : 1;              // planes per value
@@ -537,7 +537,10 @@ static Workspace carve_workspace(const rap_model* m, int64_t TP, int B, int nseg
     w.qkh = (u16*)take(T * 2 * d * 2 * pl);    // q,k [2][H][T][64]   (x2: [2][H][2 chunks][T][64 physical])
     w.vth = (u16*)take((size_t)w.vt_nblk * 64 * d * 2 * pl);   // [H][vt_nblk][64][64]   (x2: [H][vt_nblk][2 chunks][64][64 physical])
     w.atth = (u16*)take(T * d * 2 * pl);
-    w.ffmidh = (u16*)take(T * 4 * d * 2 * pl); // >= 8*T*d bytes: also hosts the fp32 head hidden layers / static features
+    // >= 8*T*d bytes: also hosts the fp32 head hidden layers and the static feature matrix (T,Ks) fp32 = 4*T*Ks bytes, which is the
+    // larger of the two at d = 256 with in_dim > 384 in the 16-bit modes (pl = 1)
+    const size_t ffmid_bytes = T * 4 * d * 2 * pl, static_bytes = T * (size_t)m->Ks * 4;
+    w.ffmidh = (u16*)take(ffmid_bytes > static_bytes ? ffmid_bytes : static_bytes);
     w.hid1 = (float*)w.ffmidh;                 // (T,d) fp32   = 4*T*d bytes
     w.hid2 = w.hid1 + T * d;                   // (T,d/2) fp32 = 2*T*d bytes
     w.astatic = (float*)w.ffmidh;

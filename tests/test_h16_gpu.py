@@ -162,8 +162,19 @@ def test_gemm_h16_qkv_split_and_transposed_v(lib, dev, dt, M):
 def test_gemm_h16_qkv_with_fused_qknorm(lib, dev, dt, M, K, q_mul):
     """EPI_H_QKV_NORM: q and k = MultiHeadRMSNorm(x W^T) (norm.py:28-33: normalize * gamma * 8; q times q_mul / 8 instead) from the fp32
     accumulators, rounded once; v exactly as the un-fused epilogue.  Reference: fp64 on the same rounded operands."""
+    _check_gemm_h16_qkv_with_fused_qknorm(lib, dev, dt, M, K, q_mul, 4)
+
+
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("M", [37, 1000])
+@pytest.mark.parametrize("H", [12, 16])
+def test_gemm_h16_qkv_with_fused_qknorm_at_other_head_counts(lib, dev, dt, M, H):
+    """N = 192 H at the head counts of d = 768 / 1024 (K = d): a few-row M (128 x 128 tiles) and an M that is not a multiple of 256"""
+    _check_gemm_h16_qkv_with_fused_qknorm(lib, dev, dt, M, 64 * H, 8.0, H)
+
+
+def _check_gemm_h16_qkv_with_fused_qknorm(lib, dev, dt, M, K, q_mul, H):
     g = torch.Generator().manual_seed(15)
-    H = 4
     N = 3 * H * 64
     A = to_h(torch.randn(M, K, generator=g), dt); W = to_h(torch.randn(N, K, generator=g) / K ** 0.5, dt)
     gq, gk = torch.rand(H, 64, generator=g) + 0.5, torch.rand(H, 64, generator=g) + 0.5
@@ -329,8 +340,23 @@ def test_gemm_h16_splitk_of_the_residual_gemm(lib, dev, dt, epi, M, splits):
     split over 4 (<= 64 tiles) or 2 blocks per tile and a combine pass forms resid + (bias + partials) in a fixed order.  Checked: the
     split count the workspace query implies, the result within one rounding of the fp64 evaluation, agreement with the unsplit kernel
     (tuning key 6 = 0) to fp32-association level, run-to-run determinism, and that a short workspace is refused."""
+    _check_gemm_h16_splitk_of_the_residual_gemm(lib, dev, dt, epi, M, 512, 2048, splits)
+
+
+# ff2 of the other model widths: N = d, K = 4 d = 1024 / 3072 / 4096, at M that give 4, 2 and 1 splits
+WIDTH_FF2 = [(100, 256, 1024, 4), (5000, 256, 1024, 2), (300, 768, 3072, 4), (2048, 768, 3072, 2), (777, 1024, 4096, 4),
+             (2048, 1024, 4096, 2), (3000, 1024, 4096, 1)]
+
+
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("epi", [1, 7], ids=["fp32-stream", "fp16-stream"])
+@pytest.mark.parametrize("M,N,K,splits", WIDTH_FF2, ids=[f"M{m}-N{n}-K{k}" for m, n, k, _ in WIDTH_FF2])
+def test_gemm_h16_splitk_of_the_residual_gemm_at_other_widths(lib, dev, dt, epi, M, N, K, splits):
+    _check_gemm_h16_splitk_of_the_residual_gemm(lib, dev, dt, epi, M, N, K, splits)
+
+
+def _check_gemm_h16_splitk_of_the_residual_gemm(lib, dev, dt, epi, M, N, K, splits):
     g = torch.Generator().manual_seed(43)
-    N, K = 512, 2048
     need = lib.rap_gemm_h16_splitk_workspace_bytes(M, N, K)
     assert need == (splits * M * N * 4 if splits > 1 else 0)
     A = to_h(torch.randn(M, K, generator=g), dt); W = to_h(torch.randn(N, K, generator=g) / K ** 0.5, dt)
@@ -424,7 +450,7 @@ def logit_bound(q, k):
 
 @pytest.mark.parametrize("bounded", [False, True], ids=["online-max", "bounded"])
 @pytest.mark.parametrize("dt", [1, 2])
-@pytest.mark.parametrize("H", [1, 8])
+@pytest.mark.parametrize("H", [1, 8, 4, 12, 16])      # (4 / 12 / 16: the head counts of d = 256 / 768 / 1024)
 def test_attention_h16_ragged_segments(lib, dev, dt, H, bounded):
     g = torch.Generator().manual_seed(11 + H)
     lens = [1, 63, 64, 65, 300, 0, 257, 1000, 31, 512]          # unaligned starts, empty segment, multi-block segments
@@ -500,8 +526,19 @@ def test_attention_h16_full_size_agrees_with_fp32_kernel(lib, dev, dt):
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dt", [1, 2])
 def test_layernorm_h16(lib, dev, dt):
+    _check_layernorm_h16(lib, dev, dt, 512)
+
+
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("d", [256, 768, 1024])
+def test_layernorm_h16_at_other_widths(lib, dev, dt, d):
+    """d / 256 = 1, 3, 4 float4 per lane (layernorm_h16_kernel<NV>)"""
+    _check_layernorm_h16(lib, dev, dt, d)
+
+
+def _check_layernorm_h16(lib, dev, dt, d):
     g = torch.Generator().manual_seed(2)
-    TP, d, rows = 777, 512, 3
+    TP, rows = 777, 3
     x = torch.randn(TP, d, generator=g) * 3 + 0.5
     mod = torch.randn(rows, 4, 2 * d, generator=g) * 0.3
     token_row = torch.randint(0, rows, (TP,), generator=g, dtype=torch.int32)
@@ -525,8 +562,18 @@ def test_layernorm_h16(lib, dev, dt):
 
 @pytest.mark.parametrize("dt", [1, 2])
 def test_qknorm_h16(lib, dev, dt):
+    _check_qknorm_h16(lib, dev, dt, 8)
+
+
+@pytest.mark.parametrize("dt", [1, 2])
+@pytest.mark.parametrize("H", [4, 12, 16])
+def test_qknorm_h16_at_other_head_counts(lib, dev, dt, H):
+    _check_qknorm_h16(lib, dev, dt, H)
+
+
+def _check_qknorm_h16(lib, dev, dt, H):
     g = torch.Generator().manual_seed(6)
-    TP, H = 301, 8
+    TP = 301
     qk = to_h(torch.randn(2, H, TP, 64, generator=g) * 2, dt)
     gq, gk = torch.rand(H, 64, generator=g) + 0.5, torch.rand(H, 64, generator=g) + 0.5
     buf = qk.to(dev).clone()

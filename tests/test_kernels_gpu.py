@@ -117,6 +117,45 @@ def test_gemm_qkv_headmajor_scatter(lib, dev):
     assert (C.cpu().double() - ref).abs().max().item() < 2e-5
 
 
+# the fp32 GEMM shapes of the other model widths at ragged and few-row M: residual GEMMs (N = d, K = d or 4d = 1024 / 3072 / 4096), the
+# head's second layer (N = d / 2 = 128 / 384, bias + SiLU) and the head-major QKV scatter (N = 3 * 64 * H for 4 / 12 / 16 heads)
+WIDTH_GEMMS = [(1, 256, 1024), (1, 768, 3072), (1, 1024, 4096), (1, 1024, 1024), (2, 128, 256), (2, 384, 768)]
+
+
+@pytest.mark.parametrize("M", [100, 777])
+@pytest.mark.parametrize("epi,N,K", WIDTH_GEMMS, ids=[f"{'resid' if e == 1 else 'silu'}-N{n}-K{k}" for e, n, k in WIDTH_GEMMS])
+def test_gemm_residual_and_head_shapes_of_the_other_widths(lib, dev, epi, N, K, M):
+    g = torch.Generator().manual_seed(M + N + K)
+    A = torch.randn(M, K, generator=g); W = torch.randn(N, K, generator=g) / K ** 0.5; b = torch.randn(N, generator=g)
+    base = A.double() @ W.double().T + b.double()
+    Ad, Wd, bd = A.to(dev), W.to(dev), b.to(dev)
+    if epi == 1:
+        h = torch.randn(M, N, generator=g) * 3
+        C = h.to(dev).clone()
+        gemm(lib, dev, 1, Ad, Wd, C, M, N, K, bias=bd, resid=C)        # in place, as the model runs it
+        ref = h.double() + base
+    else:
+        C = torch.full((M, N), float("nan"), device=dev)
+        gemm(lib, dev, 2, Ad, Wd, C, M, N, K, bias=bd)
+        ref = F.silu(base)
+    err = (C.cpu().double() - ref).abs().max().item()
+    # the bound of test_gemm_bias_matches_fp64 (K <= 2048), grown as sqrt(K) with the fp32 fma chain beyond it
+    assert err < 2e-5 * max(1.0, (K / 2048) ** 0.5), err
+
+
+@pytest.mark.parametrize("M", [150, 1000])
+@pytest.mark.parametrize("H", [4, 12, 16])
+def test_gemm_qkv_headmajor_scatter_at_other_head_counts(lib, dev, H, M):
+    g = torch.Generator().manual_seed(5 + H)
+    K = 64 * H
+    N = 3 * H * 64
+    A = torch.randn(M, K, generator=g); W = torch.randn(N, K, generator=g) / K ** 0.5
+    ref = (A.double() @ W.double().T).reshape(M, 3, H, 64).permute(1, 2, 0, 3)   # [3][H][M][64]
+    C = torch.full((3, H, M, 64), float("nan"), device=dev)
+    gemm(lib, dev, 4, A.to(dev), W.to(dev), C, M, N, K, heads=H)
+    assert (C.cpu().double() - ref).abs().max().item() < 2e-5
+
+
 @pytest.mark.parametrize("epi,M,N,K", [(0, 16384, 2048, 512), (1, 65536, 512, 2048), (1, 65536, 512, 512), (2, 65536, 512, 512), (3, 16384, 2048, 512),
                                        (4, 32768, 1536, 512)])
 def test_persistent_fp32_gemm_is_bit_identical_to_the_one_tile_per_block_kernel(lib, dev, epi, M, N, K):
@@ -185,7 +224,7 @@ def run_attention(lib, dev, qkv_thd, cu, bound=None):
 
 
 @pytest.mark.parametrize("bounded", [False, True], ids=["online-max", "bounded"])
-@pytest.mark.parametrize("H", [1, 8])
+@pytest.mark.parametrize("H", [1, 8, 4, 12, 16])      # (4 / 12 / 16: the head counts of d = 256 / 768 / 1024)
 def test_attention_ragged_segments_match_fp64(lib, dev, H, bounded):
     g = torch.Generator().manual_seed(11 + H)
     cu = torch.tensor([0, 1, 38, 38, 294, 600, 1624, 1657])     # lengths 1, 37, 0, 256, 306, 1024, 33
@@ -280,8 +319,18 @@ def test_attention_full_size_properties(lib, dev):
 # normalisation / embedding / adaLN
 # ---------------------------------------------------------------------------------------------
 def test_layernorm_modulate_and_affine(lib, dev):
+    _check_layernorm_modulate_and_affine(lib, dev, 512)
+
+
+@pytest.mark.parametrize("d", [256, 768, 1024])
+def test_layernorm_modulate_and_affine_at_other_widths(lib, dev, d):
+    """the other model widths the library accepts: d / 256 = 1, 3, 4 float4 per lane"""
+    _check_layernorm_modulate_and_affine(lib, dev, d)
+
+
+def _check_layernorm_modulate_and_affine(lib, dev, d):
     g = torch.Generator().manual_seed(6)
-    TP, d, B = 1001, 512, 3
+    TP, B = 1001, 3
     x = torch.randn(TP, d, generator=g) * 3 + 0.5
     mod = torch.randn(B, 4, 2 * d, generator=g)            # rows = samples, 4 LNs per row
     cu = torch.tensor([0, 400, 401, 1001])
@@ -311,8 +360,17 @@ def test_layernorm_modulate_and_affine(lib, dev):
 
 
 def test_qknorm(lib, dev):
+    _check_qknorm(lib, dev, 8)
+
+
+@pytest.mark.parametrize("H", [4, 12, 16])
+def test_qknorm_at_other_head_counts(lib, dev, H):
+    _check_qknorm(lib, dev, H)
+
+
+def _check_qknorm(lib, dev, H):
     g = torch.Generator().manual_seed(7)
-    TP, H = 333, 8
+    TP = 333
     qkv = torch.randn(3, H, TP, 64, generator=g)
     gq, gk = torch.rand(H, 64, generator=g) + 0.5, torch.rand(H, 64, generator=g) + 0.5
     qkv[0, 3, 5] = 0.0    # an all-zero row exercises the eps clamp
@@ -368,7 +426,21 @@ def small_model(dev):
 
 
 def test_adaln_table_matches_oracle(lib, dev, small_model):
-    cfg, sd, m = small_model
+    _check_adaln_table(lib, dev, *small_model)
+
+
+@pytest.mark.parametrize("d", [256, 768, 1024])
+def test_adaln_table_matches_oracle_at_other_widths(lib, dev, d):
+    import rap_amd
+    cfg = dict(S.RAP_12); cfg.update(embed_dim=d, num_heads=d // 64, num_layers=2, local_feat_dim=8)
+    sd = S.make_weights(cfg, 4)
+    m = rap_amd.PointCloudDiT(in_dim=0, out_dim=3, embed_dim=d, num_layers=2, num_heads=d // 64, local_feat_dim=8)
+    m.load_state_dict(sd)
+    m.to(dev)
+    _check_adaln_table(lib, dev, cfg, sd, m)
+
+
+def _check_adaln_table(lib, dev, cfg, sd, m):
     rows, L, d = 5, cfg["num_layers"], cfg["embed_dim"]
     t = torch.tensor([1.0, 0.95, 0.5, 0.05, 0.3])
     out = torch.empty((rows, 2 * L, 2 * d), device=dev)

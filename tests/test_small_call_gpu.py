@@ -140,28 +140,12 @@ def test_key_group_attention_kernel_against_fp64(dev, dt, mode):
     with tuning key 20 forcing the key-group kernel: ragged segments from 1 to 1000 keys incl. an empty one (groups without a tile,
     unaligned starts, masks in first and last tiles), online and bounded softmax; single-key segments return v; one dominant key in the
     last / first / a middle tile (the groups' running maxima differ by far more than the deferred-rescale threshold when they meet)."""
-    import torch.nn.functional as F
     import test_h16_gpu as T
     lib = _lib.load()
     try:
         assert lib.rap_set_tuning(20, mode) == 0
         for H in (1, 8):
-            g = torch.Generator().manual_seed(11 + H)
-            lens = [1, 63, 64, 65, 300, 0, 257, 1000, 31, 512, 129, 191]
-            cu = torch.tensor([0] + lens).cumsum(0)
-            TP = int(cu[-1])
-            q = F.normalize(torch.randn(H, TP, 64, generator=g), dim=-1) * 8 * (0.5 + torch.rand(H, 1, 64, generator=g))
-            k = F.normalize(torch.randn(H, TP, 64, generator=g), dim=-1) * 8 * (0.5 + torch.rand(H, 1, 64, generator=g))
-            v = torch.randn(H, TP, 64, generator=g)
-            ref = T.attention_ref64(q, k, v, cu, dt)
-            for bounded in (False, True):
-                out = T.run_attention_h(lib, dev, dt, q, k, v, cu, bound=T.logit_bound(q, k) if bounded else None)
-                assert not torch.isnan(out.float()).any()
-                err = (out.double() - ref).abs().max().item()
-                print(f"key groups, mode {mode} dt={dt} H={H} bounded={bounded}: max abs err vs fp64 {err:.2e}")
-                assert err < 8 * T.ULP[dt], (H, bounded, err)
-                again = T.run_attention_h(lib, dev, dt, q, k, v, cu, bound=T.logit_bound(q, k) if bounded else None)
-                assert torch.equal(out.view(torch.int16), again.view(torch.int16))              # fixed merge order: run-to-run identical
+            _check_ragged_attention_h16(lib, dev, dt, H, mode)
         g = torch.Generator().manual_seed(3)
         TP, H = 130, 2
         q, k, v = (torch.randn(H, TP, 64, generator=g) for _ in range(3))
@@ -177,6 +161,43 @@ def test_key_group_attention_kernel_against_fp64(dev, dt, mode):
                 out = T.run_attention_h(lib, dev, dt, q, k, v, torch.tensor([0, L]), bound=bound)
                 err = (out.double() - ref).abs().max().item()
                 assert err < 8 * T.ULP[dt], (spike_at, bound is not None, err)
+    finally:
+        assert lib.rap_set_tuning(20, 1) == 0
+
+
+def _check_ragged_attention_h16(lib, dev, dt, H, mode):
+    """ragged segments from 1 to 1000 keys incl. an empty one, online and bounded softmax, against fp64 on the rounded operands; run-to-run
+    identical (tuning key 20 already set to `mode`)"""
+    import torch.nn.functional as F
+    import test_h16_gpu as T
+    g = torch.Generator().manual_seed(11 + H)
+    lens = [1, 63, 64, 65, 300, 0, 257, 1000, 31, 512, 129, 191]
+    cu = torch.tensor([0] + lens).cumsum(0)
+    TP = int(cu[-1])
+    q = F.normalize(torch.randn(H, TP, 64, generator=g), dim=-1) * 8 * (0.5 + torch.rand(H, 1, 64, generator=g))
+    k = F.normalize(torch.randn(H, TP, 64, generator=g), dim=-1) * 8 * (0.5 + torch.rand(H, 1, 64, generator=g))
+    v = torch.randn(H, TP, 64, generator=g)
+    ref = T.attention_ref64(q, k, v, cu, dt)
+    for bounded in (False, True):
+        out = T.run_attention_h(lib, dev, dt, q, k, v, cu, bound=T.logit_bound(q, k) if bounded else None)
+        assert not torch.isnan(out.float()).any()
+        err = (out.double() - ref).abs().max().item()
+        print(f"key groups, mode {mode} dt={dt} H={H} bounded={bounded}: max abs err vs fp64 {err:.2e}")
+        assert err < 8 * T.ULP[dt], (H, bounded, err)
+        again = T.run_attention_h(lib, dev, dt, q, k, v, cu, bound=T.logit_bound(q, k) if bounded else None)
+        assert torch.equal(out.view(torch.int16), again.view(torch.int16))              # fixed merge order: run-to-run identical
+
+
+@pytest.mark.parametrize("mode", [64, 128, 66, 130], ids=["64-rows", "128-rows", "64-rows-x-4-key-groups", "128-rows-x-2-key-groups"])
+@pytest.mark.parametrize("dt", [1, 2], ids=["bf16", "f16"])
+@pytest.mark.parametrize("H", [4, 12, 16])
+def test_few_token_attention_kernels_at_other_head_counts_against_fp64(dev, H, dt, mode):
+    """the few-token forms of the 16-bit attention (tuning key 20: 64 / 128-row work items, with and without key groups) at the head
+    counts of d = 256 / 768 / 1024"""
+    lib = _lib.load()
+    try:
+        assert lib.rap_set_tuning(20, mode) == 0
+        _check_ragged_attention_h16(lib, dev, dt, H, mode)
     finally:
         assert lib.rap_set_tuning(20, 1) == 0
 

@@ -190,8 +190,18 @@ def test_x2_gemm_geglu_epilogue(lib, dev):
 def test_x2_gemm_qkv_with_fused_qknorm(lib, dev, M, K):
     """q, k = MultiHeadRMSNorm(x W^T) as head / tail planes [2][H][2 chunks][M][64]; v as the paired transposed image
     [H][blk][2 chunks][64 d][64]; against fp64 on the original operands."""
+    _check_x2_gemm_qkv_with_fused_qknorm(lib, dev, M, K, 4 if M < 60000 else 8)
+
+
+@pytest.mark.parametrize("M", [37, 1000])
+@pytest.mark.parametrize("H", [12, 16])
+def test_x2_gemm_qkv_with_fused_qknorm_at_other_head_counts(lib, dev, M, H):
+    """N = 192 H at the head counts of d = 768 / 1024 (K = d): a few-row M (128 x 128 tiles) and an M that is not a multiple of 256"""
+    _check_x2_gemm_qkv_with_fused_qknorm(lib, dev, M, 64 * H, H)
+
+
+def _check_x2_gemm_qkv_with_fused_qknorm(lib, dev, M, K, H):
     g = torch.Generator().manual_seed(15)
-    H = 4 if M < 60000 else 8
     N = 3 * H * 64
     A = torch.randn(M, K, generator=g); W = torch.randn(N, K, generator=g) / K ** 0.5 * 0.3
     gq, gk = torch.rand(H, 64, generator=g) + 0.5, torch.rand(H, 64, generator=g) + 0.5
@@ -277,7 +287,7 @@ def attention_ref64(q, k, v, cu):
 
 
 @pytest.mark.parametrize("wpe", [2, 4], ids=["one-block-per-cu", "two-blocks-per-cu"])
-@pytest.mark.parametrize("H", [1, 8])
+@pytest.mark.parametrize("H", [1, 8, 4, 12, 16])      # (4 / 12 / 16: the head counts of d = 256 / 768 / 1024)
 def test_x2_attention_ragged_segments(lib, dev, H, wpe):
     g = torch.Generator().manual_seed(11 + H)
     lens = [1, 63, 64, 65, 300, 0, 257, 1000, 31, 512]          # unaligned starts, empty segment, multi-block segments
@@ -357,8 +367,18 @@ def test_x2_attention_full_size_agrees_with_fp64_on_sampled_rows(lib, dev):
 # LayerNorm
 # ---------------------------------------------------------------------------------------------
 def test_x2_layernorm_writes_head_and_tail_planes(lib, dev):
+    _check_x2_layernorm(lib, dev, 512)
+
+
+@pytest.mark.parametrize("d", [256, 768, 1024])
+def test_x2_layernorm_at_other_widths(lib, dev, d):
+    """d / 256 = 1, 3, 4 float4 per lane (layernorm_x2_kernel<NV>)"""
+    _check_x2_layernorm(lib, dev, d)
+
+
+def _check_x2_layernorm(lib, dev, d):
     g = torch.Generator().manual_seed(4)
-    TP, d, rows = 1001, 512, 3
+    TP, rows = 1001, 3
     x = torch.randn(TP, d, generator=g) * 3 + 0.5
     mod = torch.randn(rows, 2 * d, generator=g) * 0.3
     tok = torch.randint(0, rows, (TP,), generator=g, dtype=torch.int32)
