@@ -1,5 +1,11 @@
 """GPU parity tests of the MiniSpinNet local feature extractor through the C ABI, against the
-fixture produced by the reference's own module and against the CPU oracle (oracle/spinnet_oracle.py)."""
+fixture produced by the reference's own module and against the CPU oracle (oracle/spinnet_oracle.py).
+
+Sizes: the reference fixtures hold 16 keypoints of a 3 000-point cloud (M = 2 240 convolution rows), the fresh-cloud test 13
+keypoints in chunks of 5 (M = 700 / 420), the yaw property 256 keypoints of 20 000 points.  The realistic sizes -- 4 500 keypoints of
+50 000 points at the default chunk of 2 048 (M = 286 720), both convolution paths, both alignment modes, the device permutation --
+and the constructed edges (in-radius counts 0 ... 2 200, N = 1 ... 4 099, FPS ties and 20 000 of 100 000 picks, outlier removal at the
+LDS tile boundary and at 100 000 points) are in tests/test_preproc_scale_gpu.py."""
 import os
 
 import numpy as np
@@ -226,7 +232,8 @@ def test_statistical_outlier_removal_matches_the_restated_open3d_rule():
         assert idx.cpu().tolist() == sorted(idx.cpu().tolist())
         assert 0 < len(got) < 6150 and len(want - got) <= len(edge)
     few, idx_few = remove_statistical_outlier(pts[:5].to(dev), nb_neighbors=20)       # fewer points than neighbours: k = N
-    assert idx_few.numel() <= 5
+    assert idx_few.cpu().tolist() == O.remove_statistical_outlier(pts[:5].numpy(), 20, 2.5)[0].tolist()
+    assert torch.equal(few.cpu(), pts[:5][idx_few.cpu()])
 
 
 def test_adaptive_sample_count_matches_the_reference_values():
