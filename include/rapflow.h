@@ -29,7 +29,8 @@ extern "C" {
  * round 3 without a bump; the fp16-residual epilogue of rap_gemm_h16 moved from 6 to 7 and 6 is refused; rap_poison_on_flag is new;
  * round 5, version 5: compute dtype 3 (split precision) and the rap_x2_* entry points are new, nothing was removed or re-numbered;
  * round 6, version 6: additive -- the *_latent entry points (in_dim > 0), rap_transform_errors, tuning keys 18 / 19 / 20; the scratch of the
- * kernel-level attention entry points grew by a sanitised copy of cu_seqlens (rap_attention_workspace_bytes reports it)). */
+ * kernel-level attention entry points grew by a sanitised copy of cu_seqlens (rap_attention_workspace_bytes reports it)).  Still version
+ * 6, additive: rap_pair_metrics_workspace_bytes, rap_pair_metrics and rap_transform_errors_direct (the evaluator's metrics table). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -238,6 +239,28 @@ int rap_chamfer_rmse(const float* pointclouds_gt, const float* pointclouds_pred,
 int rap_correspondence_rmse(const float* source_gt, const float* target_gt, const float* source_pred, const float* target_pred,
                             int32_t n_source, int32_t n_target, float distance_threshold, float* out3, void* ws, size_t ws_bytes,
                             void* stream);
+
+/* Scan-pair metrics of a whole packed batch with P = 2, as Evaluator._compute_metrics forms them per pair in a Python loop (reference
+ * eval/evaluator.py:124-248 with compute_correspondence_rmse, eval/metrics.py:386-469, and compute_approximate_transform_error, :487-508,
+ * under the identity covariance).  Per sample b: source = part 0, target = part 1, every cloud multiplied by scales[b] (metres); a
+ * correspondence is a source_gt point whose nearest target_gt point (first arg-min) lies within distance_threshold (the evaluator passes
+ * 0.05).  R_pred / t_pred given ("transformed"): `cloud` = the input clouds, the compared clouds are (cloud s) R_pred^T + t_pred s per part;
+ * both NULL ("direct"): `cloud` = the predicted clouds, compared as they are.  out4 (B,4) = {RMS of |src_i - tgt_nn(i)| over the
+ * correspondences (inf if none), their number / n_source, transform error, their number}; transform error = sqrt(|dt|^2 + |q_xyz(dR)|^2)
+ * with R_rel = R_tgt R_src^T, t_rel = s t_tgt - R_rel (s t_src), dR = R_rel_gt^T R_rel_pred, dt = t_rel_pred - t_rel_gt (inf in direct
+ * mode).  A sample with an empty part gives {inf, 0, inf, 0}.  pointclouds_gt, cloud (TP,3); points_per_part (B,2) int64; cu_batch (B+1,)
+ * int32; scales (B,); R_* (B,2,3,3), t_* (B,2,3).  Deterministic (no floating-point atomics); three launches, no host read.
+ * ws >= rap_pair_metrics_workspace_bytes(TP, B). */
+size_t rap_pair_metrics_workspace_bytes(int64_t n_points, int32_t B);
+int rap_pair_metrics(const float* pointclouds_gt, const float* cloud, const int64_t* points_per_part, const int32_t* cu_batch,
+                     const float* scales, const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred, int32_t B,
+                     int64_t TP, float distance_threshold, float* out4, void* ws, size_t ws_bytes, void* stream);
+/* Replaces compute_transform_errors_direct (reference eval/metrics.py:305-383): rap_transform_errors without the anchor frame -- every
+ * non-empty part counts, delta_R = R_gt^T R_pred, delta_t = (t_pred - t_gt) * scale[b]; same shapes, outputs and NULL rules as
+ * rap_transform_errors (per-part errors are 0 for empty parts; the means are over the non-empty parts, NaN for a sample without one). */
+int rap_transform_errors_direct(const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred,
+                                const int64_t* points_per_part, const int64_t* matched_part_ids, const float* scale, int32_t B, int32_t P,
+                                float* rot_err_per_part, float* trans_err_per_part, float* rot_err_mean, float* trans_err_mean, void* stream);
 
 /* ---- MiniSpinNet local feature extractor (the step before the path) ----
  * Replaces MiniSpinNet.forward (reference dataset_process/utils/spinnet/patch_embedder.py:49-183 with patchnet.py:16-84 and

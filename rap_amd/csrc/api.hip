@@ -1579,6 +1579,45 @@ extern "C" int rap_correspondence_rmse(const float* source_gt, const float* targ
                                     distance_threshold, out3, w.d2a, w.nn, w.items);
 }
 
+// batched scan-pair metrics of the evaluator + compute_transform_errors_direct: see pair_metrics.hip
+struct PairWs { NnWork* items; void* partials; void* ranges; size_t total; };
+static PairWs carve_pair(int64_t n, int B, char* basep) {
+  PairWs w; size_t off = 0;
+  auto take = [&](size_t bytes) { char* r = basep ? basep + off : nullptr; off += align_up(bytes, 256); return r; };
+  const size_t max_items = nn_max_items((long)n, B);
+  w.items = (NnWork*)take(max_items * sizeof(NnWork));
+  w.partials = take(max_items * 16);
+  w.ranges = take((size_t)B * 16);
+  w.total = off;
+  return w;
+}
+extern "C" size_t rap_pair_metrics_workspace_bytes(int64_t n_points, int32_t B) {
+  return (n_points < 0 || B < 0) ? 0 : carve_pair(n_points, B, nullptr).total;
+}
+extern "C" int rap_pair_metrics(const float* pointclouds_gt, const float* cloud, const int64_t* points_per_part, const int32_t* cu_batch,
+                                const float* scales, const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred,
+                                int32_t B, int64_t TP, float distance_threshold, float* out4, void* ws, size_t ws_bytes, void* stream) {
+  if (!pointclouds_gt || !cloud || !points_per_part || !cu_batch || !scales || !R_gt || !t_gt || !out4 || B <= 0 || TP <= 0 ||
+      TP > 0x7fffffffLL / 8 || !(distance_threshold >= 0.0f))
+    return RAP_ERR_INVALID;
+  if ((R_pred == nullptr) != (t_pred == nullptr)) return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  PairWs w = carve_pair(TP, B, (char*)ws);
+  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_pair_metrics((hipStream_t)stream, pointclouds_gt, cloud, points_per_part, cu_batch, scales, R_gt, t_gt, R_pred, t_pred, B,
+                             (long)TP, distance_threshold, out4, w.items, w.partials, w.ranges);
+}
+extern "C" int rap_transform_errors_direct(const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred,
+                                           const int64_t* points_per_part, const int64_t* matched_part_ids, const float* scale, int32_t B,
+                                           int32_t P, float* rot_err_per_part, float* trans_err_per_part, float* rot_err_mean,
+                                           float* trans_err_mean, void* stream) {
+  if (!R_gt || !t_gt || !R_pred || !t_pred || !points_per_part || !rot_err_per_part || !trans_err_per_part || !rot_err_mean ||
+      !trans_err_mean || B <= 0 || P <= 0)
+    return RAP_ERR_INVALID;
+  return launch_transform_errors_direct((hipStream_t)stream, R_gt, t_gt, R_pred, t_pred, points_per_part, matched_part_ids, scale, B, P,
+                                        rot_err_per_part, trans_err_per_part, rot_err_mean, trans_err_mean);
+}
+
 extern "C" int rap_farthest_point_sampling(const float* points, const int32_t* cloud_start, const int32_t* cloud_len,
                                            const int32_t* k_per_cloud, const int32_t* start_idx, int32_t n_clouds, int32_t k_max,
                                            int32_t* indices_out, float* dist_ws, void* stream) {

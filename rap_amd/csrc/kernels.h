@@ -247,6 +247,15 @@ int launch_chamfer_rmse(hipStream_t stream, const float* gt, const float* pred, 
 int launch_correspondence_rmse(hipStream_t stream, const float* source_gt, const float* target_gt, const float* source_pred,
                                const float* target_pred, int Ns, int Nt, float thr, float* out3, float* d2, int32_t* nn, NnWork* items);
 
+// batched scan-pair metrics of the evaluator and the anchor-free pose errors (pair_metrics.hip; reference eval/evaluator.py:124-248,
+// eval/metrics.py:305-383, 487-508).  items: nn_max_items(TP, B) NnWork; partials: 16 bytes per item; ranges: 16 bytes per sample
+int launch_pair_metrics(hipStream_t stream, const float* gt, const float* cloud, const int64_t* ppp, const int32_t* cu_batch,
+                        const float* scales, const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred, int B, long TP,
+                        float thr, float* out4, NnWork* items, void* partials, void* ranges);
+int launch_transform_errors_direct(hipStream_t stream, const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred,
+                                   const int64_t* ppp, const int64_t* matched, const float* scale, int B, int P, float* rot_pp,
+                                   float* trans_pp, float* rot_mean, float* trans_mean);
+
 // farthest point sampling (fps.hip; reference dataset_process/utils/point_sampling_utils.py:263-305)
 int launch_fps(hipStream_t stream, const float* pts, const int32_t* cloud_start, const int32_t* cloud_len, const int32_t* Ks,
                const int32_t* starts, int C, int Kmax,

@@ -1,4 +1,8 @@
-"""Host-side mirror of the reference's transform writer.
+"""Host-side mirror of the reference's evaluator: the metrics table and the transform writer.
+
+``Evaluator.compute_metrics`` is ``Evaluator._compute_metrics`` (``rectified_point_flow/eval/evaluator.py:30-250``): the same keys in
+the same order, every value a (B,) fp32 device tensor, and no host synchronisation -- the reference loops over the B pairs with
+``.cpu()`` / ``.item()`` in the loop, here the pair block is one call (``metrics.compute_pair_metrics``).
 
 ``save_transformation_files`` writes the same ``*_transform.txt`` files, names and number format as
 ``Evaluator._save_transformation_files`` (``rectified_point_flow/eval/evaluator.py:383-490``; consumed by
@@ -13,6 +17,8 @@ import torch
 
 from . import _lib
 from .flow_model import _f32c, _require_cuda
+from .metrics import compute_cd, compute_pair_metrics, compute_transform_errors
+from .selection import compute_rigidity_rmse
 
 
 def compute_relative_transforms(rotations_pred, translations_pred, rotations_gt, translations_gt, scales, points_per_part,
@@ -67,3 +73,92 @@ def save_transformation_files(data: dict, sample_dir, dataset_name: str, sample_
                     f.write(" ".join(f"{val:12.8f}" for val in row) + "\n")
             written.append(path)
     return written
+
+
+class Evaluator:
+    """Drop-in for the metric side of ``rectified_point_flow.eval.evaluator.Evaluator``.  ``model`` and the saving options of the
+    reference constructor are accepted and kept; the PLY / JSON writers are host I/O and not part of this package
+    (``save_transformation_files`` above writes the transform files)."""
+
+    PAIR_DISTANCE_THRESHOLD = 0.05          # evaluator.py:189, 210: 5 cm, hard-coded there
+
+    def __init__(self, model=None, save_pointcloud_parts: bool = False, save_merged_pointcloud_steps: bool = False,
+                 max_samples_per_batch: int | None = None, rmse_eval_on: bool = False, rmse_eval_on_transformed: bool = True,
+                 folder_suffix: str | None = None, save_json: bool = True):
+        self.model = model
+        self.save_pointcloud_parts = save_pointcloud_parts
+        self.save_merged_pointcloud_steps = save_merged_pointcloud_steps
+        self.max_samples_per_batch = max_samples_per_batch
+        self.rmse_eval_on = rmse_eval_on
+        self.rmse_eval_on_transformed = rmse_eval_on_transformed
+        self.folder_suffix = folder_suffix
+        self.save_json = save_json
+
+    @staticmethod
+    def _recall_at_thresholds(metrics: torch.Tensor, thresholds):            # evaluator.py:252-255; NaN / inf -> 0
+        return [(metrics <= threshold).float() for threshold in thresholds]
+
+    @staticmethod
+    def _combined_recall_at_specific_pairs(rot_errors, trans_errors, threshold_pairs):      # :257-280
+        return [((rot_errors <= r) & (trans_errors <= t)).float() for r, t in threshold_pairs]
+
+    def compute_metrics(self, data: dict, pointclouds_pred, rotations_pred=None, translations_pred=None) -> dict:
+        """-> {reference key: (B,) fp32 device tensor}.  ``data``: the reference's batch schema ("pointclouds", "pointclouds_gt",
+        "points_per_part", "anchor_parts", "scales", "rotations", "translations", "cu_seqlens_batch").  ``translations_pred`` is in
+        the scaled space, as there."""
+        pts, pts_gt = data["pointclouds"], data["pointclouds_gt"]
+        points_per_part, scales = data["points_per_part"], data["scales"]
+        cu = data["cu_seqlens_batch"]
+        _require_cuda(pointclouds_pred, "pointclouds_pred")
+        device = pointclouds_pred.device
+        scales = _f32c(scales.to(device))
+        object_cd = compute_cd(pts_gt, pointclouds_pred, cu)                                              # :49
+        object_cd_m = object_cd * scales
+        metrics = {"chamfer_l2 (m)": object_cd_m, "object_chamfer": object_cd}
+        have_poses = rotations_pred is not None and translations_pred is not None
+        if have_poses:
+            rot_errors, trans_errors = compute_transform_errors(pts, pts_gt, data["rotations"], data["translations"], rotations_pred,
+                                                                translations_pred, points_per_part, data["anchor_parts"], None, scales,
+                                                                cu)                                        # :60-62
+            # the direct errors of :65-67 enter no column of the reference's table (only its commented-out ECDF block read them);
+            # metrics.compute_transform_errors_direct is public on its own
+            combined = self._combined_recall_at_specific_pairs(rot_errors, trans_errors,
+                                                               [(10, 0.2), (15, 0.3), (1, 0.3), (2, 0.3), (5, 2.0), (10, 5.0)])
+            rigidity = compute_rigidity_rmse(pts, pointclouds_pred, rotations_pred, translations_pred, points_per_part, cu, scales)
+            metrics.update({
+                "average_rotation_error (deg)": rot_errors,
+                "average_translation_error (m)": trans_errors,
+                "recall_at_10deg_0.2m (nss)": combined[0],
+                "recall_at_15deg_0.3m (indoor_bufferx)": combined[1],
+                "recall_at_5deg_2m (outdoor_bufferx)": combined[4],
+                "recall_at_10deg_5m (map)": combined[5],
+                "recall_at_chamfer_0.2m": self._recall_at_thresholds(object_cd_m, [0.2])[0],
+                "rigidity_rmse (m)": rigidity,
+            })
+        if self.rmse_eval_on and points_per_part.shape[1] == 2:                                           # :125
+            if self.rmse_eval_on_transformed and not have_poses:
+                return metrics                                                                            # :127-128
+            if self.rmse_eval_on_transformed:
+                pm = compute_pair_metrics(data, pts, rotations_pred, translations_pred, self.PAIR_DISTANCE_THRESHOLD)
+            else:
+                pm = compute_pair_metrics(data, pointclouds_pred, None, None, self.PAIR_DISTANCE_THRESHOLD)
+            rmse, ratio, terr, _ = pm.t().contiguous().unbind(0)
+            metrics.update({
+                "correspondence_rmse (m)": rmse,
+                "correspondence_ratio": ratio,
+                "recall_at_rmse_0.2m": self._recall_at_thresholds(rmse, [0.2])[0],
+                "transform_error_rmse (m)": terr,
+                "recall_at_transform_error_rmse_0.2m": self._recall_at_thresholds(terr, [0.2])[0],
+            })
+        return metrics
+
+    _compute_metrics = compute_metrics          # the reference's name
+
+    def run(self, data: dict, pointclouds_pred, rotations_pred=None, translations_pred=None, save_results: bool = False,
+            generation_idx=0, trajectory=None, original_trajectory=None) -> dict:
+        """Reference signature (evaluator.py:827-837) -> the metrics table.  ``save_results=True`` is not supported: the PLY / JSON
+        writers are host I/O; write the transform files with ``save_transformation_files``."""
+        if save_results:
+            raise NotImplementedError("Evaluator.run(save_results=True): the PLY / JSON writers are not part of rap_amd; use "
+                                      "rap_amd.evaluator.save_transformation_files for the *_transform.txt files")
+        return self.compute_metrics(data, pointclouds_pred, rotations_pred, translations_pred)
