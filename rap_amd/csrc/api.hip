@@ -1,6 +1,6 @@
 // C ABI of librapflow (see include/rapflow.h): model packing, workspace carving and the launch
 // sequences of one velocity-network forward and of the whole Euler sampling loop.  Host code only;
-// every kernel lives in the sibling .hip files.
+// every kernel lives in the sibling .hip files, the kernel-level and metric / preprocessing entry points in api_ops.hip.
 #include "../../include/rapflow.h"
 #include "half.h"
 #include "kernels.h"
@@ -178,26 +178,37 @@ rap_tuning_t g_rap_fuse_qknorm = 1;            // tuning key 7: qk-norm fused in
 // residual GEMMs), 7 fused qk-norm, 9 GEGLU's Phi by the
 // 1.5e-7 erfc polynomial (1) or erff (0), 11 / 12 persistent 16-bit / fp32 GEMM, 15 the order of the attention work lists (identical results).  Keys 0-4 (kernel-variant A/B of the round-1/2 experiments) exist
 // only in a library built with -DRAP_ABLATION_BUILD; the shipped library refuses them.
-extern "C" int rap_set_tuning(int32_t key, int32_t value) {
+// One row per key: the values it accepts (n_values < 0: every value >= 0) and the switch it stores them in.
+struct TuningRow { int32_t key; rap_tuning_t* var; int n_values; int32_t values[7]; };
+static const TuningRow kTuning[] = {
 #ifdef RAP_ABLATION_BUILD
-  if (key == 0 && (value == 16 || value == 32 || value == 48)) { g_rap_gemm_variant = value; return RAP_OK; }
-  if (key == 2 && (value == 0 || value == 1 || value == 14)) { g_rap_gemm_h16_variant = value; return RAP_OK; }
-  if (key == 3 && (value == 0 || value == 5)) { g_rap_attn_h16_variant = value; return RAP_OK; }
-  if (key == 4 && value >= 0 && value <= 2) { g_rap_gemm_stagger = value; return RAP_OK; }
+  {0, &g_rap_gemm_variant, 3, {16, 32, 48}},
+  {2, &g_rap_gemm_h16_variant, 3, {0, 1, 14}},
+  {3, &g_rap_attn_h16_variant, 2, {0, 5}},
+  {4, &g_rap_gemm_stagger, 3, {0, 1, 2}},
 #endif
-  if (key == 5 && (value == 0 || value == 1)) { g_rap_attn_split = value; return RAP_OK; }
-  if (key == 6 && (value == 0 || value == 1)) { g_rap_gemm_splitk = value; return RAP_OK; }
-  if (key == 7 && (value == 0 || value == 1)) { g_rap_fuse_qknorm = value; return RAP_OK; }
-  if (key == 9 && (value == 0 || value == 1)) { g_rap_geglu_fast = value; return RAP_OK; }
-  if (key == 11 && (value == 0 || value == 1)) { g_rap_gemm_h16_persistent = value; return RAP_OK; }
-  if (key == 12 && (value == 0 || value == 1)) { g_rap_gemm_f32_persistent = value; return RAP_OK; }
-  if (key == 13 && (value == 0 || value == 1)) { g_rap_attn_h16_dma = value; return RAP_OK; }
-  if (key == 15 && (value == 0 || value == 1)) { g_rap_attn_lpt = value; return RAP_OK; }
-  if (key == 17 && value >= 0) { g_rap_x2_min_rows = value; return RAP_OK; }   // split precision from this many token rows per call (smaller calls: exact fp32)
-  if (key == 18 && value >= 0) { g_rap_ring_blocks = value; return RAP_OK; }      // four-stage ring of the 128 x 128 16-bit GEMM up to this many blocks per launch (0 = never)
-  if (key == 19 && (value == 0 || value == 1)) { g_rap_small_fused = value; return RAP_OK; }      // combine + LayerNorm fusion of few-token calls
-  if (key == 20 && (value == 0 || value == 1 || value == 2 || value == 64 || value == 128 || value == 66 || value == 130)) { g_rap_attn_h16_small = value; return RAP_OK; }   // 16-bit attention of few-token calls: 64 / 128-row work items + four-stage ring
-  if (key == 16 && (value == 2 || value == 4)) { g_rap_attn_x2_wpe = value; return RAP_OK; }   // split-precision attention: 1 / 2 blocks per CU
+  {5, &g_rap_attn_split, 2, {0, 1}},
+  {6, &g_rap_gemm_splitk, 2, {0, 1}},
+  {7, &g_rap_fuse_qknorm, 2, {0, 1}},
+  {9, &g_rap_geglu_fast, 2, {0, 1}},
+  {11, &g_rap_gemm_h16_persistent, 2, {0, 1}},
+  {12, &g_rap_gemm_f32_persistent, 2, {0, 1}},
+  {13, &g_rap_attn_h16_dma, 2, {0, 1}},
+  {15, &g_rap_attn_lpt, 2, {0, 1}},
+  {16, &g_rap_attn_x2_wpe, 2, {2, 4}},           // split-precision attention: 1 / 2 blocks per CU
+  {17, &g_rap_x2_min_rows, -1, {}},              // split precision from this many token rows per call (smaller calls: exact fp32)
+  {18, &g_rap_ring_blocks, -1, {}},              // four-stage ring of the 128 x 128 16-bit GEMM up to this many blocks per launch (0 = never)
+  {19, &g_rap_small_fused, 2, {0, 1}},           // combine + LayerNorm fusion of few-token calls
+  {20, &g_rap_attn_h16_small, 7, {0, 1, 2, 64, 128, 66, 130}},   // 16-bit attention of few-token calls: 64 / 128-row work items + four-stage ring
+};
+extern "C" int rap_set_tuning(int32_t key, int32_t value) {
+  for (const TuningRow& r : kTuning) {
+    if (r.key != key) continue;
+    bool ok = r.n_values < 0 && value >= 0;
+    for (int i = 0; i < r.n_values; ++i) ok = ok || r.values[i] == value;
+    if (ok) *r.var = value;
+    return ok ? RAP_OK : RAP_ERR_INVALID;
+  }
   return RAP_ERR_INVALID;
 }
 
@@ -504,8 +515,7 @@ struct Workspace {
 static Workspace carve_workspace(const rap_model* m, int64_t TP, int B, int nseg_part, int rows, char* basep, int force_dtype = -1) {
   Workspace w;
   const size_t d = m->d, L = m->L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = basep ? basep + off : nullptr; off += align_up(bytes, 256); return r; };
+  Carver c(basep);
   // Every token-row buffer is carved at TQ = align_up(TP, 256) rows (round 4): the layer kernels run over TQ rows, so the persistent
   // 256-row-tile GEMMs serve ANY token count (ragged batches are the reference's real regime, RAP_inference.yaml:30-36); rows
   // TP .. TQ-1 are finite filler nobody reads (rows are independent in every kernel but attention, whose work lists and key
@@ -514,51 +524,51 @@ static Workspace carve_workspace(const rap_model* m, int64_t TP, int B, int nseg
   w.rows = (int)T;
   const int dtype = w.dtype = force_dtype >= 0 ? force_dtype : eff_dtype(m, T);
   w.qk_norm = m->qk_norm;
-  w.base = (float*)take(T * d * 4);
+  w.base = (float*)c.take(T * d * 4);
   const bool x2 = dtype == RAP_DT_F32X2;    // split precision: fp32 residual stream, every 16-bit activation buffer holds heads AND tails
   const bool h16 = dtype != RAP_DT_F32 && !x2 && m->resid_dtype == RAP_DT_F16;
-  w.h = h16 ? nullptr : (float*)take(T * d * 4);
-  w.h16 = h16 ? (u16*)take(T * d * 2) : nullptr;
+  w.h = h16 ? nullptr : (float*)c.take(T * d * 4);
+  w.h16 = h16 ? (u16*)c.take(T * d * 2) : nullptr;
   w.xn = w.qkv = w.att = w.ffmid = nullptr;
   w.xnh = w.qkh = w.vth = w.atth = w.ffmidh = nullptr;
   w.splitk_h = nullptr;
   w.splitk_planes = 0;
   w.vt_nblk = 0;
   if (dtype == RAP_DT_F32) {
-    w.xn = (float*)take(T * d * 4);            // also head hidden 1 (TP,d)
-    w.qkv = (float*)take(T * 3 * d * 4);
-    w.att = (float*)take(T * d * 4);           // also head hidden 2 (TP,d/2)
-    w.ffmid = (float*)take(T * 4 * d * 4);     // also the static feature matrix (TP,Ks) during prepare (16 T d >= 4 T Ks bytes for d >= 256)
+    w.xn = (float*)c.take(T * d * 4);            // also head hidden 1 (TP,d)
+    w.qkv = (float*)c.take(T * 3 * d * 4);
+    w.att = (float*)c.take(T * d * 4);           // also head hidden 2 (TP,d/2)
+    w.ffmid = (float*)c.take(T * 4 * d * 4);     // also the static feature matrix (TP,Ks) during prepare (16 T d >= 4 T Ks bytes for d >= 256)
     w.hid1 = w.xn; w.hid2 = w.att; w.astatic = w.ffmid;
   } else {
     const size_t pl = x2 ? 2 : 1;              // planes per value
     w.vt_nblk = (int)(T / 64);                 // V^T image: whole 64-token blocks over the padded rows
-    w.xnh = (u16*)take(T * d * 2 * pl);
-    w.qkh = (u16*)take(T * 2 * d * 2 * pl);    // q,k [2][H][T][64]   (x2: [2][H][2 chunks][T][64 physical])
-    w.vth = (u16*)take((size_t)w.vt_nblk * 64 * d * 2 * pl);   // [H][vt_nblk][64][64]   (x2: [H][vt_nblk][2 chunks][64][64 physical])
-    w.atth = (u16*)take(T * d * 2 * pl);
+    w.xnh = (u16*)c.take(T * d * 2 * pl);
+    w.qkh = (u16*)c.take(T * 2 * d * 2 * pl);    // q,k [2][H][T][64]   (x2: [2][H][2 chunks][T][64 physical])
+    w.vth = (u16*)c.take((size_t)w.vt_nblk * 64 * d * 2 * pl);   // [H][vt_nblk][64][64]   (x2: [H][vt_nblk][2 chunks][64][64 physical])
+    w.atth = (u16*)c.take(T * d * 2 * pl);
     // >= 8*T*d bytes: also hosts the fp32 head hidden layers and the static feature matrix (T,Ks) fp32 = 4*T*Ks bytes, which is the
     // larger of the two at d = 256 with in_dim > 384 in the 16-bit modes (pl = 1)
     const size_t ffmid_bytes = T * 4 * d * 2 * pl, static_bytes = T * (size_t)m->Ks * 4;
-    w.ffmidh = (u16*)take(ffmid_bytes > static_bytes ? ffmid_bytes : static_bytes);
+    w.ffmidh = (u16*)c.take(ffmid_bytes > static_bytes ? ffmid_bytes : static_bytes);
     w.hid1 = (float*)w.ffmidh;                 // (T,d) fp32   = 4*T*d bytes
     w.hid2 = w.hid1 + T * d;                   // (T,d/2) fp32 = 2*T*d bytes
     w.astatic = (float*)w.ffmidh;
     // ff2: the one layer GEMM with K >= 1024.  Reserved by SHAPE alone (tuning key 6 only gates the launch), so that the size
     // rap_workspace_bytes reports cannot change between the query and the call
     const int splits = gemm_h16_splits_by_shape((int)T, (int)d, (int)((x2 ? 8 : 4) * d));   // (split precision: the physical K of ff2 is 8 d)
-    if (splits > 1) { w.splitk_h = (float*)take((size_t)splits * T * d * 4); w.splitk_planes = splits; }
+    if (splits > 1) { w.splitk_h = (float*)c.take((size_t)splits * T * d * 4); w.splitk_planes = splits; }
   }
-  w.ax = (float*)take(T * 64 * 4);
-  w.v = (float*)take(T * 3 * 4);
-  w.xt = (float*)take(T * 3 * 4);
-  w.mod = (float*)take((size_t)rows * 2 * L * 2 * d * 4);
-  w.ada_scratch = (float*)take((size_t)rows * (256 + 4 * L * d) * 4);
-  w.tgrid = (float*)take((size_t)rows * 4);
-  w.token_sample = (int32_t*)take(T * 4);
-  w.part_offsets = (int32_t*)take(((size_t)nseg_part + 1) * 4);
-  w.cu_batch_s = (int32_t*)take(((size_t)B + 1) * 4);
-  w.cu_part_s = (int32_t*)take(((size_t)nseg_part + 1) * 4);
+  w.ax = (float*)c.take(T * 64 * 4);
+  w.v = (float*)c.take(T * 3 * 4);
+  w.xt = (float*)c.take(T * 3 * 4);
+  w.mod = (float*)c.take((size_t)rows * 2 * L * 2 * d * 4);
+  w.ada_scratch = (float*)c.take((size_t)rows * (256 + 4 * L * d) * 4);
+  w.tgrid = (float*)c.take((size_t)rows * 4);
+  w.token_sample = (int32_t*)c.take(T * 4);
+  w.part_offsets = (int32_t*)c.take(((size_t)nseg_part + 1) * 4);
+  w.cu_batch_s = (int32_t*)c.take(((size_t)B + 1) * 4);
+  w.cu_part_s = (int32_t*)c.take(((size_t)nseg_part + 1) * 4);
   w.cu_part_live = w.part_offsets; w.nseg_part = nseg_part; w.nseg_batch = B;
   // query rows per attention work item: 256, or 64 / 128 for few-token calls of the 16-bit modes (attention_h16_block_queries)
   w.attn_bq = (dtype == RAP_DT_BF16 || dtype == RAP_DT_F16) ? attention_h16_block_queries(dtype, (long)T) : RAP_ATTN_BQ;
@@ -566,13 +576,13 @@ static Workspace carve_workspace(const rap_model* m, int64_t TP, int B, int nseg
   w.max_items_batch = (int)(TP / w.attn_bq) + B + 1;
   w.max_items_part = (int)(TP / w.attn_bq) + nseg_part + 1;
   // (reserved for the smallest work items whatever tuning key 20 says: the size rap_workspace_bytes reports does not depend on the key)
-  w.items_batch = (AttnWorkItem*)take(((size_t)(TP / 64) + B + 1) * sizeof(AttnWorkItem));
-  w.items_part = (AttnWorkItem*)take(((size_t)(TP / 64) + nseg_part + 1) * sizeof(AttnWorkItem));
-  w.attn_sort = (int32_t*)take(((size_t)(nseg_part > B ? nseg_part : B) + 1) * 4);   // scratch of the longest-first work-list order
-  w.proc_partials = (double*)take((size_t)nseg_part * RAP_PROC_CHUNKS * 16 * 8);
-  w.Rc = (float*)take((size_t)nseg_part * 9 * 4);
-  w.tc = (float*)take((size_t)nseg_part * 3 * 4);
-  w.total = off;
+  w.items_batch = (AttnWorkItem*)c.take(((size_t)(TP / 64) + B + 1) * sizeof(AttnWorkItem));
+  w.items_part = (AttnWorkItem*)c.take(((size_t)(TP / 64) + nseg_part + 1) * sizeof(AttnWorkItem));
+  w.attn_sort = (int32_t*)c.take(((size_t)(nseg_part > B ? nseg_part : B) + 1) * 4);   // scratch of the longest-first work-list order
+  w.proc_partials = (double*)c.take((size_t)nseg_part * RAP_PROC_CHUNKS * 16 * 8);
+  w.Rc = (float*)c.take((size_t)nseg_part * 9 * 4);
+  w.tc = (float*)c.take((size_t)nseg_part * 3 * 4);
+  w.total = c.total();
   return w;
 }
 
@@ -651,10 +661,157 @@ static int prepare_static(const rap_model* m, const Workspace& w, hipStream_t st
   return launch_gemm_f32(stream, EPI_BIAS_ANCHOR, g);
 }
 
+// ---- one transformer block in exact fp32 (layer i).  mod: see forward_step.
+static int block_f32(const rap_model* m, const Workspace& w, hipStream_t stream, int i, const float* mod, long mod_stride,
+                     const int32_t* token_row) {
+  const int d = m->d, H = m->H, TP = w.rows;
+  const LayerW& lw = m->layers[i];
+  int rc;
+  for (int a = 0; a < 2; ++a) {   // a = 0: per-part attention, a = 1: per-sample attention (layer.py:152-160)
+    const int j = 2 * i + a;
+    { ProfScope ps(stream, 3); rc = launch_layernorm_mod(stream, w.h, w.xn, TP, d, mod + (size_t)j * 2 * d, mod_stride, token_row); }
+    if (rc) return rc;
+    GemmParams g{};
+    g.A = w.xn; g.lda = d; g.W = lw.Wqkv[a]; g.ldw = d; g.C = w.qkv; g.M = TP; g.N = 3 * d; g.K = d; g.heads = H;
+    const bool fuse_qk = g_rap_fuse_qknorm != 0 && w.qk_norm;
+    if (fuse_qk) { g.gamma_q = lw.gq[a]; g.gamma_k = lw.gk[a]; }        // qk-norm in the QKV epilogue (tuning key 7)
+    { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_QKV_HEADMAJOR, g); }
+    if (rc) return rc;
+    if (!fuse_qk && w.qk_norm && (rc = launch_qknorm(stream, w.qkv, TP, H, lw.gq[a], lw.gk[a]))) return rc;
+    {
+      ProfScope ps(stream, a);
+      const float* bound = (w.qk_norm && m->bounded[j]) ? m->logit_bound + (size_t)j * H : nullptr;
+      // few-token calls: split the keys of every work item over up to 4 blocks; the partial O planes live in the (idle) FFN
+      // buffer (4 x TP x d floats), the partial row sums in the (idle) LN-output buffer
+      const int max_items = a == 0 ? w.max_items_part : w.max_items_batch;
+      const int splits = attention_f32_splits(max_items, H, bound != nullptr);
+      rc = launch_attention_f32(stream, w.qkv, w.att, TP, H, a == 0 ? w.items_part : w.items_batch, max_items, bound, w.ffmid, w.xn,
+                                splits, a == 0 ? w.cu_part_live : w.cu_batch_s, a == 0 ? w.nseg_part : w.nseg_batch);
+    }
+    if (rc) return rc;
+    GemmParams o{};
+    o.A = w.att; o.lda = d; o.W = lw.Wout[a]; o.ldw = d; o.C = w.h; o.ldc = d; o.M = TP; o.N = d; o.K = d;
+    o.bias = lw.bout[a]; o.resid = w.h; o.ldr = d;
+    o.splitk_ws = w.ffmid;     // idle between the FFNs (the split attention's partial planes are consumed by now): 4 partial (T,d) planes
+    { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_BIAS_RESID, o); }
+    if (rc) return rc;
+  }
+  { ProfScope ps(stream, 3); rc = launch_layernorm_affine(stream, w.h, w.xn, TP, d, lw.ffn_g, lw.ffn_b); }
+  if (rc) return rc;
+  GemmParams f1{};
+  f1.A = w.xn; f1.lda = d; f1.W = lw.Wff1p; f1.ldw = d; f1.C = w.ffmid; f1.ldc = 4 * d; f1.M = TP; f1.N = 8 * d; f1.K = d;
+  f1.bias = lw.bff1p;
+  { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_GEGLU, f1); }
+  if (rc) return rc;
+  GemmParams f2{};
+  f2.A = w.ffmid; f2.lda = 4 * d; f2.W = lw.Wff2; f2.ldw = 4 * d; f2.C = w.h; f2.ldc = d; f2.M = TP; f2.N = d; f2.K = 4 * d;
+  f2.bias = lw.bff2; f2.resid = w.h; f2.ldr = d;
+  f2.splitk_ws = w.qkv;      // idle during the FFN; qkv (3 T d) and att (T d) are adjacent: 4 partial (T,d) planes
+  { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_BIAS_RESID, f2); }
+  return rc;
+}
+
+// ---- one reduced-precision transformer block (layer i): 16-bit MFMA operands, fp32 accumulate, fp32 LN / softmax; ONE kernel sequence
+// for the three modes.  bf16 / fp16: one plane per value, residual stream in fp32 or fp16 (w.h16).  Split precision (RAP_DT_F32X2, round 5):
+// fp32-accurate products on the fp16 matrix pipe -- the same sequence on paired head / tail operands (pl = 2: physical K = 2 d resp. 8 d),
+// per-tensor power-of-two scales, fp32 residual stream, qk-norm always fused, online softmax (probabilities must fit fp16).
+// fused: few-token calls (see forward_step) -- every LayerNorm but the first of the forward is then part of the combine pass before it.
+static int block_h16(const rap_model* m, const Workspace& w, hipStream_t stream, int i, const float* mod, long mod_stride,
+                     const int32_t* token_row, int TP_valid, bool fused) {
+  const int d = m->d, H = m->H, TP = w.rows, dt = w.dtype;
+  const bool x2 = dt == RAP_DT_F32X2;
+  const int pl = x2 ? 2 : 1;                // planes per value
+  const LayerW& lw = m->layers[i];
+  // the 16-bit modes leave every s_* / g_* of LayerWH at 1.f, which are GemmParamsH's own defaults: the scales below are split precision's
+  const LayerWH& lh = m->half[dt].layers[i];
+  void* const hres = w.h16 ? (void*)w.h16 : (void*)w.h;      // the residual stream as the 16-bit LayerNorms and the residual GEMMs see it
+  const int hres_f16 = w.h16 ? 1 : 0;
+  const int epi_resid = w.h16 ? EPI_H_BIAS_RESID_H16 : EPI_H_BIAS_RESID_F32;
+  auto onto_resid = [&](GemmParamsH& g) { g.C = hres; g.ldc = d; g.ldr = d; if (w.h16) g.resid_h = w.h16; else g.resid = w.h; };
+  // (the count is fixed HERE: the GEMM and the pass that reads its planes cannot disagree)
+  auto defer_combine = [&](GemmParamsH& g) { const int sp = gemm_h16_splits(g.M, g.N, g.K); g.defer_combine = 1; g.force_splits = sp > 1 ? sp : 1; };
+  int rc = RAP_OK;
+  for (int a = 0; a < 2; ++a) {
+    const int j = 2 * i + a;
+    if (!fused || j == 0) { ProfScope ps(stream, 3); rc = launch_layernorm_mod_h16(stream, dt, hres, hres_f16, w.xnh, TP, d, mod + (size_t)j * 2 * d, mod_stride, token_row); }
+    if (rc) return rc;
+    GemmParamsH g{};
+    g.A = w.xnh; g.lda = pl * d; g.W = lh.Wqkv[a]; g.ldw = pl * d; g.C = w.qkh; g.M = TP; g.N = 3 * d; g.K = pl * d; g.heads = H;
+    g.vt = w.vth; g.vt_nblk = w.vt_nblk; g.acc_scale = lh.s_qkv[a]; g.out_scale = lh.g_v[a];
+    const bool bnd = !x2 && w.qk_norm && m->bounded[j] != 0;         // this launch's softmax kernel (per layer and branch)
+    const bool prescale = attention_h16_wants_prescaled_q(dt, bnd);
+    const float q_mul = prescale ? RAP_QMUL_PRESCALED : 8.0f;
+    // (few-token calls: the fused epilogue exists on 128 x 128 tiles too since round 6 -- launch_gemm_h16 picks the tile; until then
+    // such calls ran the projection and qk-norm as two kernels, r03 call 32)
+    if (x2 || (g_rap_fuse_qknorm && w.qk_norm)) {
+      // qk-norm in the QKV epilogue: one kernel, q / k normalised from the fp32 accumulators (no 16-bit round trip through HBM)
+      if (w.qk_norm) { g.gamma_q = lw.gq[a]; g.gamma_k = lw.gk[a]; }      // (split precision) null gains: the epilogue splits q / k as projected
+      g.q_mul = q_mul;
+      { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_QKV_NORM, g); }
+      if (rc) return rc;
+    } else {
+      { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_QKV, g); }
+      if (rc) return rc;
+      if (w.qk_norm && (rc = launch_qknorm_h16(stream, dt, w.qkh, TP, H, lw.gq[a], lw.gk[a], q_mul))) return rc;
+    }
+    {
+      ProfScope ps(stream, a);
+      const AttnWorkItem* items = a == 0 ? w.items_part : w.items_batch;
+      const int max_items = a == 0 ? w.max_items_part : w.max_items_batch;
+      if (x2) {
+        // few-token calls: the keys of every work item over 2 / 4 blocks; the partial O planes (4 x TQ x d floats) live in the idle FFN
+        // buffer (16 TQ d bytes in this mode), the partial (max, row sum) pairs in the idle LayerNorm-output buffer
+        rc = launch_attention_x2(stream, w.qkh, w.vth, w.vt_nblk, w.atth, TP, H, items, max_items, reinterpret_cast<float*>(w.ffmidh),
+                                 reinterpret_cast<float*>(w.xnh), attention_x2_splits(max_items, H), TP_valid,
+                                 a == 0 ? w.cu_part_live : w.cu_batch_s, a == 0 ? w.nseg_part : w.nseg_batch);
+      } else {
+        rc = launch_attention_h16(stream, dt, w.qkh, w.vth, w.vt_nblk, w.atth, TP, H, items, max_items,
+                                  bnd ? m->logit_bound + (size_t)j * H : nullptr, prescale ? 1 : 0, w.attn_bq, w.attn_kg);
+      }
+    }
+    if (rc) return rc;
+    GemmParamsH o{};
+    o.A = w.atth; o.lda = pl * d; o.W = lh.Wout[a]; o.ldw = pl * d; o.M = TP; o.N = d; o.K = pl * d;
+    o.bias = lw.bout[a]; o.acc_scale = lh.s_out[a] / lh.g_v[a];      // (the attention output carries V's activation scale)
+    onto_resid(o);
+    if (fused) { o.splitk_ws = w.splitk_h; defer_combine(o); }
+    { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, epi_resid, o); }
+    if (rc) return rc;
+    if (fused) {      // combine pass + the NEXT LayerNorm in one kernel: adaLN of the per-sample branch after a = 0, the FFN's affine LN after a = 1
+      ProfScope ps(stream, 3);
+      rc = launch_resid_combine_ln_h16(stream, dt, w.splitk_h, o.force_splits, o.bias, hres, hres_f16, w.xnh, TP, d,
+                                       a == 0 ? mod + (size_t)(j + 1) * 2 * d : nullptr, mod_stride, token_row, lw.ffn_g, lw.ffn_b);
+      if (rc) return rc;
+    }
+  }
+  if (!fused) { ProfScope ps(stream, 3); rc = launch_layernorm_affine_h16(stream, dt, hres, hres_f16, w.xnh, TP, d, lw.ffn_g, lw.ffn_b); }
+  if (rc) return rc;
+  GemmParamsH f1{};
+  f1.A = w.xnh; f1.lda = pl * d; f1.W = lh.Wff1p; f1.ldw = pl * d; f1.C = w.ffmidh; f1.ldc = pl * 4 * d; f1.M = TP; f1.N = 8 * d; f1.K = pl * d;
+  f1.bias = lw.bff1p; f1.acc_scale = lh.s_ff1; f1.out_scale = lh.g_ff1;
+  { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_GEGLU, f1); }
+  if (rc) return rc;
+  GemmParamsH f2{};
+  f2.A = w.ffmidh; f2.lda = pl * 4 * d; f2.W = lh.Wff2; f2.ldw = pl * 4 * d; f2.M = TP; f2.N = d; f2.K = pl * 4 * d;
+  f2.bias = lw.bff2; f2.acc_scale = lh.s_ff2 / lh.g_ff1;
+  onto_resid(f2);
+  f2.splitk_ws = w.splitk_h;               // few-token calls: K = 4d (physical 8d in split precision) split over 2 / 4 blocks per tile (null otherwise)
+  const bool f2_fused = fused && i + 1 < m->L;      // ... and its combine pass is the first LayerNorm of the next layer
+  if (f2_fused) defer_combine(f2);
+  { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, epi_resid, f2); }
+  if (rc) return rc;
+  if (f2_fused) {
+    ProfScope ps(stream, 3);
+    rc = launch_resid_combine_ln_h16(stream, dt, w.splitk_h, f2.force_splits, f2.bias, hres, hres_f16, w.xnh, TP, d,
+                                     mod + (size_t)(2 * i + 2) * 2 * d, mod_stride, token_row, nullptr, nullptr);
+  }
+  return rc;
+}
+
 // mod: (scale|shift) rows for this forward: row r at mod + r*mod_stride, LN j at + j*2d.
 static int forward_step(const rap_model* m, const Workspace& w, hipStream_t stream, const float* x_t, const float* mod,
                         long mod_stride, const int32_t* token_row, int TP_valid, float* v_out, float* feats_out) {
-  const int d = m->d, H = m->H;
+  const int d = m->d;
   int rc;
   // embed = PE63(x_t) Wx^T + base
   { ProfScope ps(stream, 4); rc = launch_posenc_x(stream, x_t, w.ax, TP_valid); }
@@ -671,197 +828,14 @@ static int forward_step(const rap_model* m, const Workspace& w, hipStream_t stre
     if ((rc = launch_gemm_f32(stream, EPI_BIAS_RESID, g))) return rc;
     if (w.h16 && (rc = launch_convert_f16_sat(stream, w.hid1, w.h16, (size_t)TP * d))) return rc;
   }
-  const int dt = w.dtype;
-  const void* hres = w.h16 ? (const void*)w.h16 : (const void*)w.h;      // the residual stream as the 16-bit LayerNorms read it
-  const int hres_f16 = w.h16 ? 1 : 0;
-  const int epi_resid = w.h16 ? EPI_H_BIAS_RESID_H16 : EPI_H_BIAS_RESID_F32;
   // Few-token calls of the 16-bit / split-precision blocks (round 6; the reference's everyday batch_size: 1, RAP_inference.yaml:30-36): every
   // residual GEMM leaves fp32 partial planes (split-K where gemm_h16_splits says so, one plane otherwise) and ONE kernel forms the new
   // residual-stream value and the LayerNorm that follows it (launch_resid_combine_ln_h16) -- 11 launches per layer instead of 14.  The planes
   // live in the split-K buffer, which exists exactly for the calls this is meant for (<= 128 tiles of 128 x 128 in the N = d GEMMs).
-  const bool fused = g_rap_small_fused && dt != RAP_DT_F32 && w.splitk_h != nullptr && g_rap_gemm_splitk;
-  auto fused_splits = [](const GemmParamsH& g) { const int sp = gemm_h16_splits(g.M, g.N, g.K); return sp > 1 ? sp : 1; };
-  bool xn_ready = false;                    // the LayerNorm output the next QKV projection reads is already in xnh
+  const bool fused = g_rap_small_fused && w.dtype != RAP_DT_F32 && w.splitk_h != nullptr && g_rap_gemm_splitk;
   for (int i = 0; i < m->L; ++i) {
-    const LayerW& lw = m->layers[i];
-    if (dt == RAP_DT_F32X2) {
-      // ---- split-precision block (round 5): fp32-accurate products on the fp16 matrix pipe.  Same kernel sequence as the 16-bit
-      // block below on paired head / tail operands (physical K = 2 d resp. 8 d), fp32 residual stream, qk-norm always fused,
-      // online softmax (probabilities must fit fp16).
-      const LayerWH& lh = m->half[dt].layers[i];
-      for (int a = 0; a < 2; ++a) {
-        const int j = 2 * i + a;
-        if (!xn_ready) { ProfScope ps(stream, 3); rc = launch_layernorm_mod_h16(stream, dt, w.h, 0, w.xnh, TP, d, mod + (size_t)j * 2 * d, mod_stride, token_row); }
-        if (rc) return rc;
-        GemmParamsH g{};
-        g.A = w.xnh; g.lda = 2 * d; g.W = lh.Wqkv[a]; g.ldw = 2 * d; g.C = w.qkh; g.M = TP; g.N = 3 * d; g.K = 2 * d; g.heads = H;
-        g.vt = w.vth; g.vt_nblk = w.vt_nblk; g.q_mul = 8.0f; g.acc_scale = lh.s_qkv[a]; g.out_scale = lh.g_v[a];
-        if (w.qk_norm) { g.gamma_q = lw.gq[a]; g.gamma_k = lw.gk[a]; }      // null gains: the epilogue splits q / k as projected
-        { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_QKV_NORM, g); }
-        if (rc) return rc;
-        {
-          ProfScope ps(stream, a);
-          // few-token calls: the keys of every work item over 2 / 4 blocks; the partial O planes (4 x TQ x d floats) live in the idle FFN
-          // buffer (16 TQ d bytes in this mode), the partial (max, row sum) pairs in the idle LayerNorm-output buffer
-          const int max_items = a == 0 ? w.max_items_part : w.max_items_batch;
-          const int splits = attention_x2_splits(max_items, H);
-          rc = launch_attention_x2(stream, w.qkh, w.vth, w.vt_nblk, w.atth, TP, H, a == 0 ? w.items_part : w.items_batch, max_items,
-                                   reinterpret_cast<float*>(w.ffmidh), reinterpret_cast<float*>(w.xnh), splits, TP_valid,
-                                   a == 0 ? w.cu_part_live : w.cu_batch_s, a == 0 ? w.nseg_part : w.nseg_batch);
-        }
-        if (rc) return rc;
-        GemmParamsH o{};
-        o.A = w.atth; o.lda = 2 * d; o.W = lh.Wout[a]; o.ldw = 2 * d; o.C = w.h; o.ldc = d; o.M = TP; o.N = d; o.K = 2 * d;
-        o.bias = lw.bout[a]; o.resid = w.h; o.ldr = d; o.acc_scale = lh.s_out[a] / lh.g_v[a];      // (the attention output carries V's activation scale)
-        if (fused) { o.splitk_ws = w.splitk_h; o.defer_combine = 1; o.force_splits = fused_splits(o); }      // (the count is fixed HERE: the GEMM and the pass that reads its planes cannot disagree)
-        { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_BIAS_RESID_F32, o); }
-        if (rc) return rc;
-        if (fused) {      // combine pass + the NEXT LayerNorm in one kernel: adaLN of the per-sample branch after a = 0, the FFN's affine LN after a = 1
-          ProfScope ps(stream, 3);
-          rc = launch_resid_combine_ln_h16(stream, dt, w.splitk_h, o.force_splits, o.bias, w.h, 0, w.xnh, TP, d,
-                                           a == 0 ? mod + (size_t)(j + 1) * 2 * d : nullptr, mod_stride, token_row, lw.ffn_g, lw.ffn_b);
-          if (rc) return rc;
-          xn_ready = true;
-        }
-      }
-      if (!fused) { ProfScope ps(stream, 3); rc = launch_layernorm_affine_h16(stream, dt, w.h, 0, w.xnh, TP, d, lw.ffn_g, lw.ffn_b); }
-      if (rc) return rc;
-      GemmParamsH f1{};
-      f1.A = w.xnh; f1.lda = 2 * d; f1.W = lh.Wff1p; f1.ldw = 2 * d; f1.C = w.ffmidh; f1.ldc = 8 * d; f1.M = TP; f1.N = 8 * d; f1.K = 2 * d;
-      f1.bias = lw.bff1p; f1.acc_scale = lh.s_ff1; f1.out_scale = lh.g_ff1;
-      { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_GEGLU, f1); }
-      if (rc) return rc;
-      GemmParamsH f2{};
-      f2.A = w.ffmidh; f2.lda = 8 * d; f2.W = lh.Wff2; f2.ldw = 8 * d; f2.C = w.h; f2.ldc = d; f2.M = TP; f2.N = d; f2.K = 8 * d;
-      f2.bias = lw.bff2; f2.resid = w.h; f2.ldr = d; f2.acc_scale = lh.s_ff2 / lh.g_ff1;
-      f2.splitk_ws = w.splitk_h;               // few-token calls: the physical K = 8d split over 2 / 4 blocks per tile (null otherwise)
-      const bool f2_fused = fused && i + 1 < m->L;      // ... and its combine pass is the first LayerNorm of the next layer
-      if (f2_fused) { f2.defer_combine = 1; f2.force_splits = fused_splits(f2); }
-      { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_BIAS_RESID_F32, f2); }
-      if (rc) return rc;
-      xn_ready = false;
-      if (f2_fused) {
-        ProfScope ps(stream, 3);
-        rc = launch_resid_combine_ln_h16(stream, dt, w.splitk_h, f2.force_splits, f2.bias, w.h, 0, w.xnh, TP, d,
-                                         mod + (size_t)(2 * i + 2) * 2 * d, mod_stride, token_row, nullptr, nullptr);
-        if (rc) return rc;
-        xn_ready = true;
-      }
-      continue;
-    }
-    if (dt != RAP_DT_F32) {
-      // ---- reduced-precision block: 16-bit MFMA operands, fp32 accumulate, fp32 residual stream / LN / softmax
-      const LayerWH& lh = m->half[dt].layers[i];
-      for (int a = 0; a < 2; ++a) {
-        const int j = 2 * i + a;
-        if (!xn_ready) { ProfScope ps(stream, 3); rc = launch_layernorm_mod_h16(stream, dt, hres, hres_f16, w.xnh, TP, d, mod + (size_t)j * 2 * d, mod_stride, token_row); }
-        if (rc) return rc;
-        GemmParamsH g{};
-        g.A = w.xnh; g.lda = d; g.W = lh.Wqkv[a]; g.ldw = d; g.C = w.qkh; g.M = TP; g.N = 3 * d; g.K = d; g.heads = H;
-        g.vt = w.vth; g.vt_nblk = w.vt_nblk;
-        const bool bnd = w.qk_norm && m->bounded[j] != 0;                // this launch's softmax kernel (per layer and branch)
-        const bool prescale = attention_h16_wants_prescaled_q(dt, bnd);
-        // (few-token calls: the fused epilogue exists on 128 x 128 tiles too since round 6 -- launch_gemm_h16 picks the tile; until then
-        // such calls ran the projection and qk-norm as two kernels, r03 call 32)
-        if (g_rap_fuse_qknorm && w.qk_norm) {
-          // qk-norm in the QKV epilogue: one kernel, q / k normalised from the fp32 accumulators (no 16-bit round trip through HBM)
-          g.gamma_q = lw.gq[a]; g.gamma_k = lw.gk[a]; g.q_mul = prescale ? RAP_QMUL_PRESCALED : 8.0f;
-          { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_QKV_NORM, g); }
-          if (rc) return rc;
-        } else {
-          { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_QKV, g); }
-          if (rc) return rc;
-          if (w.qk_norm && (rc = launch_qknorm_h16(stream, dt, w.qkh, TP, H, lw.gq[a], lw.gk[a], prescale ? RAP_QMUL_PRESCALED : 8.0f))) return rc;
-        }
-        {
-          ProfScope ps(stream, a);
-          const float* bound = bnd ? m->logit_bound + (size_t)j * H : nullptr;
-          rc = launch_attention_h16(stream, dt, w.qkh, w.vth, w.vt_nblk, w.atth, TP, H, a == 0 ? w.items_part : w.items_batch,
-                                    a == 0 ? w.max_items_part : w.max_items_batch, bound, prescale ? 1 : 0, w.attn_bq, w.attn_kg);
-        }
-        if (rc) return rc;
-        GemmParamsH o{};
-        o.A = w.atth; o.lda = d; o.W = lh.Wout[a]; o.ldw = d; o.ldc = d; o.M = TP; o.N = d; o.K = d;
-        o.bias = lw.bout[a]; o.ldr = d;
-        if (w.h16) { o.C = w.h16; o.resid_h = w.h16; } else { o.C = w.h; o.resid = w.h; }
-        if (fused) { o.splitk_ws = w.splitk_h; o.defer_combine = 1; o.force_splits = fused_splits(o); }
-        { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, epi_resid, o); }
-        if (rc) return rc;
-        if (fused) {      // combine pass + the NEXT LayerNorm in one kernel (see the split-precision block)
-          ProfScope ps(stream, 3);
-          rc = launch_resid_combine_ln_h16(stream, dt, w.splitk_h, o.force_splits, o.bias, w.h16 ? (void*)w.h16 : (void*)w.h, hres_f16, w.xnh, TP, d,
-                                           a == 0 ? mod + (size_t)(j + 1) * 2 * d : nullptr, mod_stride, token_row, lw.ffn_g, lw.ffn_b);
-          if (rc) return rc;
-          xn_ready = true;
-        }
-      }
-      if (!fused) { ProfScope ps(stream, 3); rc = launch_layernorm_affine_h16(stream, dt, hres, hres_f16, w.xnh, TP, d, lw.ffn_g, lw.ffn_b); }
-      if (rc) return rc;
-      GemmParamsH f1{};
-      f1.A = w.xnh; f1.lda = d; f1.W = lh.Wff1p; f1.ldw = d; f1.C = w.ffmidh; f1.ldc = 4 * d; f1.M = TP; f1.N = 8 * d; f1.K = d;
-      f1.bias = lw.bff1p;
-      { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_GEGLU, f1); }
-      if (rc) return rc;
-      GemmParamsH f2{};
-      f2.A = w.ffmidh; f2.lda = 4 * d; f2.W = lh.Wff2; f2.ldw = 4 * d; f2.ldc = d; f2.M = TP; f2.N = d; f2.K = 4 * d;
-      f2.bias = lw.bff2; f2.ldr = d;
-      f2.splitk_ws = w.splitk_h;               // few-token calls: K = 4d split over 2 / 4 blocks per tile (null otherwise)
-      if (w.h16) { f2.C = w.h16; f2.resid_h = w.h16; } else { f2.C = w.h; f2.resid = w.h; }
-      const bool f2_fused = fused && i + 1 < m->L;
-      if (f2_fused) { f2.defer_combine = 1; f2.force_splits = fused_splits(f2); }
-      { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, epi_resid, f2); }
-      if (rc) return rc;
-      xn_ready = false;
-      if (f2_fused) {
-        ProfScope ps(stream, 3);
-        rc = launch_resid_combine_ln_h16(stream, dt, w.splitk_h, f2.force_splits, f2.bias, w.h16 ? (void*)w.h16 : (void*)w.h, hres_f16, w.xnh, TP, d,
-                                         mod + (size_t)(2 * i + 2) * 2 * d, mod_stride, token_row, nullptr, nullptr);
-        if (rc) return rc;
-        xn_ready = true;
-      }
-      continue;
-    }
-    for (int a = 0; a < 2; ++a) {   // a = 0: per-part attention, a = 1: per-sample attention (layer.py:152-160)
-      const int j = 2 * i + a;
-      { ProfScope ps(stream, 3); rc = launch_layernorm_mod(stream, w.h, w.xn, TP, d, mod + (size_t)j * 2 * d, mod_stride, token_row); }
-      if (rc) return rc;
-      GemmParams g{};
-      g.A = w.xn; g.lda = d; g.W = lw.Wqkv[a]; g.ldw = d; g.C = w.qkv; g.M = TP; g.N = 3 * d; g.K = d; g.heads = H;
-      const bool fuse_qk = g_rap_fuse_qknorm != 0 && w.qk_norm;
-      if (fuse_qk) { g.gamma_q = lw.gq[a]; g.gamma_k = lw.gk[a]; }        // qk-norm in the QKV epilogue (tuning key 7)
-      { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_QKV_HEADMAJOR, g); }
-      if (rc) return rc;
-      if (!fuse_qk && w.qk_norm && (rc = launch_qknorm(stream, w.qkv, TP, H, lw.gq[a], lw.gk[a]))) return rc;
-      {
-        ProfScope ps(stream, a);
-        const float* bound = (w.qk_norm && m->bounded[j]) ? m->logit_bound + (size_t)j * H : nullptr;
-        // few-token calls: split the keys of every work item over up to 4 blocks; the partial O planes live in the (idle) FFN
-        // buffer (4 x TP x d floats), the partial row sums in the (idle) LN-output buffer
-        const int max_items = a == 0 ? w.max_items_part : w.max_items_batch;
-        const int splits = attention_f32_splits(max_items, H, bound != nullptr);
-        rc = launch_attention_f32(stream, w.qkv, w.att, TP, H, a == 0 ? w.items_part : w.items_batch, max_items, bound, w.ffmid, w.xn,
-                                  splits, a == 0 ? w.cu_part_live : w.cu_batch_s, a == 0 ? w.nseg_part : w.nseg_batch);
-      }
-      if (rc) return rc;
-      GemmParams o{};
-      o.A = w.att; o.lda = d; o.W = lw.Wout[a]; o.ldw = d; o.C = w.h; o.ldc = d; o.M = TP; o.N = d; o.K = d;
-      o.bias = lw.bout[a]; o.resid = w.h; o.ldr = d;
-      o.splitk_ws = w.ffmid;     // idle between the FFNs (the split attention's partial planes are consumed by now): 4 partial (T,d) planes
-      { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_BIAS_RESID, o); }
-      if (rc) return rc;
-    }
-    { ProfScope ps(stream, 3); rc = launch_layernorm_affine(stream, w.h, w.xn, TP, d, lw.ffn_g, lw.ffn_b); }
-    if (rc) return rc;
-    GemmParams f1{};
-    f1.A = w.xn; f1.lda = d; f1.W = lw.Wff1p; f1.ldw = d; f1.C = w.ffmid; f1.ldc = 4 * d; f1.M = TP; f1.N = 8 * d; f1.K = d;
-    f1.bias = lw.bff1p;
-    { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_GEGLU, f1); }
-    if (rc) return rc;
-    GemmParams f2{};
-    f2.A = w.ffmid; f2.lda = 4 * d; f2.W = lw.Wff2; f2.ldw = 4 * d; f2.C = w.h; f2.ldc = d; f2.M = TP; f2.N = d; f2.K = 4 * d;
-    f2.bias = lw.bff2; f2.resid = w.h; f2.ldr = d;
-    f2.splitk_ws = w.qkv;      // idle during the FFN; qkv (3 T d) and att (T d) are adjacent: 4 partial (T,d) planes
-    { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_BIAS_RESID, f2); }
+    rc = w.dtype == RAP_DT_F32 ? block_f32(m, w, stream, i, mod, mod_stride, token_row)
+                               : block_h16(m, w, stream, i, mod, mod_stride, token_row, TP_valid, fused);
     if (rc) return rc;
   }
   // 16-bit residual stream: the fp32 head (and the caller's transformer_features) read an fp32 image of it -- written into the
@@ -926,6 +900,13 @@ extern "C" int rap_dit_forward_latent(const rap_model* m, const float* x_t, cons
   return forward_step(m, w, stream, x_t, w.mod, (long)2 * m->L * 2 * m->d, w.token_sample, (int)TP, v_out, feats_out);
 }
 
+// kernel-level: the adaLN modulation table of this model for `rows` timesteps
+extern "C" int rap_adaln_table(const rap_model* m, const float* t, int32_t rows, float* scratch, float* out, void* stream) {
+  if (!m || !t || !scratch || !out) return RAP_ERR_INVALID;
+  return launch_adaln_table((hipStream_t)stream, t, rows, 2 * m->L, m->d, m->adaW1, m->adab1, m->adaW2, m->adab2, m->adaW3,
+                            m->adab3, scratch, out);
+}
+
 extern "C" int rap_euler_step(const float* x_t, const float* v, float t, float dt, float* x0_hat, float* x_next,
                               float* traj_xt_slot, int64_t n, void* stream) {
   if (!x_t || !v || !x0_hat || !x_next || n < 0) return RAP_ERR_INVALID;
@@ -937,60 +918,56 @@ extern "C" int rap_euler_step(const float* x_t, const float* v, float t, float d
 // ---------------------------------------------------------------------------------------------
 struct ProcWs { int32_t* off; double* partials; float* Rc; float* tc; size_t total; };
 static ProcWs carve_proc(int nparts, char* basep) {
-  ProcWs p; size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = basep ? basep + off : nullptr; off += align_up(bytes, 256); return r; };
-  p.off = (int32_t*)take(((size_t)nparts + 1) * 4);
-  p.partials = (double*)take((size_t)nparts * RAP_PROC_CHUNKS * 16 * 8);
-  p.Rc = (float*)take((size_t)nparts * 9 * 4);
-  p.tc = (float*)take((size_t)nparts * 3 * 4);
-  p.total = off;
+  ProcWs p; Carver c(basep);
+  p.off = (int32_t*)c.take(((size_t)nparts + 1) * 4);
+  p.partials = (double*)c.take((size_t)nparts * RAP_PROC_CHUNKS * 16 * 8);
+  p.Rc = (float*)c.take((size_t)nparts * 9 * 4);
+  p.tc = (float*)c.take((size_t)nparts * 3 * 4);
+  p.total = c.total();
   return p;
 }
 extern "C" size_t rap_procrustes_workspace_bytes(int32_t nparts) { return nparts < 0 ? 0 : carve_proc(nparts, nullptr).total; }
 
+// what the three entry points below start with: shape checks, the carved workspace, the parts' point offsets
+static int proc_begin(hipStream_t stream, const int64_t* points_per_part, int32_t B, int32_t P, void* ws, size_t ws_bytes, ProcWs* p) {
+  if (B <= 0 || P <= 0 || (int64_t)B * P > 65535) return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  *p = carve_proc(B * P, (char*)ws);
+  if (p->total > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_part_offsets(stream, points_per_part, B * P, p->off);
+}
+
 extern "C" int rap_fit_transformations(const float* src, const float* tgt, const int64_t* points_per_part, int32_t B,
                                        int32_t P, float* R_out, float* t_out, void* ws, size_t ws_bytes, void* stream_) {
-  if (!src || !tgt || !points_per_part || !R_out || !t_out || B <= 0 || P <= 0) return RAP_ERR_INVALID;
-  if ((int64_t)B * P > 65535) return RAP_ERR_INVALID;
-  const int np = B * P;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  ProcWs p = carve_proc(np, (char*)ws);
-  if (p.total > ws_bytes) return RAP_ERR_WORKSPACE;
+  if (!src || !tgt || !points_per_part || !R_out || !t_out) return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
+  ProcWs p;
   int rc;
-  if ((rc = launch_part_offsets(stream, points_per_part, np, p.off))) return rc;
-  return launch_procrustes_fit(stream, src, tgt, p.off, np, R_out, t_out, p.partials);
+  if ((rc = proc_begin(stream, points_per_part, B, P, ws, ws_bytes, &p))) return rc;
+  return launch_procrustes_fit(stream, src, tgt, p.off, B * P, R_out, t_out, p.partials);
 }
 
 extern "C" int rap_rigidify(const float* prediction, const float* condition, const int64_t* points_per_part, int32_t B,
                             int32_t P, float* out, void* ws, size_t ws_bytes, void* stream_) {
-  if (!prediction || !condition || !points_per_part || !out || B <= 0 || P <= 0) return RAP_ERR_INVALID;
-  if ((int64_t)B * P > 65535) return RAP_ERR_INVALID;
-  const int np = B * P;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  ProcWs p = carve_proc(np, (char*)ws);
-  if (p.total > ws_bytes) return RAP_ERR_WORKSPACE;
+  if (!prediction || !condition || !points_per_part || !out) return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
+  ProcWs p;
   int rc;
-  if ((rc = launch_part_offsets(stream, points_per_part, np, p.off))) return rc;
-  if ((rc = launch_procrustes_fit(stream, condition, prediction, p.off, np, p.Rc, p.tc, p.partials))) return rc;
-  return launch_rigid_apply(stream, condition, p.Rc, p.tc, p.off, np, out, nullptr, 0.f, 0.f, nullptr, 0);
+  if ((rc = proc_begin(stream, points_per_part, B, P, ws, ws_bytes, &p))) return rc;
+  if ((rc = launch_procrustes_fit(stream, condition, prediction, p.off, B * P, p.Rc, p.tc, p.partials))) return rc;
+  return launch_rigid_apply(stream, condition, p.Rc, p.tc, p.off, B * P, out, nullptr, 0.f, 0.f, nullptr, 0);
 }
 
 extern "C" int rap_rigidify_blend(const float* x0_hat, const float* condition, const int64_t* points_per_part, int32_t B,
                                   int32_t P, const float* x_1, float w0, float w1, float* x_t_out, void* ws, size_t ws_bytes,
                                   void* stream_) {
-  if (!x0_hat || !condition || !points_per_part || !x_1 || !x_t_out || B <= 0 || P <= 0) return RAP_ERR_INVALID;
-  if ((int64_t)B * P > 65535) return RAP_ERR_INVALID;
-  const int np = B * P;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  ProcWs p = carve_proc(np, (char*)ws);
-  if (p.total > ws_bytes) return RAP_ERR_WORKSPACE;
+  if (!x0_hat || !condition || !points_per_part || !x_1 || !x_t_out) return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
+  ProcWs p;
   int rc;
-  if ((rc = launch_part_offsets(stream, points_per_part, np, p.off))) return rc;
-  if ((rc = launch_procrustes_fit(stream, condition, x0_hat, p.off, np, p.Rc, p.tc, p.partials))) return rc;
-  return launch_rigid_apply(stream, condition, p.Rc, p.tc, p.off, np, x_t_out, x_1, w0, w1, nullptr, 1);
+  if ((rc = proc_begin(stream, points_per_part, B, P, ws, ws_bytes, &p))) return rc;
+  if ((rc = launch_procrustes_fit(stream, condition, x0_hat, p.off, B * P, p.Rc, p.tc, p.partials))) return rc;
+  return launch_rigid_apply(stream, condition, p.Rc, p.tc, p.off, B * P, x_t_out, x_1, w0, w1, nullptr, 1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1061,699 +1038,3 @@ extern "C" int rap_sample_latent(const rap_model* m, const float* cond, const fl
                                w.proc_partials);
 }
 
-// ---------------------------------------------------------------------------------------------
-// kernel-level entry points
-// ---------------------------------------------------------------------------------------------
-extern "C" int rap_gemm_f32(int32_t epilogue, const float* A, int32_t lda, const float* W, int32_t ldw, float* C, int32_t ldc,
-                            int32_t M, int32_t N, int32_t K, const float* bias, const float* resid, int32_t ldr,
-                            const uint8_t* anchor, const float* anchor_emb, int32_t heads, void* stream) {
-  if (!A || !W || !C) return RAP_ERR_INVALID;
-  if (epilogue == EPI_BIAS_RESID && !resid) return RAP_ERR_INVALID;
-  if (epilogue == EPI_BIAS_ANCHOR && (!anchor || !anchor_emb)) return RAP_ERR_INVALID;
-  GemmParams g{};
-  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias;
-  g.resid = resid; g.ldr = ldr; g.anchor = anchor; g.anchor_emb = anchor_emb; g.heads = heads;
-  return launch_gemm_f32((hipStream_t)stream, epilogue, g);
-}
-
-extern "C" int rap_geglu_interleave(const float* W, const float* b, float* Wp, float* bp, int32_t inner, int32_t K,
-                                    void* stream) {
-  if (!W || !b || !Wp || !bp) return RAP_ERR_INVALID;
-  return launch_geglu_interleave((hipStream_t)stream, W, b, Wp, bp, inner, K);
-}
-
-// [work items | sanitised copy of the caller's cu_seqlens]: the kernel-level attention entry points index with the copy only (ADVICE r05:
-// an entry above TP in the caller's table made seg_start + q run past the planes; the model path has sanitised its tables since round 5)
-// (work items reserved at the smallest granularity, 64 rows: tuning key 20's forced item sizes reach rap_attention_h16 too)
-static size_t attn_items_bytes(int64_t TP, int32_t nseg) { return align_up(((size_t)(TP / 64) + (size_t)nseg + 1) * sizeof(AttnWorkItem), 256); }
-extern "C" size_t rap_attention_workspace_bytes(int64_t TP, int32_t nseg) {
-  return attn_items_bytes(TP, nseg) + align_up(((size_t)nseg + 1) * sizeof(int32_t), 256);
-}
-// -> device pointer to the clamped, non-decreasing copy of cu_seqlens inside ws
-static int attn_ws_sanitize(hipStream_t stream, const int32_t* cu_seqlens, int32_t nseg, int64_t TP, void* ws, const int32_t** cu_out) {
-  int32_t* cu_s = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + attn_items_bytes(TP, nseg));
-  *cu_out = cu_s;
-  return launch_sanitize_cu(stream, cu_seqlens, nseg + 1, (long)TP, cu_s);
-}
-
-// the work list of one attention launch as rap_sample / rap_dit_forward build it: one {seg_start, seg_len, q0, 0} item per
-// `block_queries` query rows of every segment, longest segment first when sort_ws (nseg ints) is given, zero items after the last
-extern "C" int rap_build_attention_worklist(const int32_t* cu_seqlens, int32_t nseg, int32_t block_queries, int32_t* items_out,
-                                            int32_t max_items, int32_t* sort_ws, void* stream) {
-  if (!cu_seqlens || !items_out || nseg < 0 || max_items < 0 || block_queries <= 0) return RAP_ERR_INVALID;
-  return launch_build_attn_worklist((hipStream_t)stream, cu_seqlens, nseg, reinterpret_cast<AttnWorkItem*>(items_out), max_items,
-                                    block_queries, sort_ws);
-}
-
-extern "C" int rap_attention_f32(const float* qkv_headmajor, const int32_t* cu_seqlens, int32_t nseg, float* out,
-                                 int64_t TP, int32_t heads, const float* logit_bound, void* ws, size_t ws_bytes,
-                                 void* stream_) {
-  if (!qkv_headmajor || !cu_seqlens || !out || nseg < 0 || TP < 0 || TP > 0x7fffffffLL / 8) return RAP_ERR_INVALID;
-  if (!ws || ws_bytes < rap_attention_workspace_bytes(TP, nseg)) return RAP_ERR_WORKSPACE;
-  const int max_items = (int)(TP / RAP_ATTN_BQ) + nseg + 1;
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc;
-  if ((rc = attn_ws_sanitize(stream, cu_seqlens, nseg, TP, ws, &cu_seqlens))) return rc;
-  if ((rc = launch_build_attn_worklist(stream, cu_seqlens, nseg, (AttnWorkItem*)ws, max_items, 0))) return rc;
-  return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, nullptr, nullptr, 1);
-}
-
-extern "C" int rap_layernorm_mod(const float* x, float* out, int64_t TP, int32_t d, const float* mod, int64_t mod_stride,
-                                 const int32_t* token_row, void* stream) {
-  if (!x || !out || !mod) return RAP_ERR_INVALID;
-  return launch_layernorm_mod((hipStream_t)stream, x, out, (int)TP, d, mod, (long)mod_stride, token_row);
-}
-extern "C" int rap_layernorm_affine(const float* x, float* out, int64_t TP, int32_t d, const float* gain, const float* shift,
-                                    void* stream) {
-  if (!x || !out || !gain || !shift) return RAP_ERR_INVALID;
-  return launch_layernorm_affine((hipStream_t)stream, x, out, (int)TP, d, gain, shift);
-}
-extern "C" int rap_qknorm(float* qkv_headmajor, int64_t TP, int32_t heads, const float* gamma_q, const float* gamma_k,
-                          void* stream) {
-  if (!qkv_headmajor || !gamma_q || !gamma_k) return RAP_ERR_INVALID;
-  return launch_qknorm((hipStream_t)stream, qkv_headmajor, (int)TP, heads, gamma_q, gamma_k);
-}
-extern "C" int rap_posenc_x(const float* x, float* ax, int64_t TP, void* stream) {
-  if (!x || !ax) return RAP_ERR_INVALID;
-  return launch_posenc_x((hipStream_t)stream, x, ax, (int)TP);
-}
-extern "C" int rap_posenc_static(const float* cond, const float* scales, const int32_t* token_sample, const float* feat,
-                                 int32_t feat_dim, float* astatic, int64_t TP, void* stream) {
-  if (!cond || !scales || !token_sample || !astatic) return RAP_ERR_INVALID;
-  return launch_posenc_static((hipStream_t)stream, cond, scales, token_sample, feat, feat_dim, astatic, (int)TP);
-}
-extern "C" int rap_token_sample(const int32_t* cu_batch, int32_t B, int32_t* token_sample, void* stream) {
-  if (!cu_batch || !token_sample) return RAP_ERR_INVALID;
-  return launch_token_sample((hipStream_t)stream, cu_batch, B, token_sample);
-}
-extern "C" int rap_adaln_table(const rap_model* m, const float* t, int32_t rows, float* scratch, float* out, void* stream) {
-  if (!m || !t || !scratch || !out) return RAP_ERR_INVALID;
-  return launch_adaln_table((hipStream_t)stream, t, rows, 2 * m->L, m->d, m->adaW1, m->adab1, m->adaW2, m->adab2, m->adaW3,
-                            m->adab3, scratch, out);
-}
-
-// ---- reduced-precision kernel-level entry points (dtype: 1 = bf16, 2 = fp16; 16-bit tensors as uint16_t*) ----
-extern "C" int rap_convert_h16(int32_t dtype, const float* src, uint16_t* dst, int64_t n, void* stream) {
-  if (!src || !dst || n < 0) return RAP_ERR_INVALID;
-  return launch_convert_h16((hipStream_t)stream, dtype, src, dst, (size_t)n);
-}
-extern "C" int rap_gemm_h16(int32_t dtype, int32_t epilogue, const uint16_t* A, int32_t lda, const uint16_t* W, int32_t ldw,
-                            void* C, int32_t ldc, int32_t M, int32_t N, int32_t K, const float* bias, const float* resid,
-                            int32_t ldr, int32_t heads, uint16_t* vt, int32_t vt_nblk, void* stream) {
-  if (!A || !W || !C) return RAP_ERR_INVALID;
-  GemmParamsH g{};
-  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias;
-  g.resid = resid; g.ldr = ldr; g.heads = heads; g.vt = vt; g.vt_nblk = vt_nblk;
-  if (epilogue == EPI_H_BIAS_RESID_H16) { g.resid_h = reinterpret_cast<const uint16_t*>(resid); g.resid = nullptr; }   // fp16 residual
-  return launch_gemm_h16((hipStream_t)stream, dtype, epilogue, g);
-}
-// the residual epilogues (1, 6) with an optional split-K workspace (what rap_sample hands ff2 on few-token calls)
-extern "C" size_t rap_gemm_h16_splitk_workspace_bytes(int32_t M, int32_t N, int32_t K) {
-  const int s = gemm_h16_splits_by_shape(M, N, K);
-  return s > 1 ? (size_t)s * (size_t)M * (size_t)N * sizeof(float) : 0;
-}
-extern "C" int rap_gemm_h16_splitk(int32_t dtype, int32_t epilogue, const uint16_t* A, int32_t lda, const uint16_t* W, int32_t ldw, void* C,
-                                   int32_t ldc, int32_t M, int32_t N, int32_t K, const float* bias, const void* resid, int32_t ldr,
-                                   void* ws, size_t ws_bytes, void* stream) {
-  if (!A || !W || !C || (epilogue != EPI_H_BIAS_RESID_F32 && epilogue != EPI_H_BIAS_RESID_H16)) return RAP_ERR_INVALID;
-  const size_t need = rap_gemm_h16_splitk_workspace_bytes(M, N, K);
-  if (need && (!ws || ws_bytes < need)) return RAP_ERR_WORKSPACE;
-  GemmParamsH g{};
-  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias; g.ldr = ldr;
-  if (epilogue == EPI_H_BIAS_RESID_H16) g.resid_h = reinterpret_cast<const uint16_t*>(resid); else g.resid = reinterpret_cast<const float*>(resid);
-  g.splitk_ws = need ? reinterpret_cast<float*>(ws) : nullptr;
-  return launch_gemm_h16((hipStream_t)stream, dtype, epilogue, g);
-}
-extern "C" int rap_attention_h16(int32_t dtype, const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk,
-                                 const int32_t* cu_seqlens, int32_t nseg, uint16_t* out, int64_t TP, int32_t heads,
-                                 const float* logit_bound, void* ws, size_t ws_bytes, void* stream_) {
-  if (!qk || !vt || !cu_seqlens || !out || nseg < 0 || TP < 0 || TP > 0x7fffffffLL / 8) return RAP_ERR_INVALID;
-  if (!ws || ws_bytes < rap_attention_workspace_bytes(TP, nseg)) return RAP_ERR_WORKSPACE;
-  // 256-row work items, two stages -- unless tuning key 20 FORCES an item size / key groups (64, 128, 66, 130: the A/B values), which
-  // then applies here as it does to a model call of the same row count (so the few-token kernels have kernel-level tests)
-  const long rows = attention_h16_forced() ? (long)align_up((size_t)TP, 256) : 0;
-  const int bq = attention_h16_block_queries(dtype, rows), kg = attention_h16_key_groups(dtype, rows);
-  const int max_items = (int)(TP / bq) + nseg + 1;
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc;
-  if ((rc = attn_ws_sanitize(stream, cu_seqlens, nseg, TP, ws, &cu_seqlens))) return rc;
-  if ((rc = launch_build_attn_worklist(stream, cu_seqlens, nseg, (AttnWorkItem*)ws, max_items, bq))) return rc;
-  return launch_attention_h16(stream, dtype, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, 0, bq, kg);
-}
-extern "C" int rap_layernorm_mod_h16(int32_t dtype, const float* x, uint16_t* out, int64_t TP, int32_t d, const float* mod,
-                                     int64_t mod_stride, const int32_t* token_row, void* stream) {
-  if (!x || !out || !mod) return RAP_ERR_INVALID;
-  return launch_layernorm_mod_h16((hipStream_t)stream, dtype, x, 0, out, (int)TP, d, mod, (long)mod_stride, token_row);
-}
-extern "C" int rap_layernorm_affine_h16(int32_t dtype, const float* x, uint16_t* out, int64_t TP, int32_t d, const float* gain,
-                                        const float* shift, void* stream) {
-  if (!x || !out || !gain || !shift) return RAP_ERR_INVALID;
-  return launch_layernorm_affine_h16((hipStream_t)stream, dtype, x, 0, out, (int)TP, d, gain, shift);
-}
-extern "C" int rap_qknorm_h16(int32_t dtype, uint16_t* qk, int64_t TP, int32_t heads, const float* gamma_q,
-                              const float* gamma_k, void* stream) {
-  if (!qk || !gamma_q || !gamma_k) return RAP_ERR_INVALID;
-  return launch_qknorm_h16((hipStream_t)stream, dtype, qk, (int)TP, heads, gamma_q, gamma_k, 8.0f);
-}
-
-// ---- split-precision kernel-level entry points (compute dtype 3; paired fp16 head / tail operands, see include/rapflow.h) ----
-extern "C" int rap_x2_pack(const float* src, int64_t ld_src, int64_t rows, int32_t cols, float scale, uint16_t* dst, void* stream) {
-  if (!src || !dst || rows < 0 || cols < 0 || ld_src < cols) return RAP_ERR_INVALID;
-  return launch_x2_pack((hipStream_t)stream, src, (long)ld_src, (long)rows, cols, scale, dst);
-}
-extern "C" int rap_x2_unpack(const uint16_t* src, int64_t rows, int32_t cols, float inv_scale, float* dst, void* stream) {
-  if (!src || !dst || rows < 0 || cols < 0) return RAP_ERR_INVALID;
-  return launch_x2_unpack((hipStream_t)stream, src, (long)rows, cols, inv_scale, dst);
-}
-extern "C" int rap_x2_gemm(int32_t epilogue, const uint16_t* A, int32_t lda, const uint16_t* W, int32_t ldw, void* C, int32_t ldc, int32_t M,
-                           int32_t N, int32_t K_physical, const float* bias, const float* resid, int32_t ldr, float acc_scale, int32_t heads,
-                           const float* gamma_q, const float* gamma_k, float q_mul, uint16_t* vt, int32_t vt_nblk, void* stream) {
-  if (!A || !W || !C) return RAP_ERR_INVALID;
-  GemmParamsH g{};
-  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K_physical; g.bias = bias;
-  g.resid = resid; g.ldr = ldr; g.heads = heads; g.vt = vt; g.vt_nblk = vt_nblk; g.gamma_q = gamma_q; g.gamma_k = gamma_k;
-  g.q_mul = q_mul; g.acc_scale = acc_scale;
-  return launch_gemm_h16((hipStream_t)stream, RAP_DT_F32X2, epilogue, g);
-}
-extern "C" int rap_x2_attention(const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens, int32_t nseg,
-                                uint16_t* out, int64_t TP, int32_t heads, void* ws, size_t ws_bytes, void* stream_) {
-  if (!qk || !vt || !cu_seqlens || !out || nseg < 0 || TP < 0 || TP > 0x7fffffffLL / 16) return RAP_ERR_INVALID;
-  if (!ws || ws_bytes < rap_attention_workspace_bytes(TP, nseg)) return RAP_ERR_WORKSPACE;
-  const int max_items = (int)(TP / RAP_ATTN_BQ) + nseg + 1;
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc;
-  if ((rc = attn_ws_sanitize(stream, cu_seqlens, nseg, TP, ws, &cu_seqlens))) return rc;
-  if ((rc = launch_build_attn_worklist(stream, cu_seqlens, nseg, (AttnWorkItem*)ws, max_items, 256))) return rc;
-  return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items);
-}
-
-// ---------------------------------------------------------------------------------------------
-// generation selection by rigidity
-// ---------------------------------------------------------------------------------------------
-struct RigWs { int32_t* off; double* partials; float* Rc; float* tc; float* per_step; size_t total; };
-static RigWs carve_rig(int nparts, int S, int B, char* basep) {
-  RigWs p; size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = basep ? basep + off : nullptr; off += align_up(bytes, 256); return r; };
-  p.off = (int32_t*)take(((size_t)nparts + 1) * 4);
-  p.partials = (double*)take((size_t)nparts * RAP_PROC_CHUNKS * 16 * 8);
-  p.Rc = (float*)take((size_t)nparts * 9 * 4);
-  p.tc = (float*)take((size_t)nparts * 3 * 4);
-  p.per_step = (float*)take((size_t)(S > 0 ? S : 1) * B * 4);
-  p.total = off;
-  return p;
-}
-extern "C" size_t rap_rigidity_workspace_bytes(int32_t nparts, int32_t steps, int32_t B) {
-  return (nparts < 0 || steps < 0 || B < 0) ? 0 : carve_rig(nparts, steps, B, nullptr).total;
-}
-
-extern "C" int rap_rigidity_rmse(const float* cond, const float* pred, const float* R, const float* t,
-                                 const int64_t* points_per_part, int32_t B, int32_t P, const float* scales,
-                                 int32_t average_per_part, float* out, void* ws, size_t ws_bytes, void* stream_) {
-  if (!cond || !pred || !R || !t || !points_per_part || !out || B <= 0 || P <= 0) return RAP_ERR_INVALID;
-  if ((int64_t)B * P > 65535) return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  RigWs w = carve_rig(B * P, 0, B, (char*)ws);
-  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc;
-  if ((rc = launch_part_offsets(stream, points_per_part, B * P, w.off))) return rc;
-  return launch_rigidity_rmse(stream, cond, pred, R, t, w.off, B, P, scales, average_per_part, out, w.partials);
-}
-
-extern "C" int rap_trajectory_rigidity_rmse(const float* cond, const float* traj, const int64_t* points_per_part, int32_t B,
-                                            int32_t P, int64_t TP, int32_t steps, const float* scales, float* mean_out,
-                                            float* per_step_out, void* ws, size_t ws_bytes, void* stream_) {
-  if (!cond || !traj || !points_per_part || !mean_out || B <= 0 || P <= 0 || TP <= 0 || steps <= 0) return RAP_ERR_INVALID;
-  if ((int64_t)B * P > 65535) return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  RigWs w = carve_rig(B * P, steps, B, (char*)ws);
-  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  float* per_step = per_step_out ? per_step_out : w.per_step;
-  int rc;
-  if ((rc = launch_part_offsets(stream, points_per_part, B * P, w.off))) return rc;
-  for (int s = 0; s < steps; ++s) {
-    const float* x0 = traj + (size_t)s * TP * 3;
-    if ((rc = launch_procrustes_fit(stream, cond, x0, w.off, B * P, w.Rc, w.tc, w.partials))) return rc;      // modeling.py:479-481
-    if ((rc = launch_rigidity_rmse(stream, cond, x0, w.Rc, w.tc, w.off, B, P, scales, 0, per_step + (size_t)s * B, w.partials)))
-      return rc;                                                                                              // :484-487
-  }
-  return launch_step_mean(stream, per_step, steps, B, mean_out);                                             // :489
-}
-
-extern "C" int rap_select_generation(const float* rmse, int32_t G, int32_t B, int32_t P, int64_t TP, const int32_t* cu_batch,
-                                     const float* clouds, const float* R, const float* t, int32_t pick_largest,
-                                     int32_t* best_out, float* cloud_out, float* R_out, float* t_out, void* stream) {
-  if (!rmse || !best_out || G <= 0 || B <= 0) return RAP_ERR_INVALID;
-  if (clouds && (!R || !t || !cu_batch || !cloud_out || !R_out || !t_out || P <= 0 || TP <= 0)) return RAP_ERR_INVALID;
-  return launch_select_generation((hipStream_t)stream, rmse, G, B, P, (long)TP, cu_batch, clouds, R, t, pick_largest, best_out,
-                                  cloud_out, R_out, t_out);
-}
-
-extern "C" int rap_relative_transforms(const float* R_pred, const float* t_pred, const float* R_gt, const float* t_gt,
-                                       const float* scales, const int64_t* points_per_part, int32_t B, int32_t P,
-                                       const float* global_rotation, const float* global_translation, float* out, void* stream) {
-  if (!R_pred || !t_pred || !R_gt || !t_gt || !scales || !points_per_part || !out || B <= 0 || P <= 0) return RAP_ERR_INVALID;
-  if ((global_rotation == nullptr) != (global_translation == nullptr)) return RAP_ERR_INVALID;
-  return launch_relative_transforms((hipStream_t)stream, R_pred, t_pred, R_gt, t_gt, scales, points_per_part, B, P,
-                                    global_rotation, global_translation, out);
-}
-
-// ---------------------------------------------------------------------------------------------
-// cross-part overlap ratio
-// ---------------------------------------------------------------------------------------------
-// compute_transform_errors without ICP (reference eval/metrics.py:165-303): see transforms.hip
-extern "C" int rap_transform_errors(const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred,
-                                    const int64_t* points_per_part, const uint8_t* anchor_part, const int64_t* matched_part_ids,
-                                    const float* scale, int32_t B, int32_t P, float* rot_err_per_part, float* trans_err_per_part,
-                                    float* rot_err_mean, float* trans_err_mean, void* stream) {
-  if (!R_gt || !t_gt || !R_pred || !t_pred || !points_per_part || !anchor_part || !rot_err_per_part || !trans_err_per_part ||
-      !rot_err_mean || !trans_err_mean || B <= 0 || P <= 0)
-    return RAP_ERR_INVALID;
-  return launch_transform_errors((hipStream_t)stream, R_gt, t_gt, R_pred, t_pred, points_per_part, anchor_part, matched_part_ids, scale,
-                                 B, P, rot_err_per_part, trans_err_per_part, rot_err_mean, trans_err_mean);
-}
-
-struct OvWs { int32_t* off; int32_t* pid; float* min_dist; void* items; size_t total; };
-static OvWs carve_ov(int64_t TP, int B, int P, char* basep) {
-  OvWs w; size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = basep ? basep + off : nullptr; off += align_up(bytes, 256); return r; };
-  w.off = (int32_t*)take(((size_t)B * P + 1) * 4);
-  w.pid = (int32_t*)take((size_t)TP * 4);
-  w.min_dist = (float*)take((size_t)TP * 4);
-  w.items = take(overlap_max_items((long)TP, B) * 16);
-  w.total = off;
-  return w;
-}
-extern "C" size_t rap_overlap_workspace_bytes(int64_t TP, int32_t B, int32_t P) {
-  return (TP < 0 || B < 0 || P < 0) ? 0 : carve_ov(TP, B, P, nullptr).total;
-}
-extern "C" int rap_overlap_ratio(const float* pointclouds_pred, const int64_t* points_per_part, const int32_t* cu_batch, int32_t B,
-                                 int32_t P, int64_t TP, const float* h_taus, int32_t n_taus, float* ratios_out, float* min_dist_out,
-                                 void* ws, size_t ws_bytes, void* stream_) {
-  if (!pointclouds_pred || !points_per_part || !cu_batch || !h_taus || !ratios_out || B <= 0 || P <= 0 || TP <= 0) return RAP_ERR_INVALID;
-  if ((int64_t)B * P > 65535 || TP > 0x7fffffffLL / 8) return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  OvWs w = carve_ov(TP, B, P, (char*)ws);
-  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc;
-  if ((rc = launch_part_offsets(stream, points_per_part, B * P, w.off))) return rc;
-  return launch_overlap_ratio(stream, pointclouds_pred, cu_batch, w.off, B, P, (long)TP, h_taus, n_taus, ratios_out,
-                              min_dist_out ? min_dist_out : w.min_dist, w.pid, w.items);
-}
-
-// ---------------------------------------------------------------------------------------------
-// MiniSpinNet local feature extractor
-// ---------------------------------------------------------------------------------------------
-#include <cmath>
-struct SpinLayer { int Cin, Cout, Kd, ldw; bool bn_relu; const float* W; const float* b; const float* Wt; const float* bt; };   // Wt / bt: tap-major (implicit GEMM)
-struct rap_spinnet {
-  float* raw = nullptr;       // the caller's blob (MiniSpinNet.state_dict() float tensors, registration order)
-  float* derived = nullptr;   // folded + padded conv weights / biases, voxel table, pool weights
-  float h_w1[48], h_b1[16];   // point MLP with BatchNorm folded (kernel argument)
-  const float* vox;           // (420,3)
-  const void* pool_w;         // SpinPoolW on the device
-  SpinLayer layers[8];
-  const float* zeros = nullptr;   // 256 bytes of zeros: the elevation pad of the implicit-GEMM convolutions
-};
-static const int kSpinCin[8] = {16, 64, 64, 128, 128, 64, 64, 32};
-static const int kSpinCout[8] = {64, 64, 128, 128, 64, 64, 32, 32};
-
-extern "C" int64_t rap_spinnet_weight_count(void) {
-  int64_t n = 48 + 16 * 5 + (512 + 16 * 5 + 16 + 5);
-  for (int i = 0; i < 8; ++i) {
-    const int64_t kd = (int64_t)kSpinCin[i] * (i == 0 ? 27 : 9);
-    n += kSpinCout[i] * kd + kSpinCout[i] + (i < 7 ? 2 * kSpinCout[i] : 0);
-  }
-  return n;
-}
-
-extern "C" void rap_spinnet_destroy(rap_spinnet* m) {
-  if (!m) return;
-  if (m->raw) (void)hipFree(m->raw);
-  if (m->derived) (void)hipFree(m->derived);
-  delete m;
-}
-
-extern "C" int rap_spinnet_create(const float* d_weights, int64_t n_floats, void* stream_, rap_spinnet** out) {
-  if (!out) return RAP_ERR_INVALID;
-  *out = nullptr;
-  if (!d_weights || n_floats != rap_spinnet_weight_count()) return RAP_ERR_INVALID;
-  hipStream_t stream = (hipStream_t)stream_;
-  rap_spinnet* m = new (std::nothrow) rap_spinnet();
-  if (!m) return RAP_ERR_ALLOC;
-  auto fail = [&](int code) { rap_spinnet_destroy(m); return code; };
-  if (hipMalloc((void**)&m->raw, (size_t)n_floats * 4) != hipSuccess) { delete m; return RAP_ERR_ALLOC; }
-  size_t n_der = 420 * 3 + 1024;      // voxel table + pool struct (613 floats used)
-  for (int i = 0; i < 8; ++i) n_der += (size_t)128 * (i == 0 ? 448 : kSpinCin[i] * 9) + 128 + (i ? (size_t)kSpinCout[i] * kSpinCin[i] * 9 + 128 : (size_t)64 * 448 + 128);
-  n_der += 64;      // zero page
-  if (hipMalloc((void**)&m->derived, n_der * 4) != hipSuccess) return fail(RAP_ERR_ALLOC);
-  if (hipMemcpyAsync(m->raw, d_weights, (size_t)n_floats * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) return fail(RAP_ERR_HIP);
-  // ---- small heads on the host: point MLP (128 floats) and attention pool (613 floats)
-  std::vector<float> h(128 + 613);
-  if (hipMemcpyAsync(h.data(), m->raw, h.size() * 4, hipMemcpyDeviceToHost, stream) != hipSuccess) return fail(RAP_ERR_HIP);
-  if (hipStreamSynchronize(stream) != hipSuccess) return fail(RAP_ERR_HIP);
-  {
-    const float *W = &h[0], *b = &h[48], *g = &h[64], *be = &h[80], *rm = &h[96], *rv = &h[112];
-    for (int c = 0; c < 16; ++c) {
-      const float s = g[c] / std::sqrt(rv[c] + 1e-5f);
-      for (int d = 0; d < 3; ++d) m->h_w1[c * 3 + d] = W[c * 3 + d] * s;
-      m->h_b1[c] = (b[c] - rm[c]) * s + be[c];
-    }
-  }
-  std::vector<float> pool(16 * 32 + 16 + 16 + 1);
-  {
-    const float* p0 = &h[128];
-    const float *W1 = p0, *b1 = p0 + 512, *g1 = p0 + 528, *be1 = p0 + 544, *rm1 = p0 + 560, *rv1 = p0 + 576;
-    const float *W2 = p0 + 592, *b2 = p0 + 608, *g2 = p0 + 609, *be2 = p0 + 610, *rm2 = p0 + 611, *rv2 = p0 + 612;
-    for (int j = 0; j < 16; ++j) {
-      const float s = g1[j] / std::sqrt(rv1[j] + 1e-5f);
-      for (int c = 0; c < 32; ++c) pool[j * 32 + c] = W1[j * 32 + c] * s;
-      pool[512 + j] = (b1[j] - rm1[j]) * s + be1[j];
-    }
-    const float s2 = g2[0] / std::sqrt(rv2[0] + 1e-5f);
-    for (int j = 0; j < 16; ++j) pool[528 + j] = W2[j] * s2;
-    pool[544] = (b2[0] - rm2[0]) * s2 + be2[0];
-  }
-  // ---- voxel centres: get_voxel_coordinate(radius 1, rad_n 3, azi_n 20, ele_n 7)  (utils/common.py:213-225, 338-372, 387-393)
-  std::vector<float> vox(420 * 3);
-  for (int r = 0; r < 3; ++r)
-    for (int e = 0; e < 7; ++e)
-      for (int a = 0; a < 20; ++a) {
-        const double beta = M_PI * e / 7.0 + M_PI / 7.0 / 2.0, alpha = 2.0 * M_PI * a / 20.0 + M_PI / 20.0;
-        const double sc = (double)r / 3.0 + 1.0 / 6.0;
-        float* v = &vox[((r * 7 + e) * 20 + a) * 3];
-        v[0] = (float)(sc * std::sin(beta) * std::cos(alpha));
-        v[1] = (float)(sc * std::sin(beta) * std::sin(alpha));
-        v[2] = (float)(sc * std::cos(beta));
-      }
-  float* q = m->derived;
-  if (hipMemcpyAsync(q, vox.data(), vox.size() * 4, hipMemcpyHostToDevice, stream) != hipSuccess) return fail(RAP_ERR_HIP);
-  m->vox = q; q += 420 * 3;
-  if (hipMemcpyAsync(q, pool.data(), pool.size() * 4, hipMemcpyHostToDevice, stream) != hipSuccess) return fail(RAP_ERR_HIP);
-  m->pool_w = q; q += 1024;
-  if (hipStreamSynchronize(stream) != hipSuccess) return fail(RAP_ERR_HIP);   // vox / pool are stack-backed host vectors
-  // ---- conv stack: fold BatchNorm (affine=False) and pad to 128 output columns / 32-multiple k
-  const float* p = m->raw + 128 + 613;
-  for (int i = 0; i < 8; ++i) {
-    SpinLayer& L = m->layers[i];
-    L.Cin = kSpinCin[i]; L.Cout = kSpinCout[i]; L.Kd = L.Cin * (i == 0 ? 27 : 9); L.ldw = i == 0 ? 448 : L.Kd; L.bn_relu = i < 7;
-    const float* W = p; p += (size_t)L.Cout * L.Kd;
-    const float* b = p; p += L.Cout;
-    const float *rm = nullptr, *rv = nullptr;
-    if (L.bn_relu) { rm = p; p += L.Cout; rv = p; p += L.Cout; }
-    float* Wd = q; q += (size_t)128 * L.ldw;
-    float* bd = q; q += 128;
-    int rc;
-    if ((rc = launch_spin_fold(stream, W, b, nullptr, nullptr, rm, rv, L.Cout, L.Kd, Wd, L.ldw, 128, bd))) return fail(rc);
-    L.W = Wd; L.b = bd; L.Wt = nullptr; L.bt = nullptr;
-    {
-      const int ldt = i == 0 ? 448 : L.Kd;
-      float* Wt = q; q += (size_t)L.Cout * ldt;
-      float* bt = q; q += 128;
-      if ((rc = launch_spin_fold_tapmajor(stream, W, b, rm, rv, L.Cin, L.Cout, i == 0 ? 27 : 9, ldt, Wt, bt))) return fail(rc);
-      L.Wt = Wt; L.bt = bt;
-    }
-  }
-  if (hipMemsetAsync(q, 0, 256, stream) != hipSuccess) return fail(RAP_ERR_HIP);
-  m->zeros = q; q += 64;
-  if ((int64_t)(p - m->raw) != n_floats) return fail(RAP_ERR_INVALID);
-  *out = m;
-  return RAP_OK;
-}
-
-struct SpinWs { float *x0, *A, *Y0, *Y1; size_t total; };
-static SpinWs carve_spin(int Kc, char* basep) {
-  SpinWs w; size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = basep ? basep + off : nullptr; off += align_up(bytes, 256); return r; };
-  w.x0 = (float*)take((size_t)Kc * 420 * 16 * 4);
-  w.A = (float*)take((size_t)Kc * 140 * 1152 * 4);
-  w.Y0 = (float*)take((size_t)Kc * 140 * 128 * 4);
-  w.Y1 = (float*)take((size_t)Kc * 140 * 128 * 4);
-  w.total = off;
-  return w;
-}
-extern "C" size_t rap_spinnet_workspace_bytes(int32_t keypoints_per_chunk) {
-  return keypoints_per_chunk <= 0 ? 0 : carve_spin(keypoints_per_chunk, nullptr).total;
-}
-
-extern "C" int rap_spinnet_describe(const rap_spinnet* m, const float* pts, const int32_t* perm, int64_t N, const float* kpts,
-                                    int32_t K, float des_r, int32_t flags, float* desc_out, int32_t keypoints_per_chunk, void* ws,
-                                    size_t ws_bytes, void* stream_) {
-  if (!m || !pts || !kpts || !desc_out || N <= 0 || K < 0 || !(des_r > 0.f) || keypoints_per_chunk <= 0) return RAP_ERR_INVALID;
-  if (flags & ~(RAP_SPINNET_PATCH_LRF | RAP_SPINNET_IM2COL_PATH)) return RAP_ERR_INVALID;
-  // per-call options (round 3, ADVICE r02: they used to be mutable state of the handle, a race between two callers of one model)
-  const int lrf = (flags & RAP_SPINNET_PATCH_LRF) ? 1 : 0;
-  const bool implicit = !(flags & RAP_SPINNET_IM2COL_PATH);
-  if (K == 0) return RAP_OK;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  SpinWs w = carve_spin(keypoints_per_chunk, (char*)ws);
-  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  int rc;
-  for (int k0 = 0; k0 < K; k0 += keypoints_per_chunk) {
-    const int Kc = K - k0 < keypoints_per_chunk ? K - k0 : keypoints_per_chunk;
-    const int M = Kc * 140;
-    if ((rc = launch_spin_patch(stream, pts, perm, (long)N, kpts + (size_t)k0 * 3, Kc, des_r, m->vox, m->h_w1, m->h_b1, w.x0, lrf))) return rc;
-    float* yin = nullptr;
-    float* yout = w.Y0;
-    int ld_in = 128;
-    for (int i = 0; i < 8; ++i) {
-      const SpinLayer& L = m->layers[i];
-      if (implicit) {
-        // implicit GEMM: the gather of the 3x3(x3) cylindrical neighbourhood happens in the DMA source addresses, output is dense (M, Cout)
-        if (i == 0) rc = launch_spin_conv3d(stream, w.x0, L.Wt, L.bt, m->zeros, yout, M);
-        else rc = launch_spin_conv3x3(stream, yin, ld_in, L.Cin, L.Wt, L.bt, m->zeros, yout, L.Cout, M, L.bn_relu);
-        if (rc) return rc;
-        ld_in = L.Cout;
-      } else {
-        if (i == 0) rc = launch_spin_im2col3d(stream, w.x0, Kc, w.A, L.ldw);
-        else rc = launch_spin_im2col2d(stream, yin, 128, L.Cin, Kc, w.A);
-        if (rc) return rc;
-        GemmParams g{};
-        g.A = w.A; g.lda = L.ldw; g.W = L.W; g.ldw = L.ldw; g.C = yout; g.ldc = 128; g.M = M; g.N = 128; g.K = L.ldw; g.bias = L.b;
-        if ((rc = launch_gemm_f32(stream, L.bn_relu ? EPI_BIAS_RELU : EPI_BIAS, g))) return rc;
-        ld_in = 128;
-      }
-      yin = yout; yout = (yout == w.Y0) ? w.Y1 : w.Y0;
-    }
-    if ((rc = launch_spin_pool(stream, yin, ld_in, Kc, m->pool_w, desc_out + (size_t)k0 * 32))) return rc;
-  }
-  return RAP_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// nearest-neighbour registration metrics
-// ---------------------------------------------------------------------------------------------
-struct NnWs { float* d2a; float* d2b; int32_t* nn; NnWork* items; size_t total; };
-static NnWs carve_nn(int64_t n, int B, char* basep) {
-  NnWs w; size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = basep ? basep + off : nullptr; off += align_up(bytes, 256); return r; };
-  w.d2a = (float*)take((size_t)n * 4);
-  w.d2b = (float*)take((size_t)n * 4);
-  w.nn = (int32_t*)take((size_t)n * 4);
-  w.items = (NnWork*)take(nn_max_items((long)n, B) * sizeof(NnWork));
-  w.total = off;
-  return w;
-}
-extern "C" size_t rap_nn_metrics_workspace_bytes(int64_t n_points, int32_t B) {
-  return (n_points < 0 || B < 0) ? 0 : carve_nn(n_points, B, nullptr).total;
-}
-extern "C" int rap_chamfer_rmse(const float* pointclouds_gt, const float* pointclouds_pred, const int32_t* cu_batch, int32_t B,
-                                int64_t TP, float* out, void* ws, size_t ws_bytes, void* stream) {
-  if (!pointclouds_gt || !pointclouds_pred || !cu_batch || !out || B <= 0 || TP <= 0 || TP > 0x7fffffffLL / 8) return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  NnWs w = carve_nn(TP, B, (char*)ws);
-  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
-  return launch_chamfer_rmse((hipStream_t)stream, pointclouds_gt, pointclouds_pred, cu_batch, B, (long)TP, out, w.d2a, w.d2b, w.items);
-}
-extern "C" int rap_correspondence_rmse(const float* source_gt, const float* target_gt, const float* source_pred,
-                                       const float* target_pred, int32_t n_source, int32_t n_target, float distance_threshold,
-                                       float* out3, void* ws, size_t ws_bytes, void* stream) {
-  if (!source_gt || !target_gt || !source_pred || !target_pred || !out3 || n_source <= 0 || n_target <= 0) return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  NnWs w = carve_nn(n_source, 1, (char*)ws);
-  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
-  return launch_correspondence_rmse((hipStream_t)stream, source_gt, target_gt, source_pred, target_pred, n_source, n_target,
-                                    distance_threshold, out3, w.d2a, w.nn, w.items);
-}
-
-// batched scan-pair metrics of the evaluator + compute_transform_errors_direct: see pair_metrics.hip
-struct PairWs { NnWork* items; void* partials; void* ranges; size_t total; };
-static PairWs carve_pair(int64_t n, int B, char* basep) {
-  PairWs w; size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = basep ? basep + off : nullptr; off += align_up(bytes, 256); return r; };
-  const size_t max_items = nn_max_items((long)n, B);
-  w.items = (NnWork*)take(max_items * sizeof(NnWork));
-  w.partials = take(max_items * 16);
-  w.ranges = take((size_t)B * 16);
-  w.total = off;
-  return w;
-}
-extern "C" size_t rap_pair_metrics_workspace_bytes(int64_t n_points, int32_t B) {
-  return (n_points < 0 || B < 0) ? 0 : carve_pair(n_points, B, nullptr).total;
-}
-extern "C" int rap_pair_metrics(const float* pointclouds_gt, const float* cloud, const int64_t* points_per_part, const int32_t* cu_batch,
-                                const float* scales, const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred,
-                                int32_t B, int64_t TP, float distance_threshold, float* out4, void* ws, size_t ws_bytes, void* stream) {
-  if (!pointclouds_gt || !cloud || !points_per_part || !cu_batch || !scales || !R_gt || !t_gt || !out4 || B <= 0 || TP <= 0 ||
-      TP > 0x7fffffffLL / 8 || !(distance_threshold >= 0.0f))
-    return RAP_ERR_INVALID;
-  if ((R_pred == nullptr) != (t_pred == nullptr)) return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  PairWs w = carve_pair(TP, B, (char*)ws);
-  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
-  return launch_pair_metrics((hipStream_t)stream, pointclouds_gt, cloud, points_per_part, cu_batch, scales, R_gt, t_gt, R_pred, t_pred, B,
-                             (long)TP, distance_threshold, out4, w.items, w.partials, w.ranges);
-}
-extern "C" int rap_transform_errors_direct(const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred,
-                                           const int64_t* points_per_part, const int64_t* matched_part_ids, const float* scale, int32_t B,
-                                           int32_t P, float* rot_err_per_part, float* trans_err_per_part, float* rot_err_mean,
-                                           float* trans_err_mean, void* stream) {
-  if (!R_gt || !t_gt || !R_pred || !t_pred || !points_per_part || !rot_err_per_part || !trans_err_per_part || !rot_err_mean ||
-      !trans_err_mean || B <= 0 || P <= 0)
-    return RAP_ERR_INVALID;
-  return launch_transform_errors_direct((hipStream_t)stream, R_gt, t_gt, R_pred, t_pred, points_per_part, matched_part_ids, scale, B, P,
-                                        rot_err_per_part, trans_err_per_part, rot_err_mean, trans_err_mean);
-}
-
-extern "C" int rap_farthest_point_sampling(const float* points, const int32_t* cloud_start, const int32_t* cloud_len,
-                                           const int32_t* k_per_cloud, const int32_t* start_idx, int32_t n_clouds, int32_t k_max,
-                                           int32_t* indices_out, float* dist_ws, void* stream) {
-  if (!points || !cloud_start || !cloud_len || !k_per_cloud || !start_idx || !indices_out || !dist_ws || n_clouds <= 0 || k_max <= 0)
-    return RAP_ERR_INVALID;
-  return launch_fps((hipStream_t)stream, points, cloud_start, cloud_len, k_per_cloud, start_idx, n_clouds, k_max, dist_ws, indices_out);
-}
-
-// ---------------------------------------------------------------------------------------------
-// voxel down-sampling (preprocessing)
-// ---------------------------------------------------------------------------------------------
-extern "C" int rap_voxel_bounds(const float* points, int64_t N, float voxel_size, int64_t* bounds6_out, float* dist_max_out,
-                                void* stream) {
-  if (!points || !bounds6_out || !dist_max_out || N <= 0 || !(voxel_size > 0.f)) return RAP_ERR_INVALID;
-  return launch_voxel_bounds((hipStream_t)stream, points, (long)N, voxel_size, (long long*)bounds6_out, (unsigned int*)dist_max_out);
-}
-static int64_t voxel_slots(const int64_t* b) {
-  int64_t v = 0;
-  for (int a = 0; a < 3; ++a) v = (b[3 + a] - b[a]) > v ? (b[3 + a] - b[a]) : v;
-  if (v > 2000000) return -1;
-  const __int128 s = (__int128)v + (__int128)v * v + (__int128)v * v * v + 1;      // largest key gx + gy v + gz v^2 with g <= v, plus one
-  return s > ((__int128)1 << 33) ? -1 : (int64_t)s;
-}
-extern "C" int64_t rap_voxel_table_slots(const int64_t* h_bounds6) { return h_bounds6 ? voxel_slots(h_bounds6) : -1; }
-extern "C" size_t rap_voxel_workspace_bytes(const int64_t* h_bounds6) {
-  const int64_t s = h_bounds6 ? voxel_slots(h_bounds6) : -1;
-  if (s < 0) return 0;
-  return align_up((size_t)s * 8, 256) + align_up((size_t)((s + 4095) / 4096) * 4, 256) + 256;
-}
-extern "C" int rap_voxel_downsample(const float* points, int64_t N, float voxel_size, const int64_t* h_bounds6, float dist_max,
-                                    int64_t* indices_out, int32_t* count_out, void* ws, size_t ws_bytes, void* stream) {
-  if (!points || !h_bounds6 || !indices_out || !count_out || N <= 0 || N > 0xffffffffLL || !(voxel_size > 0.f)) return RAP_ERR_INVALID;
-  const int64_t slots = voxel_slots(h_bounds6);
-  if (slots < 0) return RAP_ERR_INVALID;                 // grid too large for the dense table (> 2^33 slots = 64 GiB)
-  if (!ws || ws_bytes < rap_voxel_workspace_bytes(h_bounds6)) return RAP_ERR_WORKSPACE;
-  char* base = (char*)ws;
-  unsigned long long* table = (unsigned long long*)base;
-  unsigned int* block_cnt = (unsigned int*)(base + align_up((size_t)slots * 8, 256));
-  return launch_voxel_downsample((hipStream_t)stream, points, (long)N, voxel_size, (const long long*)h_bounds6,
-                                 dist_max > 0.f ? dist_max : 1.f, table, (long)slots, block_cnt, (unsigned int*)count_out,
-                                 (long long*)indices_out);
-}
-
-// exact number of occupied voxels (calculate_voxel_coverage, point_sampling_utils.py:11-31): h_bounds6 from rap_voxel_bounds
-static int64_t coverage_slots(const int64_t* b) {
-  const __int128 s = (__int128)(b[3] - b[0] + 1) * (b[4] - b[1] + 1) * (b[5] - b[2] + 1);
-  return (s <= 0 || s > ((__int128)1 << 36)) ? -1 : (int64_t)s;          // 64 GiB of one-byte slots
-}
-extern "C" size_t rap_voxel_coverage_workspace_bytes(const int64_t* h_bounds6) {
-  const int64_t s = h_bounds6 ? coverage_slots(h_bounds6) : -1;
-  return s < 0 ? 0 : align_up((size_t)s, 256) + 256;
-}
-extern "C" int rap_voxel_coverage(const float* points, int64_t N, float voxel_size, const int64_t* h_bounds6, int64_t* count_out, void* ws,
-                                  size_t ws_bytes, void* stream) {
-  if (!points || !h_bounds6 || !count_out || N <= 0 || !(voxel_size > 0.f)) return RAP_ERR_INVALID;
-  const int64_t slots = coverage_slots(h_bounds6);
-  if (slots < 0) return RAP_ERR_INVALID;
-  if (!ws || ws_bytes < rap_voxel_coverage_workspace_bytes(h_bounds6)) return RAP_ERR_WORKSPACE;
-  return launch_voxel_coverage((hipStream_t)stream, points, (long)N, voxel_size, (const long long*)h_bounds6, (unsigned char*)ws, (long)slots,
-                               (unsigned long long*)count_out);
-}
-
-// O(N)-memory variants of the two calls above (voxel_sort.hip): identical results from a radix sort of per-point keys.  For grids whose
-// dense table is large against N or beyond its 2^33 / 2^36-slot limits (a 100 m scene at 5 cm voxels = 64 GB of table).
-extern "C" size_t rap_voxel_sorted_workspace_bytes(int64_t N) { return N > 0 && N <= 0xffffffffLL ? voxel_sorted_workspace_bytes((long)N) : 0; }
-extern "C" int rap_voxel_downsample_sorted(const float* points, int64_t N, float voxel_size, const int64_t* h_bounds6, float dist_max,
-                                           int64_t* indices_out, int32_t* count_out, void* ws, size_t ws_bytes, void* stream) {
-  if (!points || !h_bounds6 || !indices_out || !count_out || N <= 0 || N > 0xffffffffLL || !(voxel_size > 0.f)) return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  return launch_voxel_downsample_sorted((hipStream_t)stream, points, (long)N, voxel_size, (const long long*)h_bounds6,
-                                        dist_max > 0.f ? dist_max : 1.f, ws, ws_bytes, (long long*)indices_out, count_out);
-}
-extern "C" int rap_voxel_coverage_sorted(const float* points, int64_t N, float voxel_size, const int64_t* h_bounds6, int64_t* count_out,
-                                         void* ws, size_t ws_bytes, void* stream) {
-  if (!points || !h_bounds6 || !count_out || N <= 0 || N > 0xffffffffLL || !(voxel_size > 0.f)) return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  return launch_voxel_coverage_sorted((hipStream_t)stream, points, (long)N, voxel_size, (const long long*)h_bounds6, ws, ws_bytes,
-                                      (long long*)count_out);
-}
-
-// ---------------------------------------------------------------------------------------------
-// input side of the boundary: raw parts -> the packed batch
-// ---------------------------------------------------------------------------------------------
-extern "C" size_t rap_collate_workspace_bytes(int32_t B, int32_t P) {
-  if (B <= 0 || P <= 0) return 0;
-  return collate_workspace_bytes(B, P);
-}
-
-extern "C" int rap_collate_transform(const void* points, int32_t points_are_f64, const int64_t* points_per_part, int32_t B, int32_t P,
-                                     int64_t TP, const int64_t* order, const float* feat_in, int32_t F, float* cond, float* gt,
-                                     float* feat_out, uint8_t* anchor_indices, int64_t* part_indices, float* rotations,
-                                     float* translations, float* scales, uint8_t* anchor_parts, float* global_translation,
-                                     int64_t* cu_seqlens, int32_t* order_flag, void* ws, size_t ws_bytes, void* stream) {
-  if (!points || !points_per_part || !cond || !gt || !anchor_indices || !part_indices || !rotations || !translations || !scales ||
-      !anchor_parts || !global_translation || !cu_seqlens)
-    return RAP_ERR_INVALID;
-  if (B <= 0 || P <= 0 || P > 256 || (int64_t)B * P > 65535 || TP < 0 || TP > 0x7fffffffLL / 8 || F < 0) return RAP_ERR_INVALID;
-  if (F > 0 && (!feat_in || !feat_out)) return RAP_ERR_INVALID;
-  if (!ws || ws_bytes < collate_workspace_bytes(B, P)) return RAP_ERR_WORKSPACE;
-  return launch_collate_transform((hipStream_t)stream, points, points_are_f64 ? 1 : 0, points_per_part, B, P, (long)TP, order, feat_in, F,
-                                  cond, gt, feat_out, anchor_indices, part_indices, rotations, translations, scales, anchor_parts,
-                                  global_translation, cu_seqlens, order_flag, ws);
-}
-
-// Consistency of a packed batch: see check_batch_kernel.  flag_out: device int32 (0 = consistent).
-extern "C" int rap_check_batch(const int64_t* points_per_part, const int32_t* cu_batch, int32_t B, int32_t P, int64_t TP,
-                               int32_t* flag_out, void* stream) {
-  if (!points_per_part || !cu_batch || !flag_out || B <= 0 || P <= 0 || TP < 0) return RAP_ERR_INVALID;
-  return launch_check_batch((hipStream_t)stream, points_per_part, cu_batch, B, P, (long)TP, flag_out);
-}
-
-extern "C" int rap_poison_on_flag(const int32_t* flag, float* buf, int64_t n, void* stream) {
-  if (!flag || !buf || n < 0) return RAP_ERR_INVALID;
-  return launch_poison_on_flag((hipStream_t)stream, flag, buf, (long)n);
-}
-
-// ---------------------------------------------------------------------------------------------
-// statistical outlier removal (preprocessing)
-// ---------------------------------------------------------------------------------------------
-extern "C" size_t rap_outlier_workspace_bytes(int64_t N) { return N <= 0 ? 0 : outlier_workspace_bytes((long)N); }
-
-extern "C" int rap_statistical_outliers(const float* points, int64_t N, int32_t nb_neighbors, double std_ratio, int64_t* inlier_indices,
-                                        int32_t* count_out, double* stats_out, void* ws, size_t ws_bytes, void* stream) {
-  if (!points || !inlier_indices || !count_out || N <= 0 || N > 0x7fffffffLL / 8 || nb_neighbors < 1 || nb_neighbors > 32 || !(std_ratio > 0.0))
-    return RAP_ERR_INVALID;
-  if (!ws || ws_bytes < outlier_workspace_bytes((long)N)) return RAP_ERR_WORKSPACE;
-  return launch_statistical_outliers((hipStream_t)stream, points, (long)N, nb_neighbors, std_ratio, inlier_indices, count_out, stats_out, ws);
-}
-
-// QKV projection with MultiHeadRMSNorm fused into the epilogue (EPI_H_QKV_NORM): see rapflow.h
-extern "C" int rap_gemm_h16_qkvnorm(int32_t dtype, const uint16_t* A, int32_t lda, const uint16_t* W, int32_t ldw, uint16_t* qk_out,
-                                    int32_t M, int32_t K, int32_t heads, const float* gamma_q, const float* gamma_k, float q_mul,
-                                    uint16_t* vt, int32_t vt_nblk, void* stream) {
-  if (!A || !W || !qk_out || !gamma_q || !gamma_k || !vt || heads <= 0) return RAP_ERR_INVALID;
-  GemmParamsH g{};
-  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = qk_out; g.M = M; g.N = 3 * heads * 64; g.K = K; g.heads = heads;
-  g.vt = vt; g.vt_nblk = vt_nblk; g.gamma_q = gamma_q; g.gamma_k = gamma_k; g.q_mul = q_mul;
-  return launch_gemm_h16((hipStream_t)stream, dtype, EPI_H_QKV_NORM, g);
-}

@@ -68,3 +68,12 @@ __device__ __forceinline__ float mul_rn_nofuse(float a, float b) {
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// Carves one caller-owned workspace into consecutive 256-byte-aligned ranges.  With a null base every take() is null and only
+// total() means something: the *_workspace_bytes queries and the calls lay out with the same code.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* base_) : base((char*)base_) {}
+  char* take(size_t bytes) { char* r = base ? base + off : nullptr; off += align_up(bytes, 256); return r; }
+  size_t total() const { return off; }
+};

@@ -69,7 +69,6 @@ struct VoxelSortWs {
   void* temp;
   size_t temp_bytes, total;
 };
-static size_t vs_align(size_t x) { return (x + 255) & ~(size_t)255; }
 static int voxel_sort_carve(long N, char* base, VoxelSortWs& w) {
   size_t t_sort = 0, t_keys = 0, t_scan = 0;
   if (rocprim::radix_sort_pairs(nullptr, t_sort, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned int*)nullptr,
@@ -83,16 +82,15 @@ static int voxel_sort_carve(long N, char* base, VoxelSortWs& w) {
     return RAP_ERR_HIP;
   w.temp_bytes = t_sort > t_keys ? t_sort : t_keys;
   w.temp_bytes = w.temp_bytes > t_scan ? w.temp_bytes : t_scan;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += vs_align(bytes); return p; };
-  w.keys_a = (unsigned long long*)take((size_t)N * 8);
-  w.keys_b = (unsigned long long*)take((size_t)N * 8);
-  w.vals_a = (unsigned int*)take((size_t)N * 4);
-  w.vals_b = (unsigned int*)take((size_t)N * 4);
-  w.flags = (unsigned int*)take((size_t)N * 4);
-  w.pos = (unsigned int*)take((size_t)N * 4);
-  w.temp = take(w.temp_bytes + 256);
-  w.total = off;
+  Carver c(base);
+  w.keys_a = (unsigned long long*)c.take((size_t)N * 8);
+  w.keys_b = (unsigned long long*)c.take((size_t)N * 8);
+  w.vals_a = (unsigned int*)c.take((size_t)N * 4);
+  w.vals_b = (unsigned int*)c.take((size_t)N * 4);
+  w.flags = (unsigned int*)c.take((size_t)N * 4);
+  w.pos = (unsigned int*)c.take((size_t)N * 4);
+  w.temp = c.take(w.temp_bytes + 256);
+  w.total = c.total();
   return RAP_OK;
 }
 size_t voxel_sorted_workspace_bytes(long N) {
