@@ -366,6 +366,7 @@ int rap_adaln_table(const rap_model* m, const float* t, int32_t rows, float* scr
 
 
 /* ---- reduced-precision kernel-level entry points (dtype 1 = bf16, 2 = fp16; 16-bit tensors as uint16_t*) ---- */
+/* dst[i] = round-to-nearest-even(src[i]) for i < n.  n % 4 == 0 (values move four at a time; any other n: RAP_ERR_INVALID before any launch). */
 int rap_convert_h16(int32_t dtype, const float* src, uint16_t* dst, int64_t n, void* stream);
 /* C = A (M,K) W(N,K)^T, fp32 accumulate.  epilogue: 0 C half = acc + bias; 1 C fp32 = (resid +) acc + bias;
  * 7 C fp16 = fp16(resid + acc + bias) with `resid` pointing at an FP16 (M,N) matrix (required; row stride ldr; may alias C): the residual GEMM
@@ -373,7 +374,8 @@ int rap_convert_h16(int32_t dtype, const float* src, uint16_t* dst, int64_t n, v
  * (6 -- this epilogue's number before ABI version 4, and a different epilogue before that -- is refused);
  * 3 GEGLU on value/gate-interleaved W (C half (M,N/2)); 4 qkv split: q,k -> C half [2][H][M][64], v -> vt, the
  * TRANSPOSED image [H][vt_nblk][64 d][64 pos] the attention kernel consumes: token t sits in block t >> 6 at
- * pos = (t & 51) | ((t & 4) << 1) | ((t & 8) >> 1); vt_nblk * 64 >= M rounded up to 256; rows >= M are written as 0. */
+ * pos = (t & 51) | ((t & 4) << 1) | ((t & 8) >> 1); vt_nblk * 64 >= M rounded up to 256; every row from M up to M rounded up to 256 is
+ * written as 0, by whichever kernel the shape selects (blocks beyond that, if vt_nblk is larger, are not touched). */
 int rap_gemm_h16(int32_t dtype, int32_t epilogue, const uint16_t* A, int32_t lda, const uint16_t* W, int32_t ldw, void* C,
                  int32_t ldc, int32_t M, int32_t N, int32_t K, const float* bias, const float* resid, int32_t ldr,
                  int32_t heads, uint16_t* vt, int32_t vt_nblk, void* stream);

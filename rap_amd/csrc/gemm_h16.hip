@@ -497,8 +497,9 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 ? 1 : 2)) void gemm_h16_kerne
   const int wm = wave / WN, wn = wave % WN;
 
   const int nt = p.N / BN;
-  // (the fused QKV epilogue owns the V^T image up to align_up(M, 256) token rows -- zeros beyond M, as the 256-row kernels leave it)
-  const int mt = EPI == EPI_H_QKV_NORM ? ((p.M + 255) / 256) * (256 / BM) : (p.M + BM - 1) / BM;
+  // (both QKV epilogues own the V^T image up to align_up(M, 256) token rows -- zeros beyond M, as the 256-row kernels leave it and as
+  // include/rapflow.h documents; the plain one used to stop at align_up(M, 128), leaving up to 128 rows of the image unwritten)
+  const int mt = (EPI == EPI_H_QKV_NORM || EPI == EPI_H_QKV) ? ((p.M + 255) / 256) * (256 / BM) : (p.M + BM - 1) / BM;
   const int logical = xcd_remap(blockIdx.x, mt * nt);
   const int m0 = (logical / nt) * BM;
   const int n0 = (logical % nt) * BN;
@@ -1300,7 +1301,7 @@ static int launch_cfg(hipStream_t stream, const GemmParamsH& p, int splits = 1) 
     rap_set_last_hip_error((int)hipGetLastError());
     return RAP_ERR_HIP;
   }
-  const int mt = EPI == EPI_H_QKV_NORM ? ((p.M + 255) / 256) * (256 / BM) : (p.M + BM - 1) / BM;
+  const int mt = (EPI == EPI_H_QKV_NORM || EPI == EPI_H_QKV) ? ((p.M + 255) / 256) * (256 / BM) : (p.M + BM - 1) / BM;
   hipLaunchKernelGGL(kern, dim3(mt * (p.N / BN), splits), dim3(64 * WM * WN), LDS, stream, p);
   RAP_LAUNCH_CHECK();
   return RAP_OK;

@@ -26,6 +26,13 @@ RAP_ERR_WORKSPACE = -2
 
 TORCH_DT = {1: torch.bfloat16, 2: torch.float16}
 ULP = {1: 2.0 ** -8, 2: 2.0 ** -11}     # largest relative error of one round-to-nearest into the type
+# the bounds of this file's kernel-level comparisons with fp64 on the rounded operands (stated per test below); tests/test_guards_gpu.py
+# holds the same calls to them
+F32_OUT_BOUND = 2e-5     # fp32 outputs: exact products, fp32 accumulation of K O(1/sqrt(K)) terms
+ONE_ROUNDING = 1.01      # x ULP[dt]: one rounding into the output type, relative to |ref| + 1e-2
+GEGLU_ROUNDINGS = 1.2    # x ULP[dt]
+NORM_SLACK = 1e-4        # added where the rounded value was normalised / accumulated in fp32 first
+ATTN_ULPS = 8            # x ULP[dt], absolute, on |v| ~ 4: P rounded before P V and the output rounded once more
 
 
 @pytest.fixture(scope="module")
@@ -90,10 +97,10 @@ def test_gemm_h16_fp32_out_matches_fp64_on_rounded_operands(lib, dev, dt, M, N, 
     C = torch.full((M, N), float("nan"), device=dev)
     gemm_h(lib, dev, dt, 1, A.to(dev), W.to(dev), C, M, N, K, bias=b.to(dev))
     # exact products (16-bit x 16-bit fits fp32), fp32 accumulation of K O(1/sqrt(K)) terms
-    assert (C.cpu().double() - ref).abs().max().item() < 2e-5
+    assert (C.cpu().double() - ref).abs().max().item() < F32_OUT_BOUND
     C = h.to(dev).clone()
     gemm_h(lib, dev, dt, 1, A.to(dev), W.to(dev), C, M, N, K, bias=b.to(dev), resid=C)      # in place
-    assert (C.cpu().double() - (ref + h.double())).abs().max().item() < 2e-5
+    assert (C.cpu().double() - (ref + h.double())).abs().max().item() < F32_OUT_BOUND
     # 16-bit output
     Ch = torch.full((M, N), float("nan"), dtype=TORCH_DT[dt], device=dev)
     gemm_h(lib, dev, dt, 0, A.to(dev), W.to(dev), Ch, M, N, K, bias=b.to(dev))
@@ -126,7 +133,7 @@ def test_gemm_h16_geglu(lib, dev, dt):
     C = torch.full((M, inner), float("nan"), dtype=TORCH_DT[dt], device=dev)
     gemm_h(lib, dev, dt, 3, Ah.to(dev), Wph.to(dev), C, M, 2 * inner, K, bias=bp, ldc=inner)
     err = (C.cpu().double() - ref).abs() / (ref.abs() + 1e-2)
-    assert err.max().item() < 1.2 * ULP[dt], err.max().item()
+    assert err.max().item() < GEGLU_ROUNDINGS * ULP[dt], err.max().item()
 
 
 @pytest.mark.parametrize("dt", [1, 2])
@@ -142,14 +149,14 @@ def test_gemm_h16_qkv_split_and_transposed_v(lib, dev, dt, M):
     vt = torch.full((H, nblk, 64, 64), float("nan"), dtype=TORCH_DT[dt], device=dev)
     gemm_h(lib, dev, dt, 4, A.to(dev), W.to(dev), qk, M, N, K, heads=H, vt=vt, vt_nblk=nblk)
     err = (qk.cpu().double() - ref[:2]).abs() / (ref[:2].abs() + 1e-2)
-    assert err.max().item() < 1.01 * ULP[dt], err.max().item()
+    assert err.max().item() < ONE_ROUNDING * ULP[dt], err.max().item()
     # vt[h][t >> 6][d][vt_pos(t & 63)] == v[h][t][d]; padding rows of every M tile that was touched are zero
     vtc = vt.cpu().double()
     t = torch.arange(M)
     got = vtc[:, t >> 6, :, vt_pos(t & 63)]            # (M, H, 64): advanced indices first
     want = ref[2].permute(1, 0, 2)                     # (M, H, 64)
     errv = (got - want).abs() / (want.abs() + 1e-2)
-    assert errv.max().item() < 1.01 * ULP[dt], errv.max().item()
+    assert errv.max().item() < ONE_ROUNDING * ULP[dt], errv.max().item()
     m_tiles = 256 if ((M + 255) // 256) * (1536 // 256) >= 256 else 128      # which kernel ran (launch_variant): rows up to its M tile are written
     tp = torch.arange(M, (M + m_tiles - 1) // m_tiles * m_tiles)
     if tp.numel():
@@ -191,13 +198,13 @@ def _check_gemm_h16_qkv_with_fused_qknorm(lib, dev, dt, M, K, q_mul, H):
     _lib.check(rc, "rap_gemm_h16_qkvnorm")
     torch.cuda.synchronize()
     err = (qk.cpu().double() - ref_qk).abs() / (ref_qk.abs() + 1e-2)
-    assert err.max().item() < 1.01 * ULP[dt] + 1e-4, err.max().item()            # one rounding of the normalised value
+    assert err.max().item() < ONE_ROUNDING * ULP[dt] + NORM_SLACK, err.max().item()            # one rounding of the normalised value
     vtc = vt.cpu().double()
     t = torch.arange(M)
     got = vtc[:, t >> 6, :, vt_pos(t & 63)]
     want = x[2].permute(1, 0, 2)
     errv = (got - want).abs() / (want.abs() + 1e-2)
-    assert errv.max().item() < 1.01 * ULP[dt], errv.max().item()
+    assert errv.max().item() < ONE_ROUNDING * ULP[dt], errv.max().item()
     tp = torch.arange(M, (M + 255) // 256 * 256)
     if tp.numel():
         pad = vtc[:, tp >> 6, :, vt_pos(tp & 63)]
@@ -219,7 +226,7 @@ def test_gemm_h16_fp16_residual_epilogue(lib, dev, dt, M, K):
     Ad, Wd, bd, hd = A.to(dev), W.to(dev), bias.to(dev), h0.to(dev).clone()
     gemm_h(lib, dev, dt, 7, Ad, Wd, hd, M, N, K, bias=bd, resid=hd)
     err = (hd.cpu().double() - ref).abs() / (ref.abs() + 1e-2)
-    assert err.max().item() < 1.01 * ULP[2] + 1e-4, err.max().item()      # ULP[2]: one fp16 rounding (+ fp32 accumulation noise)
+    assert err.max().item() < ONE_ROUNDING * ULP[2] + NORM_SLACK, err.max().item()      # ULP[2]: one fp16 rounding (+ fp32 accumulation noise)
     # the stream SATURATES instead of overflowing to inf (round 4): residual rows near the fp16 maximum plus a positive
     # product stay at +-65504 (and finite values below it are untouched, as the comparison above shows)
     big = torch.full((M, N), 65000.0).to(torch.float16); big[::2] = -65000.0
@@ -379,9 +386,9 @@ def _check_gemm_h16_splitk_of_the_residual_gemm(lib, dev, dt, epi, M, N, K, spli
     assert rc == 0
     if epi == 7:
         err = (out.double() - ref).abs() / (ref.abs() + 1e-2)
-        assert err.max().item() < 1.01 * ULP[2] + 1e-4, err.max().item()     # one fp16 rounding (+ fp32 accumulation noise)
+        assert err.max().item() < ONE_ROUNDING * ULP[2] + NORM_SLACK, err.max().item()     # one fp16 rounding (+ fp32 accumulation noise)
     else:
-        assert (out.double() - ref).abs().max().item() < 2e-5               # fp32 accumulation of K exact products
+        assert (out.double() - ref).abs().max().item() < F32_OUT_BOUND               # fp32 accumulation of K exact products
     rc2, out2 = run()
     assert rc2 == 0 and torch.equal(out.view(bits), out2.view(bits))
     try:
@@ -465,7 +472,7 @@ def test_attention_h16_ragged_segments(lib, dev, dt, H, bounded):
     err = (out.double() - ref).abs().max().item()
     # P is rounded to the operand type before P*V (1 ulp relative per probability, signs of v random) and the output is
     # rounded once more: a few ulps of max|v| ~ 4
-    assert err < 8 * ULP[dt], err
+    assert err < ATTN_ULPS * ULP[dt], err
     print(f"attention dt={dt} H={H}: max abs err vs fp64 {err:.2e}")
 
 
@@ -550,14 +557,14 @@ def _check_layernorm_h16(lib, dev, dt, d):
     xn = F.layer_norm(x.double(), (d,), eps=1e-5)
     ref = xn * (1 + mod[token_row.long(), j, :d].double()) + mod[token_row.long(), j, d:].double()
     err = (out.cpu().double() - ref).abs() / (ref.abs() + 1e-2)
-    assert err.max().item() < 1.01 * ULP[dt] + 1e-4, err.max().item()
+    assert err.max().item() < ONE_ROUNDING * ULP[dt] + NORM_SLACK, err.max().item()
     gain, shift = torch.randn(d, generator=g), torch.randn(d, generator=g)
     gd, sd = gain.to(dev), shift.to(dev)
     rc = lib.rap_layernorm_affine_h16(dt, _lib.ptr(xd), _lib.ptr(out), TP, d, _lib.ptr(gd), _lib.ptr(sd), stream(dev))
     _lib.check(rc, "ln_affine_h16"); torch.cuda.synchronize()
     ref = xn * gain.double() + shift.double()
     err = (out.cpu().double() - ref).abs() / (ref.abs() + 1e-2)
-    assert err.max().item() < 1.01 * ULP[dt] + 1e-4, err.max().item()
+    assert err.max().item() < ONE_ROUNDING * ULP[dt] + NORM_SLACK, err.max().item()
 
 
 @pytest.mark.parametrize("dt", [1, 2])
@@ -583,7 +590,7 @@ def _check_qknorm_h16(lib, dev, dt, H):
     x = qk.double()
     ref = x / x.norm(dim=-1, keepdim=True).clamp_min(1e-12) * torch.stack([gq, gk])[:, :, None, :].double() * 8.0
     err = (buf.cpu().double() - ref).abs() / (ref.abs() + 1e-2)
-    assert err.max().item() < 1.01 * ULP[dt] + 1e-4, err.max().item()
+    assert err.max().item() < ONE_ROUNDING * ULP[dt] + NORM_SLACK, err.max().item()
 
 
 # ---------------------------------------------------------------------------------------------
