@@ -30,7 +30,8 @@ extern "C" {
  * round 5, version 5: compute dtype 3 (split precision) and the rap_x2_* entry points are new, nothing was removed or re-numbered;
  * round 6, version 6: additive -- the *_latent entry points (in_dim > 0), rap_transform_errors, tuning keys 18 / 19 / 20; the scratch of the
  * kernel-level attention entry points grew by a sanitised copy of cu_seqlens (rap_attention_workspace_bytes reports it)).  Still version
- * 6, additive: rap_pair_metrics_workspace_bytes, rap_pair_metrics and rap_transform_errors_direct (the evaluator's metrics table). */
+ * 6, additive: rap_pair_metrics_workspace_bytes, rap_pair_metrics and rap_transform_errors_direct (the evaluator's metrics table);
+ * rap_icp_workspace_bytes and rap_icp (batched ICP). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -261,6 +262,29 @@ int rap_pair_metrics(const float* pointclouds_gt, const float* cloud, const int6
 int rap_transform_errors_direct(const float* R_gt, const float* t_gt, const float* R_pred, const float* t_pred,
                                 const int64_t* points_per_part, const int64_t* matched_part_ids, const float* scale, int32_t B, int32_t P,
                                 float* rot_err_per_part, float* trans_err_per_part, float* rot_err_mean, float* trans_err_mean, void* stream);
+
+/* Batched point-to-point ICP: K independent problems in one call, with the semantics of pytorch3d's iterative_closest_point (which the
+ * reference calls one problem at a time: eval/metrics.py:79 in align_anchor, :261 in compute_transform_errors).  Problem k aligns
+ * X[xs : xs + xn] to Y[ys : ys + yn] with (xs, xn) = x_seg[k], (ys, yn) = y_seg[k]; the tables are (K,2) int32, rows need not be contiguous
+ * or ordered, lengths <= 0 are empty, and every row is clamped to its array on the device.  The x segments of one call must not overlap
+ * (the work list holds n_x_points / 256 + K + 1 items; a problem that no longer fits is treated as an empty one).  Row-vector convention
+ * Xt = X R + T, det R = +1.  Per problem, from R, T = init_R[k], init_T[k] (identity / zero where the pointer is NULL):
+ *   for it in 0 .. max_iterations-1:
+ *     nn(i) = first arg-min_j |Xt_i - Y_j|^2 (fp32 direct differences);  S = all i, or the i with sqrtf(d2_i) <= max_correspondence_distance;
+ *     R, T = Kabsch fit of the ORIGINAL X[S] onto Y[nn(S)];  Xt = X R + T;  rmse = sqrt(mean_S |Xt_i - Y_nn(i)|^2);
+ *     rel = 1 in the first iteration, else (prev - rmse) / prev;  iterations = it + 1;  rel <= relative_rmse_thr: converged = 1, stop.
+ * Every problem stops on its own.  prev == 0 counts as converged.  An empty S stops the problem with the R, T and the iteration count it
+ * had, rmse = inf and converged = 0.  xn == 0 or yn == 0: R, T = init or identity, rmse = NaN, iterations = 0, converged = 0.  Fewer than
+ * three points give a finite proper rotation (the fit is not unique).  max_correspondence_distance <= 0: no gate; relative_rmse_thr =
+ * -inf: no early stop.  Outputs: R (K,3,3), T (K,3), rmse (K,) fp32, iterations (K,) int32, converged (K,) uint8, and Xt (n_x_points,3) or
+ * NULL: the points of every problem's x segment moved by its result (rows outside every segment are not written).
+ * 1 + 2 * max_iterations (+ 1) launches enqueued up front; the convergence test never leaves the device, so there is no host read, no
+ * allocation, and the call can be captured into a graph.  Deterministic (no floating-point atomics); a problem's bits do not depend on the
+ * rest of the batch.  ws >= rap_icp_workspace_bytes(n_x_points, K) (0 for non-positive arguments). */
+size_t rap_icp_workspace_bytes(int64_t n_x_points, int32_t K);
+int rap_icp(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t n_x_points, int64_t n_y_points,
+            const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr, float max_correspondence_distance,
+            float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- MiniSpinNet local feature extractor (the step before the path) ----
  * Replaces MiniSpinNet.forward (reference dataset_process/utils/spinnet/patch_embedder.py:49-183 with patchnet.py:16-84 and

@@ -557,6 +557,38 @@ extern "C" int rap_transform_errors_direct(const float* R_gt, const float* t_gt,
                                         rot_err_per_part, trans_err_per_part, rot_err_mean, trans_err_mean);
 }
 
+// batched point-to-point ICP: see icp.hip
+struct IcpWs { NnWork* items; void* partials; void* ranges; double* prev; int32_t* done; size_t total; };
+static IcpWs carve_icp(int64_t n, int K, char* basep) {
+  IcpWs w; Carver c(basep);
+  const size_t max_items = nn_max_items((long)n, K);
+  w.items = (NnWork*)c.take(max_items * sizeof(NnWork));
+  w.partials = c.take(max_items * icp_partial_bytes());
+  w.ranges = c.take((size_t)K * 16);
+  w.prev = (double*)c.take((size_t)K * 8);
+  w.done = (int32_t*)c.take((size_t)K * 4);
+  w.total = c.total();
+  return w;
+}
+extern "C" size_t rap_icp_workspace_bytes(int64_t n_x_points, int32_t K) {
+  return (n_x_points <= 0 || K <= 0) ? 0 : carve_icp(n_x_points, K, nullptr).total;
+}
+extern "C" int rap_icp(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t NX, int64_t NY,
+                       const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
+                       float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt,
+                       void* ws, size_t ws_bytes, void* stream) {
+  if (!X || !x_seg || !Y || !y_seg || !R || !T || !rmse || !iterations || !converged || K <= 0 || max_iterations <= 0 || NX <= 0 || NY <= 0 ||
+      NX > 0x7fffffffLL / 8 || NY > 0x7fffffffLL / 8 || relative_rmse_thr != relative_rmse_thr ||
+      max_correspondence_distance != max_correspondence_distance)
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  IcpWs w = carve_icp(NX, K, (char*)ws);
+  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_icp((hipStream_t)stream, X, x_seg, Y, y_seg, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
+                    max_correspondence_distance > 0.f ? max_correspondence_distance : 0.f, R, T, rmse, iterations, converged, Xt, w.items,
+                    w.partials, w.ranges, w.prev, w.done);
+}
+
 extern "C" int rap_farthest_point_sampling(const float* points, const int32_t* cloud_start, const int32_t* cloud_len,
                                            const int32_t* k_per_cloud, const int32_t* start_idx, int32_t n_clouds, int32_t k_max,
                                            int32_t* indices_out, float* dist_ws, void* stream) {

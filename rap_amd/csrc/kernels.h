@@ -256,6 +256,14 @@ int launch_transform_errors_direct(hipStream_t stream, const float* R_gt, const 
                                    const int64_t* ppp, const int64_t* matched, const float* scale, int B, int P, float* rot_pp,
                                    float* trans_pp, float* rot_mean, float* trans_mean);
 
+// batched point-to-point ICP (icp.hip; pytorch3d's iterative_closest_point as reference eval/metrics.py:79, 261 call it).  items:
+// nn_max_items(NX, K) NnWork; partials: icp_partial_bytes() per item; ranges: 16 bytes, prev: 8 bytes, done: 4 bytes per problem
+size_t icp_partial_bytes();
+int launch_icp(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX, long NY,
+               const float* init_R, const float* init_T, int max_iterations, float relative_rmse_thr, float gate, float* R, float* T,
+               float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, NnWork* items, void* partials, void* ranges, double* prev,
+               int32_t* done);
+
 // farthest point sampling (fps.hip; reference dataset_process/utils/point_sampling_utils.py:263-305)
 int launch_fps(hipStream_t stream, const float* pts, const int32_t* cloud_start, const int32_t* cloud_len, const int32_t* Ks,
                const int32_t* starts, int C, int Kmax,
