@@ -31,7 +31,8 @@ extern "C" {
  * round 6, version 6: additive -- the *_latent entry points (in_dim > 0), rap_transform_errors, tuning keys 18 / 19 / 20; the scratch of the
  * kernel-level attention entry points grew by a sanitised copy of cu_seqlens (rap_attention_workspace_bytes reports it)).  Still version
  * 6, additive: rap_pair_metrics_workspace_bytes, rap_pair_metrics and rap_transform_errors_direct (the evaluator's metrics table);
- * rap_icp_workspace_bytes and rap_icp (batched ICP). */
+ * rap_icp_workspace_bytes and rap_icp (batched ICP); rap_icp_grid_workspace_bytes, rap_icp_grid, rap_nn_grid_workspace_bytes and
+ * rap_nearest_neighbors (the same search over a uniform-grid index). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -285,6 +286,34 @@ size_t rap_icp_workspace_bytes(int64_t n_x_points, int32_t K);
 int rap_icp(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t n_x_points, int64_t n_y_points,
             const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr, float max_correspondence_distance,
             float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, void* ws, size_t ws_bytes, void* stream);
+
+/* rap_icp on a uniform-grid neighbour index: the argument list, the semantics and the RESULTS of rap_icp, bit for bit -- the grid is an
+ * accelerator, not an approximation (same fp32 distance, same "first arg-min" winner, same sums in the same order).  The index over
+ * the y segments of all K problems is built once per call, on the device (nine launches after the set-up), and queried in every
+ * iteration: a query looks at the few dozen rows in the cells around it instead of at every row of its y segment.  Problems whose y
+ * segments are the same rows share one grid.  y segments that overlap without being equal can ask for more than n_y_points indexed
+ * rows; a problem that no longer fits is searched row by row (exact, and as slow as that sounds).  Rows of Y with a non-finite coordinate
+ * can never be a neighbour, here as in rap_icp.  K <= 65535.  No host read, no allocation, no floating-point atomics (integer atomics
+ * build the index; no result depends on their order); can be captured into a graph.
+ * ws >= rap_icp_grid_workspace_bytes(n_x_points, n_y_points, K): host arithmetic, 0 for non-positive arguments, never less than
+ * rap_icp_workspace_bytes(n_x_points, K); about 28 bytes per row of Y on top of it. */
+size_t rap_icp_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K);
+int rap_icp_grid(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t n_x_points,
+                 int64_t n_y_points, const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
+                 float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt,
+                 void* ws, size_t ws_bytes, void* stream);
+/* The index on its own: exact nearest neighbours of K problems.  For every row i of problem k's x segment, idx_out[i] = the row of Y
+ * (an index into Y, not into the segment) within k's y segment that is nearest to x_i R[k] + T[k] (x_i itself where R and T are NULL;
+ * both or neither; R (K,3,3), T (K,3), row vectors), the first such row among equals, and d2_out[i] = that squared distance (fp32,
+ * direct differences).  idx_out[i] = -1 and d2_out[i] = inf where no row lies within max_distance (sqrtf(d2) <= max_distance;
+ * max_distance <= 0: no limit), where the y segment is empty, and where x_i has a non-finite coordinate.  idx_out, d2_out are
+ * (n_x_points,); rows of X outside every segment are not written.  Segment tables, their clamping, the x segments that must not
+ * overlap, K <= 65535 and the execution properties: as rap_icp_grid.  ws >= rap_nn_grid_workspace_bytes(n_x_points, n_y_points, K)
+ * (host arithmetic; 0 for non-positive arguments). */
+size_t rap_nn_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K);
+int rap_nearest_neighbors(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t n_x_points,
+                          int64_t n_y_points, const float* R, const float* T, float max_distance, int32_t* idx_out, float* d2_out, void* ws,
+                          size_t ws_bytes, void* stream);
 
 /* ---- MiniSpinNet local feature extractor (the step before the path) ----
  * Replaces MiniSpinNet.forward (reference dataset_process/utils/spinnet/patch_embedder.py:49-183 with patchnet.py:16-84 and

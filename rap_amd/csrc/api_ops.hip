@@ -589,6 +589,53 @@ extern "C" int rap_icp(const float* X, const int32_t* x_seg, const float* Y, con
                     w.partials, w.ranges, w.prev, w.done);
 }
 
+// the same on a uniform-grid neighbour index, and the index as an entry point of its own: see nn_grid.hip
+#define RAP_GRID_MAX_K 65535      // the build kernels take the problem from blockIdx.y
+extern "C" size_t rap_icp_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
+  if (n_x_points <= 0 || n_y_points <= 0 || K <= 0) return 0;
+  Carver c(nullptr);
+  nn_grid_carve(c, (long)n_y_points, K);
+  return carve_icp(n_x_points, K, nullptr).total + c.total();
+}
+extern "C" int rap_icp_grid(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t NX, int64_t NY,
+                            const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
+                            float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged,
+                            float* Xt, void* ws, size_t ws_bytes, void* stream) {
+  if (!X || !x_seg || !Y || !y_seg || !R || !T || !rmse || !iterations || !converged || K <= 0 || K > RAP_GRID_MAX_K || max_iterations <= 0 ||
+      NX <= 0 || NY <= 0 || NX > 0x7fffffffLL / 8 || NY > 0x7fffffffLL / 8 || relative_rmse_thr != relative_rmse_thr ||
+      max_correspondence_distance != max_correspondence_distance)
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  IcpWs w = carve_icp(NX, K, (char*)ws);
+  Carver c((char*)ws + w.total);
+  const NnGridWs g = nn_grid_carve(c, (long)NY, K);
+  if (w.total + c.total() > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_icp_grid((hipStream_t)stream, X, x_seg, Y, y_seg, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
+                         max_correspondence_distance > 0.f ? max_correspondence_distance : 0.f, R, T, rmse, iterations, converged, Xt, w.items,
+                         w.partials, w.ranges, w.prev, w.done, g);
+}
+extern "C" size_t rap_nn_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
+  if (n_x_points <= 0 || n_y_points <= 0 || K <= 0) return 0;
+  Carver c(nullptr);
+  c.take(nn_max_items((long)n_x_points, K) * sizeof(NnWork));
+  nn_grid_carve(c, (long)n_y_points, K);
+  return c.total();
+}
+extern "C" int rap_nearest_neighbors(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t NX,
+                                     int64_t NY, const float* R, const float* T, float max_distance, int32_t* idx_out, float* d2_out, void* ws,
+                                     size_t ws_bytes, void* stream) {
+  if (!X || !x_seg || !Y || !y_seg || !idx_out || !d2_out || K <= 0 || K > RAP_GRID_MAX_K || NX <= 0 || NY <= 0 || NX > 0x7fffffffLL / 8 ||
+      NY > 0x7fffffffLL / 8 || max_distance != max_distance || (R == nullptr) != (T == nullptr))
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  Carver c(ws);
+  NnWork* items = (NnWork*)c.take(nn_max_items((long)NX, K) * sizeof(NnWork));
+  const NnGridWs g = nn_grid_carve(c, (long)NY, K);
+  if (c.total() > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_nearest_neighbors((hipStream_t)stream, X, x_seg, Y, y_seg, K, (long)NX, (long)NY, R, T, max_distance > 0.f ? max_distance : 0.f,
+                                  idx_out, d2_out, items, g);
+}
+
 extern "C" int rap_farthest_point_sampling(const float* points, const int32_t* cloud_start, const int32_t* cloud_len,
                                            const int32_t* k_per_cloud, const int32_t* start_idx, int32_t n_clouds, int32_t k_max,
                                            int32_t* indices_out, float* dist_ws, void* stream) {

@@ -15,24 +15,10 @@
 // The convergence decision stays on the device: blocks and waves of a problem whose done flag is set return at once, so the host never
 // reads anything back and the whole call can be captured into a graph.  Nothing N x M and no per-point index or distance reaches HBM.
 // Deterministic (no floating-point atomics) and batch-independent: a problem's arithmetic depends on its own segments only.
-#include "kernels.h"
+#include "icp.h"
 #include "kabsch.h"
 
-#define ICP_TILE 256
-#define ICP_NMOM 17      // sum x (3), sum y (3), sum x_i y_j (9), sum |x|^2, sum |y|^2
-
-struct IcpPartial { double m[ICP_NMOM]; long long count; };
-struct IcpRange { int first, count, x_len, y_len; };
-
 size_t icp_partial_bytes() { return sizeof(IcpPartial); }
-
-// (start, len) of row k clamped to [0, limit): an inconsistent table cannot make a kernel index outside the array
-__device__ __forceinline__ void icp_segment(const int32_t* __restrict__ seg, int k, long limit, int& start, int& len) {
-  long s = seg[(size_t)k * 2], n = seg[(size_t)k * 2 + 1];
-  s = s < 0 ? 0 : s > limit ? limit : s;
-  n = n < 0 ? 0 : n > limit - s ? limit - s : n;
-  start = (int)s; len = (int)n;
-}
 
 __global__ __launch_bounds__(ICP_TILE) void icp_setup_kernel(const int32_t* __restrict__ x_seg, const int32_t* __restrict__ y_seg, int K, long NX,
                                                              long NY, const float* __restrict__ init_R, const float* __restrict__ init_T,
@@ -73,14 +59,6 @@ __global__ __launch_bounds__(ICP_TILE) void icp_setup_kernel(const int32_t* __re
   }
 }
 
-// p R + T in fp32, row vectors (pytorch3d's _apply_similarity_transform with s = 1)
-__device__ __forceinline__ void icp_apply(const float* __restrict__ R, const float* __restrict__ T, float x, float y, float z, float& ox, float& oy,
-                                          float& oz) {
-  ox = x * R[0] + y * R[3] + z * R[6] + T[0];
-  oy = x * R[1] + y * R[4] + z * R[7] + T[1];
-  oz = x * R[2] + y * R[5] + z * R[8] + T[2];
-}
-
 __global__ __launch_bounds__(ICP_TILE) void icp_query_kernel(const float* __restrict__ X, const float* __restrict__ Y,
                                                              const NnWork* __restrict__ items, const float* __restrict__ R,
                                                              const float* __restrict__ T, const int32_t* __restrict__ done, float gate,
@@ -114,42 +92,11 @@ __global__ __launch_bounds__(ICP_TILE) void icp_query_kernel(const float* __rest
 #pragma unroll 8
     for (int j = 0; j < nk; ++j) {
       const float4 p = tile[j];
-      const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-      const float d2 = dx * dx + dy * dy + dz * dz;
+      const float d2 = nn_d2(qx, qy, qz, p.x, p.y, p.z);
       if (d2 < best) { best = d2; besti = k0 + j; }      // strict <: the first minimum wins, as nn_query_kernel
     }
   }
-  double m[ICP_NMOM];
-#pragma unroll
-  for (int i = 0; i < ICP_NMOM; ++i) m[i] = 0.0;
-  int n = 0;
-  if (active && besti >= 0 && (!(gate > 0.f) || sqrtf(best) <= gate)) {
-    const size_t ti = (size_t)w.y_start + besti;
-    const double xs[3] = {(double)x0, (double)x1, (double)x2};
-    const double ys[3] = {(double)Y[ti * 3 + 0], (double)Y[ti * 3 + 1], (double)Y[ti * 3 + 2]};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      m[i] = xs[i]; m[3 + i] = ys[i];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) m[6 + 3 * i + j] = xs[i] * ys[j];
-    }
-    m[15] = xs[0] * xs[0] + xs[1] * xs[1] + xs[2] * xs[2];
-    m[16] = ys[0] * ys[0] + ys[1] * ys[1] + ys[2] * ys[2];
-    n = 1;
-  }
-#pragma unroll
-  for (int i = 0; i < ICP_NMOM; ++i) m[i] = wave_sum_d(m[i]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < ICP_NMOM; ++i) red_m[threadIdx.x >> 6][i] = m[i];
-    red_n[threadIdx.x >> 6] = n;
-  }
-  __syncthreads();
-  IcpPartial* out = partials + blockIdx.x;
-  if (threadIdx.x < ICP_NMOM) out->m[threadIdx.x] = (red_m[0][threadIdx.x] + red_m[1][threadIdx.x]) + (red_m[2][threadIdx.x] + red_m[3][threadIdx.x]);
-  if (threadIdx.x == ICP_NMOM) out->count = (long long)(red_n[0] + red_n[1] + red_n[2] + red_n[3]);
+  icp_moments(active, besti, best, gate, x0, x1, x2, Y, w.y_start, red_m, red_n, partials + blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void icp_finish_kernel(const IcpPartial* __restrict__ partials, const IcpRange* __restrict__ ranges, int it,
@@ -239,5 +186,28 @@ int launch_icp(hipStream_t stream, const float* X, const int32_t* x_seg, const f
     hipLaunchKernelGGL(icp_apply_kernel, dim3(max_items), dim3(ICP_TILE), 0, stream, X, items, R, T, Xt);
     RAP_LAUNCH_CHECK();
   }
+  return RAP_OK;
+}
+
+// the pieces of launch_icp that a second search path (nn_grid.hip) enqueues around its own query kernel: a kernel is launched from the
+// file that defines it
+int launch_icp_setup(hipStream_t stream, const int32_t* x_seg, const int32_t* y_seg, int K, long NX, long NY, const float* init_R,
+                     const float* init_T, NnWork* items, void* ranges, float* R, float* T, float* rmse, int32_t* iterations,
+                     uint8_t* converged, double* prev, int32_t* done) {
+  hipLaunchKernelGGL(icp_setup_kernel, dim3(1), dim3(ICP_TILE), 0, stream, x_seg, y_seg, K, NX, NY, init_R, init_T, items, (IcpRange*)ranges,
+                     (int)nn_max_items(NX, K), R, T, rmse, iterations, converged, prev, done);
+  RAP_LAUNCH_CHECK();
+  return RAP_OK;
+}
+int launch_icp_finish(hipStream_t stream, const void* partials, const void* ranges, int K, int it, float relative_rmse_thr, float* R, float* T,
+                      float* rmse, int32_t* iterations, uint8_t* converged, double* prev, int32_t* done) {
+  hipLaunchKernelGGL(icp_finish_kernel, dim3(K), dim3(64), 0, stream, (const IcpPartial*)partials, (const IcpRange*)ranges, it,
+                     (double)relative_rmse_thr, R, T, rmse, iterations, converged, prev, done);
+  RAP_LAUNCH_CHECK();
+  return RAP_OK;
+}
+int launch_icp_apply(hipStream_t stream, const float* X, const NnWork* items, int max_items, const float* R, const float* T, float* Xt) {
+  hipLaunchKernelGGL(icp_apply_kernel, dim3(max_items), dim3(ICP_TILE), 0, stream, X, items, R, T, Xt);
+  RAP_LAUNCH_CHECK();
   return RAP_OK;
 }

@@ -264,6 +264,35 @@ int launch_icp(hipStream_t stream, const float* X, const int32_t* x_seg, const f
                float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, NnWork* items, void* partials, void* ranges, double* prev,
                int32_t* done);
 
+int launch_icp_setup(hipStream_t stream, const int32_t* x_seg, const int32_t* y_seg, int K, long NX, long NY, const float* init_R,
+                     const float* init_T, NnWork* items, void* ranges, float* R, float* T, float* rmse, int32_t* iterations,
+                     uint8_t* converged, double* prev, int32_t* done);
+int launch_icp_finish(hipStream_t stream, const void* partials, const void* ranges, int K, int it, float relative_rmse_thr, float* R, float* T,
+                      float* rmse, int32_t* iterations, uint8_t* converged, double* prev, int32_t* done);
+int launch_icp_apply(hipStream_t stream, const float* X, const NnWork* items, int max_items, const float* R, const float* T, float* Xt);
+
+// exact nearest neighbours over a uniform grid (nn_grid.hip): one index over the y segments of all K problems, built on the device, then
+// queried by ICP (launch_icp_grid: launch_icp's arguments and results, bit for bit) or on its own (launch_nearest_neighbors).  The
+// scratch of the index is carved by nn_grid_carve (host arithmetic in NY and K only; a null base gives the size).
+struct NnGridWs {
+  void* grids;            // K NnGrid
+  unsigned* box;          // K x 8: the bounding box of every problem's y segment as ordered integers
+  unsigned* cell_start;   // NY + 8 K + 1: counts, then their exclusive scan (first sorted row of every cell; the last entry is the total)
+  unsigned* cursor;       // NY + 8 K + 1: the fill level of every cell during the scatter
+  int32_t* row_cell;      // NY: the cell of every row that went into a grid (-1: a row with a non-finite coordinate)
+  void* sorted;           // NY float4: x, y, z and the row's index in its segment, cell by cell
+  unsigned* block_sum;    // one per 2048 cells
+  size_t n_cells;         // NY + 8 K + 1
+};
+NnGridWs nn_grid_carve(Carver& c, long NY, int K);
+int launch_icp_grid(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX, long NY,
+                    const float* init_R, const float* init_T, int max_iterations, float relative_rmse_thr, float gate, float* R, float* T,
+                    float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, NnWork* items, void* partials, void* ranges, double* prev,
+                    int32_t* done, const NnGridWs& g);
+int launch_nearest_neighbors(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX,
+                             long NY, const float* R, const float* T, float gate, int32_t* idx_out, float* d2_out, NnWork* items,
+                             const NnGridWs& g);
+
 // farthest point sampling (fps.hip; reference dataset_process/utils/point_sampling_utils.py:263-305)
 int launch_fps(hipStream_t stream, const float* pts, const int32_t* cloud_start, const int32_t* cloud_len, const int32_t* Ks,
                const int32_t* starts, int C, int Kmax,

@@ -5,7 +5,7 @@
 // One kernel does the N^2 work for both: nn_query_kernel -- a block owns 256 query points (one per lane, in registers) and streams
 // the candidate set through LDS in tiles of 256 float4 (one ds_read_b128 per candidate, broadcast to the wave); direct-difference
 // fp32 squared distances, running minimum and FIRST arg-minimum (torch.min tie rule); nothing N^2 ever reaches HBM.
-#include "kernels.h"
+#include "icp.h"
 
 #define NN_TILE 256
 
@@ -46,8 +46,7 @@ __global__ __launch_bounds__(NN_TILE) void nn_query_kernel(const float* __restri
 #pragma unroll 8
     for (int j = 0; j < nk; ++j) {
       const float4 p = tile[j];
-      const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-      const float d2 = dx * dx + dy * dy + dz * dz;
+      const float d2 = nn_d2(qx, qy, qz, p.x, p.y, p.z);
       if (d2 < best) { best = d2; besti = k0 + j; }      // strict <: the first minimum wins, as torch.min
     }
   }

@@ -22,13 +22,23 @@ ICPSolution.__doc__ = """Result of an ICP call, every field a device tensor: con
 layout X was given in), R (K,3,3) and T (K,3) with ``Xt = X @ R + T`` (row vectors, det R = +1), iterations (K,) int32."""
 
 
+SEARCHES = ("brute", "grid")
+
+
+def _check_search(search):
+    if search not in SEARCHES:
+        raise ValueError(f"search must be one of {SEARCHES}, got {search!r}")
+
+
 def icp_packed(X, x_seg, Y, y_seg, init_R=None, init_T=None, max_iterations: int = 100, relative_rmse_thr: float = 1e-6,
-               max_correspondence_distance: float | None = None, return_Xt: bool = True) -> ICPSolution:
+               max_correspondence_distance: float | None = None, return_Xt: bool = True, search: str = "brute") -> ICPSolution:
     """K problems on packed clouds: problem k aligns ``X[xs:xs+xn]`` to ``Y[ys:ys+yn]`` with ``(xs, xn) = x_seg[k]``,
     ``(ys, yn) = y_seg[k]``.  X (NX,3), Y (NY,3) fp32; x_seg, y_seg (K,2) int32 device tensors whose rows need not be contiguous or
     ordered (the x segments must not overlap); init_R (K,3,3) / init_T (K,3) or None.  Semantics, stopping rules and the treatment of
     empty problems: ``rap_icp`` in include/rapflow.h.  No host synchronisation; ``Xt`` (NX,3) starts as a copy of X, so rows outside
-    every segment pass through unchanged."""
+    every segment pass through unchanged.  ``search``: ``"brute"`` (every x against every y, ``rap_icp``) or ``"grid"`` (a uniform-grid
+    index over Y built once per call, ``rap_icp_grid``); both give the same bits."""
+    _check_search(search)
     _require_cuda(X, "X")
     _require_cuda(Y, "Y")
     device = X.device
@@ -61,13 +71,55 @@ def icp_packed(X, x_seg, Y, y_seg, init_R=None, init_T=None, max_iterations: int
     if max_correspondence_distance is not None and not gate > 0.0:
         raise ValueError("max_correspondence_distance must be positive (None: no gate)")
     lib = _lib.load()
-    ws = workspace(device, lib.rap_icp_workspace_bytes(NX, K))
+    grid = search == "grid"
+    fn, name = (lib.rap_icp_grid, "rap_icp_grid") if grid else (lib.rap_icp, "rap_icp")
+    ws = workspace(device, lib.rap_icp_grid_workspace_bytes(NX, NY, K) if grid else lib.rap_icp_workspace_bytes(NX, K))
     with torch.cuda.device(device):
-        rc = lib.rap_icp(_lib.ptr(X), _lib.ptr(xs), _lib.ptr(Y), _lib.ptr(ys), K, NX, NY, _lib.ptr(iR), _lib.ptr(iT), int(max_iterations),
-                         float(relative_rmse_thr), gate, _lib.ptr(R), _lib.ptr(T), _lib.ptr(rmse), _lib.ptr(iters), _lib.ptr(conv),
-                         _lib.ptr(Xt), _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
-    _lib.check(rc, "rap_icp")
+        rc = fn(_lib.ptr(X), _lib.ptr(xs), _lib.ptr(Y), _lib.ptr(ys), K, NX, NY, _lib.ptr(iR), _lib.ptr(iT), int(max_iterations),
+                float(relative_rmse_thr), gate, _lib.ptr(R), _lib.ptr(T), _lib.ptr(rmse), _lib.ptr(iters), _lib.ptr(conv),
+                _lib.ptr(Xt), _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
+    _lib.check(rc, name)
     return ICPSolution(conv.bool(), rmse, empty_X if Xt is None else Xt, R, T, iters)
+
+
+def nearest_neighbors_packed(X, x_seg, Y, y_seg, R=None, T=None, max_distance: float | None = None):
+    """Exact nearest neighbours of K problems on packed clouds, through the uniform-grid index of ``rap_nearest_neighbors``: for every
+    row i of ``X[xs:xs+xn]`` (moved by ``x @ R[k] + T[k]`` where R (K,3,3) and T (K,3) are given) the row of Y, within
+    ``Y[ys:ys+yn]``, that is nearest to it -- the first one among equals, as a brute-force arg-min.  -> (idx (NX,) int32: the row in Y,
+    d2 (NX,) fp32: the squared distance); -1 and inf where there is no neighbour within ``max_distance`` (None: no limit), where the
+    y segment is empty, and for rows of X outside every segment.  No host synchronisation."""
+    _require_cuda(X, "X")
+    _require_cuda(Y, "Y")
+    device = X.device
+    X, Y = _f32c(X.reshape(-1, 3)), _f32c(Y.to(device).reshape(-1, 3))
+    xs = x_seg.to(device=device, dtype=torch.int32).reshape(-1, 2).contiguous()
+    ys = y_seg.to(device=device, dtype=torch.int32).reshape(-1, 2).contiguous()
+    K = xs.shape[0]
+    if K == 0 or ys.shape[0] != K:
+        raise ValueError(f"x_seg and y_seg must hold the same positive number of (start, len) rows, got {xs.shape[0]} and {ys.shape[0]}")
+    if (R is None) != (T is None):
+        raise ValueError("R and T must be given together")
+    gate = 0.0 if max_distance is None else float(max_distance)
+    if max_distance is not None and not gate > 0.0:
+        raise ValueError("max_distance must be positive (None: no limit)")
+    NX = X.shape[0]
+    idx = torch.full((NX,), -1, dtype=torch.int32, device=device)
+    d2 = torch.full((NX,), float("inf"), dtype=torch.float32, device=device)
+    if NX == 0:
+        return idx, d2
+    if Y.shape[0] == 0:                                                  # the C ABI wants non-empty arrays; every segment clamps to nothing
+        Y = torch.zeros((1, 3), dtype=torch.float32, device=device)
+        ys = torch.zeros_like(ys)
+    NY = Y.shape[0]
+    Rk = None if R is None else _f32c(R.to(device).reshape(K, 3, 3))
+    Tk = None if T is None else _f32c(T.to(device).reshape(K, 3))
+    lib = _lib.load()
+    ws = workspace(device, lib.rap_nn_grid_workspace_bytes(NX, NY, K))
+    with torch.cuda.device(device):
+        rc = lib.rap_nearest_neighbors(_lib.ptr(X), _lib.ptr(xs), _lib.ptr(Y), _lib.ptr(ys), K, NX, NY, _lib.ptr(Rk), _lib.ptr(Tk), gate,
+                                       _lib.ptr(idx), _lib.ptr(d2), _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
+    _lib.check(rc, "rap_nearest_neighbors")
+    return idx, d2
 
 
 def _lengths(lengths, K, N, device):
@@ -77,13 +129,16 @@ def _lengths(lengths, K, N, device):
 
 
 def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100, relative_rmse_thr: float = 1e-6,
-                            max_correspondence_distance: float | None = None, x_lengths=None, y_lengths=None) -> ICPSolution:
+                            max_correspondence_distance: float | None = None, x_lengths=None, y_lengths=None,
+                            search: str = "brute") -> ICPSolution:
     """Point-to-point ICP of X onto Y: padded batches ``X (K,N,3)``, ``Y (K,M,3)`` with optional ``x_lengths`` / ``y_lengths`` (K,), or
     ``(N,3)`` / ``(M,3)`` for one problem.  ``init_transform = (R, T)`` with R (K,3,3) or (3,3), T (K,3) or (3,) in the row-vector
     convention ``Xt = X @ R + T``.  pytorch3d's algorithm and defaults (rigid, no scale estimate), except that every problem of the batch
     stops on its own and that a problem whose rmse reaches exactly 0 counts as converged.  ``max_correspondence_distance`` keeps only
     the points whose neighbour lies within that distance in each fit.  Returns an ``ICPSolution``; ``Xt`` has X's shape (padding rows
-    unchanged).  One ``rap_icp`` call, no host synchronisation."""
+    unchanged).  One ``rap_icp`` call, no host synchronisation.  ``search="grid"`` finds the same neighbours through a uniform-grid
+    index over Y (``rap_icp_grid``): the same bits, and far less work on large clouds."""
+    _check_search(search)
     _require_cuda(X, "X")
     single = X.dim() == 2
     Xb = X.unsqueeze(0) if single else X
@@ -100,7 +155,7 @@ def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100
         iR, iT = init_transform[0], init_transform[1]
         iR = iR.to(device).reshape(-1, 3, 3).expand(K, 3, 3)
         iT = iT.to(device).reshape(-1, 3).expand(K, 3)
-    sol = icp_packed(Xb, x_seg, Yb, y_seg, iR, iT, max_iterations, relative_rmse_thr, max_correspondence_distance)
+    sol = icp_packed(Xb, x_seg, Yb, y_seg, iR, iT, max_iterations, relative_rmse_thr, max_correspondence_distance, search=search)
     return sol._replace(Xt=sol.Xt.reshape(X.shape))
 
 
@@ -123,7 +178,7 @@ def _part_offsets(pointclouds, points_per_part, cu_seqlens_batch):
     return base[:, None] + ppp.cumsum(dim=1) - ppp, base
 
 
-def align_anchor(pointclouds_gt, pointclouds_pred, points_per_part, anchor_parts, cu_seqlens_batch=None) -> torch.Tensor:
+def align_anchor(pointclouds_gt, pointclouds_pred, points_per_part, anchor_parts, cu_seqlens_batch=None, search: str = "brute") -> torch.Tensor:
     """Reference signature (eval/metrics.py:50-90) plus ``cu_seqlens_batch`` for packed ``(TP,3)`` clouds -> the predicted cloud, every
     sample moved by the ICP alignment of its predicted anchor part (the first non-empty part flagged in ``anchor_parts``) onto the same
     part of the ground truth.  One ``rap_icp`` call for all samples, segment tables from cumulative sums on the device, no host sync.
@@ -134,7 +189,10 @@ def align_anchor(pointclouds_gt, pointclouds_pred, points_per_part, anchor_parts
       * metrics.py:87 -- the reference moves the cloud by ``pred @ R.T + T`` although pytorch3d's solution means ``Xt = X @ R + T``.
         Here the cloud is moved by ICP's own convention, ``pred @ R + T``.
       * metrics.py:72-87 -- a sample without an anchor keeps ``anchor_align_icp`` of the previous sample (a NameError for the first).
-        Here such a sample is returned unchanged."""
+        Here such a sample is returned unchanged.
+
+    ``search``: the neighbour search of the ICP call, ``"brute"`` or ``"grid"`` (``icp_packed``)."""
+    _check_search(search)
     _require_cuda(pointclouds_pred, "pointclouds_pred")
     device = pointclouds_pred.device
     shape = pointclouds_pred.shape
@@ -149,7 +207,7 @@ def align_anchor(pointclouds_gt, pointclouds_pred, points_per_part, anchor_parts
     seg = torch.stack([start, length], dim=1).to(torch.int32)
     pred = _f32c(pointclouds_pred.reshape(-1, 3))
     gt = _f32c(pointclouds_gt.to(device).reshape(-1, 3))
-    sol = icp_packed(pred, seg, gt, seg, return_Xt=False)                  # an empty problem returns the identity: "unchanged"
+    sol = icp_packed(pred, seg, gt, seg, return_Xt=False, search=search)                  # an empty problem returns the identity: "unchanged"
     # every point of sample b moves by (R_b, T_b); rows outside every sample (padding of a (B,N,3) batch) stay
     TPn = pred.shape[0]
     n_b = ppp.sum(dim=1)
@@ -162,14 +220,16 @@ def align_anchor(pointclouds_gt, pointclouds_pred, points_per_part, anchor_parts
 
 def compute_transform_errors_icp(pointclouds, pointclouds_gt, rotations_gt, translations_gt, rotations_pred, translations_pred,
                                  points_per_part, anchor_part, matched_part_ids=None, scale=None, cu_seqlens_batch=None,
-                                 return_per_part: bool = False):
+                                 return_per_part: bool = False, search: str = "brute"):
     """``compute_transform_errors(..., use_icp=True)`` of the reference (eval/metrics.py:165-303, the branch at :257-265), with that
     function's argument list minus ``use_icp`` -> (rot_errors_mean (B,) in degrees, trans_errors_mean (B,)).  For every non-empty
     non-anchor part ICP aligns the ground-truth part onto ``cond @ R_pred^T + t_pred``; the rotation error is the angle of the ICP
     rotation (from its trace), the translation error ``|T| * scale``; means over those parts (NaN for a sample without one, as the
     reference's division).  ``rotations_gt`` / ``translations_gt`` are accepted for signature parity: this branch does not read them.
     ``matched_part_ids`` re-orders the predicted poses (:215-218).  One ``rap_icp`` call plus elementwise torch on the device, no host
-    synchronisation.  ``return_per_part`` (an extension) also returns the (B,P) per-part errors."""
+    synchronisation.  ``return_per_part`` (an extension) also returns the (B,P) per-part errors.  ``search``: the neighbour search of
+    the ICP call, ``"brute"`` or ``"grid"`` (``icp_packed``)."""
+    _check_search(search)
     _require_cuda(pointclouds, "pointclouds")
     device = pointclouds.device
     B, P = points_per_part.shape
@@ -199,7 +259,7 @@ def compute_transform_errors_icp(pointclouds, pointclouds_gt, rotations_gt, tran
     moved = torch.where(inside[:, None], moved, cond)
     valid = (ppp != 0) & ~anchor_part.to(device=device).bool()
     seg = torch.stack([off, torch.where(valid, ppp, torch.zeros_like(ppp))], dim=2).reshape(B * P, 2).to(torch.int32)
-    sol = icp_packed(gt, seg, moved, seg, return_Xt=False)
+    sol = icp_packed(gt, seg, moved, seg, return_Xt=False, search=search)
     R64 = sol.R.to(torch.float64)
     cos = (0.5 * (R64[:, 0, 0] + R64[:, 1, 1] + R64[:, 2, 2] - 1.0)).clamp(-1.0, 1.0)
     rot = torch.rad2deg(torch.acos(cos)).to(torch.float32).reshape(B, P)

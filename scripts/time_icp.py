@@ -4,6 +4,9 @@ same work.  Two workloads: 32 problems of 4096 x 4096 points, and one problem of
 Per call: GPU time (HIP events around the call) after --warmup calls, the median and the 10th / 90th percentile over --calls; and the pair
 distances per second = iterations x sum(nx * ny) / time.  The search kernel this one is built from does 2.1 G pairs in 0.69 ms (DESIGN.md
 section 7, row 4).  Prints one JSON line per workload; --out FILE also writes them.
+
+--search grid times the same calls on the uniform-grid neighbour index (rap_icp_grid: the same results, bit for bit); its
+"pair_distances_per_s" is then the rate a brute-force search would need to keep up, not work that was done.
 """
 from __future__ import annotations
 
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--iterations", type=int, default=30)
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--search", choices=["brute", "grid"], default="brute")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -44,7 +48,7 @@ def main():
     for name in (sorted(WORKLOADS) if a.workload == "all" else [a.workload]):
         K, n = WORKLOADS[name]
         X, Y = make_problems(torch, K, n)
-        call = lambda: rap_amd.iterative_closest_point(X, Y, max_iterations=a.iterations, relative_rmse_thr=float("-inf"))
+        call = lambda: rap_amd.iterative_closest_point(X, Y, max_iterations=a.iterations, relative_rmse_thr=float("-inf"), search=a.search)
         for _ in range(a.warmup):
             sol = call()
         torch.cuda.synchronize()
@@ -60,7 +64,7 @@ def main():
         pct = lambda v, p: sorted(v)[min(len(v) - 1, int(round(p * (len(v) - 1))))]
         med = statistics.median(gpu)
         pairs = a.iterations * K * n * n
-        lines.append(json.dumps({"workload": name, "problems": K, "points": n, "iterations": a.iterations, "calls": len(gpu), "warmup": a.warmup,
+        lines.append(json.dumps({"workload": name, "search": a.search, "problems": K, "points": n, "iterations": a.iterations, "calls": len(gpu), "warmup": a.warmup,
                                  "gpu_ms": {"median": med, "p10": pct(gpu, 0.1), "p90": pct(gpu, 0.9)}, "ms_per_iteration": med / a.iterations,
                                  "pair_distances_per_s": pairs / (med * 1e-3), "mean_rmse": float(sol.rmse.mean())}))
         print(lines[-1], flush=True)
