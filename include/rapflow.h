@@ -32,7 +32,8 @@ extern "C" {
  * kernel-level attention entry points grew by a sanitised copy of cu_seqlens (rap_attention_workspace_bytes reports it)).  Still version
  * 6, additive: rap_pair_metrics_workspace_bytes, rap_pair_metrics and rap_transform_errors_direct (the evaluator's metrics table);
  * rap_icp_workspace_bytes and rap_icp (batched ICP); rap_icp_grid_workspace_bytes, rap_icp_grid, rap_nn_grid_workspace_bytes and
- * rap_nearest_neighbors (the same search over a uniform-grid index). */
+ * rap_nearest_neighbors (the same search over a uniform-grid index); rap_attention_split_workspace_bytes, rap_attention_f32_split and
+ * rap_x2_attention_split (kernel-level access to the split-KV attention of few-token calls). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -404,6 +405,22 @@ int rap_attention_f32(const float* qkv_headmajor, const int32_t* cu_seqlens, int
                       <= 40 (the fp32 kernel then drops the softmax offset: |score| log2 e <= 58); a head whose bound is larger gets
                       NaN outputs */, void* ws,
                       size_t ws_bytes, void* stream);
+/* Kernel-level access to the SPLIT forms of the fp32 and the split-precision attention that few-token rap_sample / rap_dit_forward calls
+ * run (tuning key 5): every work item is cut into `splits` key ranges (1, 2 or 4; anything else: RAP_ERR_INVALID), each range writes its
+ * un-normalised partial output and row sums to the workspace, and one combine pass merges them in a fixed order (deterministic).
+ * splits = 1 is rap_attention_f32 / rap_x2_attention, bit for bit.  Rows outside [cu_seqlens[0], cu_seqlens[nseg]) come out as ZEROS
+ * when splits > 1 (the combine pass covers every row of out).
+ * rap_attention_split_workspace_bytes: rap_attention_workspace_bytes(TP, nseg) plus, for splits > 1, splits x TP x heads x 64 floats of
+ *   partial outputs and splits x TP x heads x 2 floats of (maximum, row sum) -- the split-precision need; the fp32 form uses half of the
+ *   second plane.  0 for heads <= 0, TP < 0, nseg < 0 or a splits value that is none of 1, 2, 4.
+ * rap_attention_f32_split: only the bounded softmax can add partial results: splits > 1 without logit_bound is RAP_ERR_INVALID; a head
+ *   whose bound is above 40 gets NaN outputs, as in rap_attention_f32.
+ * rap_x2_attention_split: n_tokens (0 <= n_tokens <= TP; 0 = TP) is the number of rows the combine pass of splits > 1 writes -- rows
+ *   n_tokens .. TP - 1 of out are not touched (the filler rows of rap_sample's padded buffers); cu_seqlens must not reach beyond it.
+ * A workspace below the query's value is RAP_ERR_WORKSPACE before anything is written. */
+size_t rap_attention_split_workspace_bytes(int64_t TP, int32_t nseg, int32_t heads, int32_t splits);
+int rap_attention_f32_split(const float* qkv_headmajor, const int32_t* cu_seqlens, int32_t nseg, float* out, int64_t TP,
+                            int32_t heads, const float* logit_bound, int32_t splits, void* ws, size_t ws_bytes, void* stream);
 int rap_layernorm_mod(const float* x, float* out, int64_t TP, int32_t d, const float* mod, int64_t mod_stride,
                       const int32_t* token_row, void* stream);
 int rap_layernorm_affine(const float* x, float* out, int64_t TP, int32_t d, const float* gain, const float* shift,
@@ -490,6 +507,10 @@ int rap_x2_gemm(int32_t epilogue, const uint16_t* A, int32_t lda, const uint16_t
                 const float* gamma_k, float q_mul, uint16_t* vt, int32_t vt_nblk, void* stream);
 int rap_x2_attention(const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens, int32_t nseg, uint16_t* out,
                      int64_t TP, int32_t heads, void* ws, size_t ws_bytes, void* stream);
+/* rap_x2_attention over `splits` key ranges per work item: see rap_attention_split_workspace_bytes above. */
+int rap_x2_attention_split(const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens, int32_t nseg,
+                           uint16_t* out, int64_t TP, int64_t n_tokens, int32_t heads, int32_t splits, void* ws, size_t ws_bytes,
+                           void* stream);
 
 /* ---- input side of the boundary: raw multi-part scans -> the packed batch rap_sample consumes ----
  * Replaces, in their evaluation-split form (no augmentation), PointCloudDataset._transform

@@ -108,6 +108,8 @@ SIGNATURES = {
     "rap_build_attention_worklist": (c_int32, [_P, c_int32, c_int32, _P, c_int32, _P, _P]),
     "rap_attention_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_attention_f32": (c_int32, [_P, _P, c_int32, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
+    "rap_attention_split_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32]),
+    "rap_attention_f32_split": (c_int32, [_P, _P, c_int32, _P, c_int64, c_int32, _P, c_int32, _P, c_size_t, _P]),
     "rap_layernorm_mod": (c_int32, [_P, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "rap_layernorm_affine": (c_int32, [_P, _P, c_int64, c_int32, _P, _P, _P]),
     "rap_qknorm": (c_int32, [_P, c_int64, c_int32, _P, _P, _P]),
@@ -131,6 +133,7 @@ SIGNATURES = {
     "rap_x2_gemm": (c_int32, [c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int32, c_float, c_int32,
                               _P, _P, c_float, _P, c_int32, _P]),
     "rap_x2_attention": (c_int32, [_P, _P, c_int32, _P, c_int32, _P, c_int64, c_int32, _P, c_size_t, _P]),
+    "rap_x2_attention_split": (c_int32, [_P, _P, c_int32, _P, c_int32, _P, c_int64, c_int64, c_int32, c_int32, _P, c_size_t, _P]),
     "rap_set_tuning": (c_int32, [c_int32, c_int32]),
     "rap_profile_enable": (c_int32, [c_int32]),
     "rap_profile_reset": (c_int32, []),

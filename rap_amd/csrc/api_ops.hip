@@ -37,13 +37,14 @@ static size_t attn_items_bytes(int64_t TP, int32_t nseg) { return align_up(((siz
 extern "C" size_t rap_attention_workspace_bytes(int64_t TP, int32_t nseg) {
   return attn_items_bytes(TP, nseg) + align_up(((size_t)nseg + 1) * sizeof(int32_t), 256);
 }
-// What the three attention entry points start with, after their own pointer checks: the segment-table and workspace checks (tp_max: the
+// What the attention entry points start with, after their own pointer checks: the segment-table and workspace checks (tp_max: the
 // entry point's limit on TP), the clamped, non-decreasing copy of cu_seqlens inside ws, and from it the work list at the head of ws with
 // bq query rows per item (0: the fp32 kernel's own granularity; the list then holds room for 256-row items).  -> *max_items for the launch
+// need: what ws must hold when the entry point puts more behind the two tables (the split forms' partial planes); 0 = the tables alone
 static int attn_begin(hipStream_t stream, const int32_t* cu_seqlens, int32_t nseg, int64_t TP, int64_t tp_max, void* ws, size_t ws_bytes,
-                      int bq, int* max_items) {
+                      int bq, int* max_items, size_t need = 0) {
   if (!cu_seqlens || nseg < 0 || TP < 0 || TP > tp_max) return RAP_ERR_INVALID;
-  if (!ws || ws_bytes < rap_attention_workspace_bytes(TP, nseg)) return RAP_ERR_WORKSPACE;
+  if (!ws || ws_bytes < (need ? need : rap_attention_workspace_bytes(TP, nseg))) return RAP_ERR_WORKSPACE;
   *max_items = (int)(TP / (bq ? bq : RAP_ATTN_BQ)) + nseg + 1;
   int32_t* cu_s = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + attn_items_bytes(TP, nseg));
   const int rc = launch_sanitize_cu(stream, cu_seqlens, nseg + 1, (long)TP, cu_s);
@@ -67,6 +68,35 @@ extern "C" int rap_attention_f32(const float* qkv_headmajor, const int32_t* cu_s
   int rc, max_items;
   if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 0, &max_items))) return rc;
   return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, nullptr, nullptr, 1);
+}
+
+// The split-KV forms few-token model calls run (attention_f32_splits / attention_x2_splits pick them there), for the parity tests:
+// ws = [work items | sanitised cu_seqlens | partial O: splits x TP x heads x 64 floats | (max, row sum): splits x TP x heads x 2 floats]
+// (the fp32 form keeps its row sums in the first half of the last plane)
+static bool attn_splits_ok(int32_t splits) { return splits == 1 || splits == 2 || splits == 4; }
+static size_t attn_part_o_bytes(int64_t TP, int32_t heads, int32_t splits) { return (size_t)splits * (size_t)TP * (size_t)heads * 64 * sizeof(float); }
+extern "C" size_t rap_attention_split_workspace_bytes(int64_t TP, int32_t nseg, int32_t heads, int32_t splits) {
+  if (TP < 0 || nseg < 0 || heads <= 0 || !attn_splits_ok(splits)) return 0;
+  const size_t base = rap_attention_workspace_bytes(TP, nseg);
+  if (splits == 1) return base;
+  return base + attn_part_o_bytes(TP, heads, splits) + align_up((size_t)splits * (size_t)TP * (size_t)heads * 2 * sizeof(float), 256);
+}
+extern "C" int rap_attention_f32_split(const float* qkv_headmajor, const int32_t* cu_seqlens, int32_t nseg, float* out, int64_t TP,
+                                       int32_t heads, const float* logit_bound, int32_t splits, void* ws, size_t ws_bytes, void* stream_) {
+  if (!qkv_headmajor || !out || heads <= 0 || !attn_splits_ok(splits) || (splits > 1 && !logit_bound)) return RAP_ERR_INVALID;
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc, max_items;
+  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 0, &max_items,
+                       rap_attention_split_workspace_bytes(TP, nseg, heads, splits))))
+    return rc;
+  if (splits == 1)
+    return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, nullptr, nullptr, 1);
+  char* base = reinterpret_cast<char*>(ws);
+  const int32_t* cu_s = reinterpret_cast<const int32_t*>(base + attn_items_bytes(TP, nseg));
+  float* part_o = reinterpret_cast<float*>(base + rap_attention_workspace_bytes(TP, nseg));
+  float* part_l = reinterpret_cast<float*>(reinterpret_cast<char*>(part_o) + attn_part_o_bytes(TP, heads, splits));
+  return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, part_o, part_l,
+                              splits, cu_s, nseg);
 }
 
 extern "C" int rap_layernorm_mod(const float* x, float* out, int64_t TP, int32_t d, const float* mod, int64_t mod_stride,
@@ -189,6 +219,25 @@ extern "C" int rap_x2_attention(const uint16_t* qk, const uint16_t* vt, int32_t 
   int rc, max_items;
   if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &max_items))) return rc;
   return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items);
+}
+// the same over `splits` key ranges per work item (workspace layout: see rap_attention_f32_split)
+extern "C" int rap_x2_attention_split(const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens, int32_t nseg,
+                                      uint16_t* out, int64_t TP, int64_t n_tokens, int32_t heads, int32_t splits, void* ws, size_t ws_bytes,
+                                      void* stream_) {
+  if (!qk || !vt || !out || heads <= 0 || !attn_splits_ok(splits) || n_tokens < 0 || n_tokens > TP || (int64_t)vt_nblk * 64 < TP)
+    return RAP_ERR_INVALID;
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc, max_items;
+  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &max_items,
+                       rap_attention_split_workspace_bytes(TP, nseg, heads, splits))))
+    return rc;
+  if (splits == 1) return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items);
+  char* base = reinterpret_cast<char*>(ws);
+  const int32_t* cu_s = reinterpret_cast<const int32_t*>(base + attn_items_bytes(TP, nseg));
+  float* part_o = reinterpret_cast<float*>(base + rap_attention_workspace_bytes(TP, nseg));
+  float* part_ml = reinterpret_cast<float*>(reinterpret_cast<char*>(part_o) + attn_part_o_bytes(TP, heads, splits));
+  return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, part_o, part_ml, splits,
+                             (int)n_tokens, cu_s, nseg);
 }
 
 // ---------------------------------------------------------------------------------------------

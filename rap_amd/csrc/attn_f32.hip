@@ -444,7 +444,9 @@ __global__ __launch_bounds__(256) void attention_combine_kernel(const float* __r
     acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     l += part_l[((size_t)s * TP + t) * heads + (c >> 6)];
   }
-  const float inv = l > 0.f ? 1.0f / l : 0.f;
+  // l = NaN: a range of the main kernel refused this head (bound above 40) -- the refusal must reach out as NaN, not as zeros (l = 0,
+  // a row no key contributed to, keeps its zeros)
+  const float inv = (l > 0.f || l != l) ? 1.0f / l : 0.f;
   acc.x *= inv; acc.y *= inv; acc.z *= inv; acc.w *= inv;
   *reinterpret_cast<float4*>(out + t * dmodel + c) = acc;
 }

@@ -15,6 +15,25 @@ int main(void) {
   /* NULL operands and bad strides are refused before any launch */
   if (rap_x2_gemm(1, NULL, 1024, (const uint16_t*)sentinel, 1024, sentinel, 512, 256, 512, 1024, NULL, NULL, 0, 1.0f, 0, NULL, NULL, 8.0f, NULL, 0, NULL) != RAP_ERR_INVALID) { printf("x2 gemm NULL A\n"); ++fails; }
   if (rap_x2_gemm(1, (const uint16_t*)sentinel, 1024, (const uint16_t*)sentinel, 1024, sentinel, 514, 256, 512, 1024, NULL, NULL, 0, 1.0f, 0, NULL, NULL, 8.0f, NULL, 0, NULL) != RAP_ERR_INVALID) { printf("x2 gemm ldc 514\n"); ++fails; }
+  /* the split-KV attention entry points: the query is host arithmetic, NULL operands / a splits value that is none of 1, 2, 4 / a split
+   * without a logit bound are refused, and a short workspace is refused before anything is written */
+  if (rap_attention_split_workspace_bytes(2048, 2, 8, 1) != rap_attention_workspace_bytes(2048, 2) ||
+      rap_attention_split_workspace_bytes(2048, 2, 8, 4) != rap_attention_workspace_bytes(2048, 2) + (size_t)4 * 2048 * 8 * (64 + 2) * 4 ||
+      rap_attention_split_workspace_bytes(2048, 2, 8, 3) != 0 || rap_attention_split_workspace_bytes(2048, 2, 0, 2) != 0) { printf("split attention workspace query\n"); ++fails; }
+  if (rap_attention_f32_split(NULL, (const int32_t*)sentinel, 1, (float*)sentinel, 256, 8, (const float*)sentinel, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("f32 split attention NULL qkv\n"); ++fails; }
+  if (rap_attention_f32_split((const float*)sentinel, (const int32_t*)sentinel, 1, NULL, 256, 8, (const float*)sentinel, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("f32 split attention NULL out\n"); ++fails; }
+  if (rap_attention_f32_split((const float*)sentinel, NULL, 1, (float*)sentinel, 256, 8, (const float*)sentinel, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("f32 split attention NULL cu_seqlens\n"); ++fails; }
+  if (rap_attention_f32_split((const float*)sentinel, (const int32_t*)sentinel, 1, (float*)sentinel, 256, 8, NULL, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("f32 split attention without a bound\n"); ++fails; }
+  if (rap_attention_f32_split((const float*)sentinel, (const int32_t*)sentinel, 1, (float*)sentinel, 256, 8, (const float*)sentinel, 3, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("f32 split attention splits 3\n"); ++fails; }
+  if (rap_attention_f32_split((const float*)sentinel, (const int32_t*)sentinel, 1, (float*)sentinel, 256, 8, (const float*)sentinel, 2, NULL, (size_t)1 << 30, NULL) != RAP_ERR_WORKSPACE) { printf("f32 split attention NULL workspace\n"); ++fails; }
+  if (rap_attention_f32_split((const float*)sentinel, (const int32_t*)sentinel, 1, (float*)sentinel, 256, 8, (const float*)sentinel, 2, sentinel, rap_attention_split_workspace_bytes(256, 1, 8, 2) - 1, NULL) != RAP_ERR_WORKSPACE) { printf("f32 split attention short workspace\n"); ++fails; }
+  if (rap_x2_attention_split(NULL, (const uint16_t*)sentinel, 4, (const int32_t*)sentinel, 1, (uint16_t*)sentinel, 256, 0, 8, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("x2 split attention NULL qk\n"); ++fails; }
+  if (rap_x2_attention_split((const uint16_t*)sentinel, NULL, 4, (const int32_t*)sentinel, 1, (uint16_t*)sentinel, 256, 0, 8, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("x2 split attention NULL vt\n"); ++fails; }
+  if (rap_x2_attention_split((const uint16_t*)sentinel, (const uint16_t*)sentinel, 4, (const int32_t*)sentinel, 1, NULL, 256, 0, 8, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("x2 split attention NULL out\n"); ++fails; }
+  if (rap_x2_attention_split((const uint16_t*)sentinel, (const uint16_t*)sentinel, 4, NULL, 1, (uint16_t*)sentinel, 256, 0, 8, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("x2 split attention NULL cu_seqlens\n"); ++fails; }
+  if (rap_x2_attention_split((const uint16_t*)sentinel, (const uint16_t*)sentinel, 4, (const int32_t*)sentinel, 1, (uint16_t*)sentinel, 256, 257, 8, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("x2 split attention n_tokens above TP\n"); ++fails; }
+  if (rap_x2_attention_split((const uint16_t*)sentinel, (const uint16_t*)sentinel, 3, (const int32_t*)sentinel, 1, (uint16_t*)sentinel, 256, 0, 8, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("x2 split attention short V^T image\n"); ++fails; }
+  if (rap_x2_attention_split((const uint16_t*)sentinel, (const uint16_t*)sentinel, 4, (const int32_t*)sentinel, 1, (uint16_t*)sentinel, 256, 0, 8, 4, sentinel, rap_attention_split_workspace_bytes(256, 1, 8, 4) - 1, NULL) != RAP_ERR_WORKSPACE) { printf("x2 split attention short workspace\n"); ++fails; }
   if (rap_model_set_compute_dtype(NULL, 3, NULL) != RAP_ERR_INVALID) { printf("NULL model\n"); ++fails; }
   printf("c consumer: %d failure(s), ABI version %d\n", fails, rap_version());
   return fails;

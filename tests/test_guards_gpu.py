@@ -380,7 +380,7 @@ def test_x2_gemm_qkv_writes_only_the_planes_and_the_transposed_v_image(lib, dev,
 
 
 # ---------------------------------------------------------------------------------------------
-# attention: rap_attention_f32, rap_attention_h16, rap_x2_attention
+# attention: rap_attention_f32, rap_attention_h16, rap_x2_attention, and the split forms rap_attention_f32_split, rap_x2_attention_split
 # ---------------------------------------------------------------------------------------------
 def attention_operands(H, cu, seed):
     g = torch.Generator().manual_seed(seed)
@@ -495,6 +495,73 @@ def test_x2_attention_stays_inside_out_and_its_exact_workspace(lib, dev, seg, H)
         qkd, vtd, cud = c.inp(qk, "qk"), c.inp(vt, "vt"), c.inp(torch.tensor(cu, dtype=I32), "cu_seqlens")
         rc = lib.rap_x2_attention(_lib.ptr(qkd), _lib.ptr(vtd), nblk, _lib.ptr(cud), nseg, _lib.ptr(out), TP, H, ctypes.c_void_p(ws.ptr),
                                   need - short, stream(dev))
+        torch.cuda.synchronize()
+        return rc, out
+
+    def run(c):
+        rc, out = call(c)
+        assert rc == 0
+        got = TX.unpack_ref(out.cpu(), H * 64)
+        assert not torch.isnan(got).any()
+        assert float((got - ref).abs().max()) < TX.X2_ATTN_BOUND
+        return [out]
+    run_both(dev, run)
+    refused_call_wrote_nothing(dev, call)
+
+
+def split_attention_ws(c, lib, TP, nseg, H, splits):
+    need = lib.rap_attention_split_workspace_bytes(TP, nseg, H, splits)
+    assert need > lib.rap_attention_workspace_bytes(TP, nseg)
+    return c.out(need, name="split attention workspace"), need
+
+
+@pytest.mark.parametrize("splits", [2, 4])
+@pytest.mark.parametrize("H", [1, 4])
+@pytest.mark.parametrize("seg", list(SEGMENTS))
+def test_attention_f32_split_stays_inside_out_and_its_exact_workspace(lib, dev, seg, H, splits):
+    cu = SEGMENTS[seg]
+    TP, nseg = cu[-1], len(cu) - 1
+    q, k, v = attention_operands(H, cu, 11 + H)
+    qkv = torch.stack([q, k, v])                                                 # [3][H][TP][64]
+    ref = O.varlen_attention(qkv.permute(2, 0, 1, 3).double(), torch.tensor(cu, dtype=I32)).reshape(TP, H * 64)
+    bound = TH.logit_bound(q, k)
+    assert float(bound.max()) <= 40.0
+
+    def call(c, short=0):
+        out = c.out_view(F32, (TP, H * 64), "out")
+        ws, need = split_attention_ws(c, lib, TP, nseg, H, splits)
+        qd, cud, bd = c.inp(qkv, "qkv"), c.inp(torch.tensor(cu, dtype=I32), "cu_seqlens"), c.inp(bound, "logit_bound")
+        rc = lib.rap_attention_f32_split(_lib.ptr(qd), _lib.ptr(cud), nseg, _lib.ptr(out), TP, H, _lib.ptr(bd), splits, ctypes.c_void_p(ws.ptr),
+                                         need - short, stream(dev))
+        torch.cuda.synchronize()
+        return rc, out
+
+    def run(c):
+        rc, out = call(c)
+        assert rc == 0
+        err = (out.cpu().double() - ref).abs().max().item()
+        assert err < TK.ATTN_BOUND, err
+        return [out]
+    run_both(dev, run)
+    refused_call_wrote_nothing(dev, call)
+
+
+@pytest.mark.parametrize("splits", [2, 4])
+@pytest.mark.parametrize("H", [1, 4])
+@pytest.mark.parametrize("seg", list(SEGMENTS))
+def test_x2_attention_split_stays_inside_out_and_its_exact_workspace(lib, dev, seg, H, splits):
+    cu = SEGMENTS[seg]
+    TP, nseg = cu[-1], len(cu) - 1
+    q, k, v = attention_operands(H, cu, 11 + H)
+    ref = TX.attention_ref64(q, k, v, torch.tensor(cu))
+    qk, vt, nblk = TX.make_x2_attention_operands(q, k, v)
+
+    def call(c, short=0):
+        out = c.out_view(F16, (TP, 2 * H * 64), "out")
+        ws, need = split_attention_ws(c, lib, TP, nseg, H, splits)
+        qkd, vtd, cud = c.inp(qk, "qk"), c.inp(vt, "vt"), c.inp(torch.tensor(cu, dtype=I32), "cu_seqlens")
+        rc = lib.rap_x2_attention_split(_lib.ptr(qkd), _lib.ptr(vtd), nblk, _lib.ptr(cud), nseg, _lib.ptr(out), TP, 0, H, splits,
+                                        ctypes.c_void_p(ws.ptr), need - short, stream(dev))
         torch.cuda.synchronize()
         return rc, out
 
