@@ -77,6 +77,8 @@ def voxel_down_sample_torch(points: torch.Tensor, voxel_size: float, path: str |
     device = points.device
     pts = _f32c(points)
     N = pts.shape[0]
+    if N == 0:                                             # no voxel is occupied (the entry points refuse an empty cloud)
+        return torch.zeros(0, dtype=torch.int64, device=device)
     lib = _lib.load()
     bounds = torch.empty(6, dtype=torch.int64, device=device)
     dmax = torch.empty(1, dtype=torch.float32, device=device)
