@@ -33,7 +33,9 @@ extern "C" {
  * 6, additive: rap_pair_metrics_workspace_bytes, rap_pair_metrics and rap_transform_errors_direct (the evaluator's metrics table);
  * rap_icp_workspace_bytes and rap_icp (batched ICP); rap_icp_grid_workspace_bytes, rap_icp_grid, rap_nn_grid_workspace_bytes and
  * rap_nearest_neighbors (the same search over a uniform-grid index); rap_attention_split_workspace_bytes, rap_attention_f32_split and
- * rap_x2_attention_split (kernel-level access to the split-KV attention of few-token calls). */
+ * rap_x2_attention_split (kernel-level access to the split-KV attention of few-token calls); rap_gemm_f32_form and rap_gemm_h16_form (the
+ * GEMM dispatch decision as host arithmetic), rap_gemm_f32_splitk_workspace_bytes and rap_gemm_f32_splitk (kernel-level access to the
+ * split-K form of the fp32 residual and SiLU GEMMs of few-token calls). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -390,6 +392,38 @@ int rap_gemm_f32(int32_t epilogue, const float* A, int32_t lda, const float* W, 
                  int32_t M, int32_t N, int32_t K, const float* bias, const float* resid, int32_t ldr,
                  const uint8_t* anchor, const float* anchor_emb, int32_t heads, void* stream);
 int rap_geglu_interleave(const float* W, const float* b, float* Wp, float* bp, int32_t inner, int32_t K, void* stream);
+/* Which kernel a GEMM call takes, as pure host arithmetic (no device is touched; the launchers switch on the same function).  The FORM code is
+ *   100 * kernel + 10 * stages + splits
+ *   kernel: 1 = 128 x 128 tiles; 2 = 256 x 256, one tile per block (any M: rows are clamped, stores predicated); 3 = 256 x 256 persistent
+ *           (one block per CU walks its share of the tiles; M % 256 == 0)
+ *   stages: LDS stages of the 128 x 128 kernel: 2, or 4 for the four-stage ring of the 16-bit kernels (launches of at most tuning key 18
+ *           blocks); 0 for the 256 x 256 kernels
+ *   splits: blocks per tile that K is divided over: 1 (no split), 2 or 4 -- on the 128 x 128 kernel only
+ * so e.g. 121, 141, 144, 201, 301.  0: nothing is launched (M <= 0).  Negative (RAP_ERR_INVALID): the shape is refused.  The current
+ * tuning keys are honoured (6 split K, 11 / 12 persistent, 18 ring), as by the calls themselves.
+ * rap_gemm_f32_form: the call rap_gemm_f32 / rap_gemm_f32_splitk makes with these arguments; has_ws != 0: a split-K workspace is handed in
+ *   (planes: the planes it holds for epilogue 2 -- 2 or 4; ignored otherwise).
+ * rap_gemm_h16_form: dtype 1 / 2: rap_gemm_h16 (epilogue 5: rap_gemm_h16_qkvnorm), has_ws != 0: rap_gemm_h16_splitk with its workspace;
+ *   dtype 3: rap_x2_gemm (K, lda, ldw in physical fp16 columns). */
+int rap_gemm_f32_form(int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldc, int32_t ldr,
+                      int32_t has_ws, int32_t planes);
+int rap_gemm_h16_form(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t has_ws);
+/* Epilogues 1 (bias + residual) and 2 (bias + SiLU) of rap_gemm_f32 with the split-K form rap_sample uses on few-token calls (tuning key
+ * 6).  Counting tiles of 128 x 128 and k-tiles of 32 columns:
+ *   epilogue 1: K >= 1024 and at most 128 tiles, or K >= 512 and at most 64 tiles: K over 4 blocks per tile (block y takes k-tiles
+ *     [nk y / 4, nk (y + 1) / 4): the shares need not be equal), workspace 4 M N floats;
+ *   epilogue 2: planes (2 or 4; anything else: RAP_ERR_INVALID) blocks per tile when K >= 512, K / 32 is a multiple of planes and there are at
+ *     most 64 tiles, workspace planes M N floats.
+ * The blocks write fp32 partial tiles to ws and a combine pass forms resid + bias + partials (or SiLU of bias + partials) in a fixed order
+ * (deterministic; equals the unsplit result up to the fp32 association of the k-sum).  ldc % 4 == 0 and ldr % 4 == 0 (rows move as 16-byte
+ * pieces), otherwise the call runs unsplit.  resid (epilogue 1: required, may alias C) has row stride ldr.
+ * rap_gemm_f32_splitk_workspace_bytes: 0 when the rule does not split -- a function of the shape alone (key 6 gates the launch, not the
+ * reservation).  With a workspace size of 0 the call is rap_gemm_f32.  NULL operands, other epilogues (RAP_ERR_INVALID) and a workspace
+ * below the query's value (RAP_ERR_WORKSPACE) are refused before anything touches the device. */
+size_t rap_gemm_f32_splitk_workspace_bytes(int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t planes);
+int rap_gemm_f32_splitk(int32_t epilogue, const float* A, int32_t lda, const float* W, int32_t ldw, float* C, int32_t ldc, int32_t M,
+                        int32_t N, int32_t K, const float* bias, const float* resid, int32_t ldr, int32_t planes, void* ws,
+                        size_t ws_bytes, void* stream);
 /* The work list of one attention launch, as rap_sample / rap_dit_forward build it (once per call, on the device): one item
  * {seg_start, seg_len, q0, 0} (4 x int32) per `block_queries` (256) query rows of every segment of cu_seqlens (nseg + 1 entries),
  * LONGEST SEGMENT FIRST when sort_ws (nseg ints of scratch) is given -- a block streams all keys of its segment, blocks are

@@ -104,6 +104,11 @@ SIGNATURES = {
                                         _P, _P, _P, c_size_t, _P]),
     "rap_gemm_f32": (c_int32, [c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int32,
                                _P, _P, c_int32, _P]),
+    "rap_gemm_f32_form": (c_int32, [c_int32] * 10),
+    "rap_gemm_h16_form": (c_int32, [c_int32] * 8),
+    "rap_gemm_f32_splitk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "rap_gemm_f32_splitk": (c_int32, [c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int32, c_int32,
+                                      _P, c_size_t, _P]),
     "rap_geglu_interleave": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, _P]),
     "rap_build_attention_worklist": (c_int32, [_P, c_int32, c_int32, _P, c_int32, _P, _P]),
     "rap_attention_workspace_bytes": (c_size_t, [c_int64, c_int32]),

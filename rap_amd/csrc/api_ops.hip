@@ -24,6 +24,37 @@ extern "C" int rap_gemm_f32(int32_t epilogue, const float* A, int32_t lda, const
   return launch_gemm_f32((hipStream_t)stream, epilogue, g);
 }
 
+// the dispatch decision of rap_gemm_f32 / the model's fp32 GEMMs as host arithmetic (kernels.h: the form codes)
+extern "C" int rap_gemm_f32_form(int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldc, int32_t ldr,
+                                 int32_t has_ws, int32_t planes) {
+  static float ws_given;      // (never dereferenced: the form only asks whether a workspace was handed in)
+  GemmParams g{};
+  g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr; g.M = M; g.N = N; g.K = K;
+  g.splitk_ws = has_ws ? &ws_given : nullptr; g.splitk_planes = planes;
+  return gemm_f32_form(epilogue, g);
+}
+// the residual (1) and SiLU (2) epilogues with the split-K workspace rap_sample hands them on few-token calls
+extern "C" size_t rap_gemm_f32_splitk_workspace_bytes(int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t planes) {
+  const int s = gemm_f32_splits_by_shape(epilogue, M, N, K, planes);
+  if (s <= 1) return 0;
+  return (size_t)(epilogue == EPI_BIAS_RESID ? 4 : planes) * (size_t)M * (size_t)N * sizeof(float);
+}
+extern "C" int rap_gemm_f32_splitk(int32_t epilogue, const float* A, int32_t lda, const float* W, int32_t ldw, float* C, int32_t ldc, int32_t M,
+                                   int32_t N, int32_t K, const float* bias, const float* resid, int32_t ldr, int32_t planes, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  if (!A || !W || !C || (epilogue != EPI_BIAS_RESID && epilogue != EPI_BIAS_SILU)) return RAP_ERR_INVALID;
+  if (epilogue == EPI_BIAS_RESID && !resid) return RAP_ERR_INVALID;
+  if (epilogue == EPI_BIAS_SILU && planes != 2 && planes != 4) return RAP_ERR_INVALID;
+  const size_t need = rap_gemm_f32_splitk_workspace_bytes(epilogue, M, N, K, planes);
+  if (need && (!ws || ws_bytes < need)) return RAP_ERR_WORKSPACE;
+  GemmParams g{};
+  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K; g.bias = bias;
+  g.resid = resid; g.ldr = ldr;
+  g.splitk_ws = need ? reinterpret_cast<float*>(ws) : nullptr;
+  g.splitk_planes = need && epilogue == EPI_BIAS_SILU ? planes : 0;
+  return launch_gemm_f32((hipStream_t)stream, epilogue, g);
+}
+
 extern "C" int rap_geglu_interleave(const float* W, const float* b, float* Wp, float* bp, int32_t inner, int32_t K,
                                     void* stream) {
   if (!W || !b || !Wp || !bp) return RAP_ERR_INVALID;
@@ -164,6 +195,13 @@ extern "C" int rap_gemm_h16_splitk(int32_t dtype, int32_t epilogue, const uint16
   if (epilogue == EPI_H_BIAS_RESID_H16) g.resid_h = reinterpret_cast<const uint16_t*>(resid); else g.resid = reinterpret_cast<const float*>(resid);
   g.splitk_ws = need ? reinterpret_cast<float*>(ws) : nullptr;
   return launch_gemm_h16((hipStream_t)stream, dtype, epilogue, g);
+}
+// the dispatch decision of rap_gemm_h16 / rap_gemm_h16_qkvnorm / rap_gemm_h16_splitk (dtype 1, 2) and rap_x2_gemm (dtype 3: K, lda, ldw physical)
+extern "C" int rap_gemm_h16_form(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t has_ws) {
+  static float ws_given;      // (never dereferenced)
+  GemmParamsH g = gemm_h16_params(nullptr, lda, nullptr, ldw, nullptr, N, M, N, K, nullptr, N);
+  g.splitk_ws = has_ws ? &ws_given : nullptr;
+  return gemm_h16_form(dtype, epilogue, g);
 }
 extern "C" int rap_attention_h16(int32_t dtype, const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk,
                                  const int32_t* cu_seqlens, int32_t nseg, uint16_t* out, int64_t TP, int32_t heads,

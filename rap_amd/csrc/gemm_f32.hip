@@ -759,10 +759,9 @@ rap_tuning_t g_rap_gemm_variant = 48;
 rap_tuning_t g_rap_gemm_f32_persistent = 1;     // tuning key 12: the persistent 256 x 256 kernel for full-tile shapes (1, default) or one tile per block (0)
 
 template <int EPI>
-static int launch_gemm_variant(hipStream_t stream, const GemmParams& p, int variant) {
+static int launch_gemm_variant(hipStream_t stream, const GemmParams& p, int form) {
   const int mt = (p.M + GBM - 1) / GBM;
-  if (variant == 32 && p.N % 256 == 0 && g_rap_gemm_f32_persistent && p.M % 256 == 0 &&
-      (long)(p.M / 256) * (p.N / 256) >= 512 && p.lda <= (1 << 20) && p.ldw <= (1 << 20)) {
+  if (form / 100 == RAP_FORM_256P) {
     constexpr int LDS = 2 * (256 + 256) * 128;
     auto kern = gemm_f32_dma256p_kernel<EPI>;
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
@@ -780,7 +779,7 @@ static int launch_gemm_variant(hipStream_t stream, const GemmParams& p, int vari
     }
     const int total = (p.M / 256) * (p.N / 256);
     hipLaunchKernelGGL(kern, dim3(total < n_cu ? total : n_cu), dim3(512), LDS, stream, p);
-  } else if (variant == 32 && p.N % 256 == 0) {
+  } else if (form / 100 == RAP_FORM_256) {
     constexpr int LDS = 2 * (256 + 256) * 128;
     auto kern = gemm_f32_dma256_kernel<EPI>;
     // per device and cheap: set unconditionally (a process may drive several GPUs)
@@ -804,51 +803,71 @@ rap_tuning_t g_rap_gemm_stagger = 1;     // measured (r01 run 39): +1.3 % on the
 // headline 15 940 -> 16 049 points/s, all-step deviation from the unmodified reference unchanged (final cloud 5.4e-7 vs 6.6e-7,
 // per-step maximum 9.5e-7 vs 8.3e-7: the fp32 noise floor).  0 = libm-grade erff.
 rap_tuning_t g_rap_geglu_fast = 1;
-int launch_gemm_f32(hipStream_t stream, int epilogue, const GemmParams& p_in) {
-  GemmParams p = p_in;
-  p.geglu_fast = g_rap_geglu_fast;
-  p.stagger = ((long)((p.M + GBM - 1) / GBM) * (p.N / GBN) >= 1024) ? g_rap_gemm_stagger.load() : 0;     // only when the chip is filled twice over
-  if (p.M <= 0) return RAP_OK;
+// The dispatch decision as host arithmetic (kernels.h: the form codes): which kernel a call takes, and over how many blocks per tile its K
+// is split.  launch_gemm_f32 switches on the result; tests/test_gemm_cases_host.py pins it through rap_gemm_f32_form.
+//  * K split over 4 blocks per 128 x 128 tile, bias + residual with a workspace -- few-row calls: K >= 1024 (ff2) when the tile grid covers at
+//    most half of the CUs, K >= 512 (the out-projection) when it covers at most a quarter (r03: one pair of 2 x 1024 points -- 64 tiles, a
+//    chain of 16 k-tiles each); the k-tiles need not divide evenly (block y takes k-tiles [nk y / 4, nk (y + 1) / 4))
+//  * K split over `splitk_planes` (2 or 4) blocks per tile, bias + SiLU with a workspace -- the hidden layers of final_mlp (fp32 in every mode)
+//    of a few-token call: 64 / 32 tiles of a 16-k-tile chain on 256 CUs (r06 call 2: 39 us per launch, a fifth of a demo-size pair's per-step
+//    overhead); the k-tiles must divide evenly here
+//  * otherwise the 256 x 256 kernel from 512 of its tiles on (N % 256 == 0, K >= 256), persistent when every row tile is full
+int gemm_f32_splits_by_shape(int epilogue, int M, int N, int K, int planes) {
+  if (M <= 0 || N <= 0 || N % GBN != 0 || K <= 0 || K % GBK != 0) return 1;
+  const long tiles128 = (long)((M + GBM - 1) / GBM) * (N / GBN);
+  if (epilogue == EPI_BIAS_RESID) return ((K >= 1024 && tiles128 <= 128) || (K >= 512 && tiles128 <= 64)) ? 4 : 1;
+  if (epilogue == EPI_BIAS_SILU) return ((planes == 2 || planes == 4) && K >= 512 && (K / GBK) % planes == 0 && tiles128 <= 64) ? planes : 1;
+  return 1;
+}
+int gemm_f32_form(int epilogue, const GemmParams& p) {
+  if (p.M <= 0) return 0;
   if (p.N % GBN != 0 || p.K % GBK != 0 || p.K <= 0) return RAP_ERR_INVALID;
   if ((p.lda & 3) || (p.ldw & 3)) return RAP_ERR_INVALID;
+  if (epilogue < EPI_BIAS || epilogue > EPI_BIAS_RELU) return RAP_ERR_INVALID;
   int v = 48;
 #ifdef RAP_ABLATION_BUILD
   v = g_rap_gemm_variant;
 #endif
   if (v != 16 && v != 32) v = (p.N % 256 == 0 && p.K >= 256 && (long)((p.M + 255) / 256) * (p.N / 256) >= 512) ? 32 : 16;
-  // few-row calls: K >= 1024 (ff2) when the tile grid covers at most half of the CUs, K >= 512 (the out-projection) when it covers at
-  // most a quarter (r03: one pair of 2 x 1024 points -- 64 tiles, a chain of 16 k-tiles each)
-  const long tiles128 = (long)((p.M + GBM - 1) / GBM) * (p.N / GBN);
-  if (epilogue == EPI_BIAS_RESID && (v == 16 || v == 32) && p.splitk_ws && g_rap_gemm_splitk && (p.ldr & 3) == 0 && (p.ldc & 3) == 0 &&
-      ((p.K >= 1024 && tiles128 <= 128) || (p.K >= 512 && tiles128 <= 64))) {
-    const int splits = 4;
+  if (p.splitk_ws && g_rap_gemm_splitk && (p.ldc & 3) == 0 && (epilogue != EPI_BIAS_RESID || (p.ldr & 3) == 0)) {
+    const int splits = gemm_f32_splits_by_shape(epilogue, p.M, p.N, p.K, p.splitk_planes);
+    if (splits > 1) return rap_gemm_form(RAP_FORM_128, 2, splits);
+  }
+  if (v == 32 && p.N % 256 == 0) {
+    const bool persistent = g_rap_gemm_f32_persistent && p.M % 256 == 0 && (long)(p.M / 256) * (p.N / 256) >= 512 && p.lda <= (1 << 20) &&
+                            p.ldw <= (1 << 20);
+    return rap_gemm_form(persistent ? RAP_FORM_256P : RAP_FORM_256, 0, 1);
+  }
+  return rap_gemm_form(RAP_FORM_128, 2, 1);
+}
+
+int launch_gemm_f32(hipStream_t stream, int epilogue, const GemmParams& p_in) {
+  GemmParams p = p_in;
+  p.geglu_fast = g_rap_geglu_fast;
+  p.stagger = ((long)((p.M + GBM - 1) / GBM) * (p.N / GBN) >= 1024) ? g_rap_gemm_stagger.load() : 0;     // only when the chip is filled twice over
+  const int form = gemm_f32_form(epilogue, p);
+  if (form <= 0) return form;      // nothing to do (M <= 0) or a refused shape
+  const int splits = form % 10;
+  if (splits > 1) {                // partial tiles to splitk_ws, then one combine pass (residual + bias + partials, or SiLU of bias + partials)
     hipLaunchKernelGGL(gemm_f32_dma_kernel<EPI_SPLITK_PART>, dim3(((p.M + GBM - 1) / GBM) * (p.N / GBN), splits), dim3(256), 0, stream, p);
     RAP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gemm_splitk_combine_kernel<false>, dim3((unsigned)(((long)p.M * (p.N / 4) + 255) / 256)), dim3(256), 0, stream, p, splits);
-    RAP_LAUNCH_CHECK();
-    return RAP_OK;
-  }
-  // the hidden layers of final_mlp (Linear + SiLU, fp32 in every mode) of a few-token call: 64 / 32 tiles of a 16-k-tile chain on 256 CUs
-  // (r06 call 2: 39 us per launch, a fifth of a demo-size pair's per-step overhead) -- K over `splitk_planes` (2 or 4) blocks per tile
-  if (epilogue == EPI_BIAS_SILU && p.splitk_ws && (p.splitk_planes == 2 || p.splitk_planes == 4) && g_rap_gemm_splitk && (p.ldc & 3) == 0 &&
-      p.K >= 512 && (p.K / GBK) % p.splitk_planes == 0 && tiles128 <= 64) {
-    hipLaunchKernelGGL(gemm_f32_dma_kernel<EPI_SPLITK_PART>, dim3(((p.M + GBM - 1) / GBM) * (p.N / GBN), p.splitk_planes), dim3(256), 0, stream, p);
-    RAP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(gemm_splitk_combine_kernel<true>, dim3((unsigned)(((long)p.M * (p.N / 4) + 255) / 256)), dim3(256), 0, stream, p, p.splitk_planes);
+    const dim3 grid((unsigned)(((long)p.M * (p.N / 4) + 255) / 256));
+    if (epilogue == EPI_BIAS_RESID) hipLaunchKernelGGL(gemm_splitk_combine_kernel<false>, grid, dim3(256), 0, stream, p, splits);
+    else hipLaunchKernelGGL(gemm_splitk_combine_kernel<true>, grid, dim3(256), 0, stream, p, splits);
     RAP_LAUNCH_CHECK();
     return RAP_OK;
   }
   switch (epilogue) {
-    case EPI_BIAS: return launch_gemm_variant<EPI_BIAS>(stream, p, v);
-    case EPI_BIAS_RESID: return launch_gemm_variant<EPI_BIAS_RESID>(stream, p, v);
-    case EPI_BIAS_SILU: return launch_gemm_variant<EPI_BIAS_SILU>(stream, p, v);
-    case EPI_GEGLU: return launch_gemm_variant<EPI_GEGLU>(stream, p, v);
+    case EPI_BIAS: return launch_gemm_variant<EPI_BIAS>(stream, p, form);
+    case EPI_BIAS_RESID: return launch_gemm_variant<EPI_BIAS_RESID>(stream, p, form);
+    case EPI_BIAS_SILU: return launch_gemm_variant<EPI_BIAS_SILU>(stream, p, form);
+    case EPI_GEGLU: return launch_gemm_variant<EPI_GEGLU>(stream, p, form);
     case EPI_QKV_HEADMAJOR:
       if (p.N != 3 * p.heads * 64) return RAP_ERR_INVALID;
       if (p.gamma_q && !p.gamma_k) return RAP_ERR_INVALID;
-      return launch_gemm_variant<EPI_QKV_HEADMAJOR>(stream, p, v);
-    case EPI_BIAS_ANCHOR: return launch_gemm_variant<EPI_BIAS_ANCHOR>(stream, p, v);
-    case EPI_BIAS_RELU: return launch_gemm_variant<EPI_BIAS_RELU>(stream, p, v);
+      return launch_gemm_variant<EPI_QKV_HEADMAJOR>(stream, p, form);
+    case EPI_BIAS_ANCHOR: return launch_gemm_variant<EPI_BIAS_ANCHOR>(stream, p, form);
+    case EPI_BIAS_RELU: return launch_gemm_variant<EPI_BIAS_RELU>(stream, p, form);
     default: return RAP_ERR_INVALID;
   }
 }

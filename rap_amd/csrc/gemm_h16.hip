@@ -1313,10 +1313,13 @@ static int launch_cfg(hipStream_t stream, const GemmParamsH& p, int splits = 1) 
 // not kept: residual GEMMs 14.5 vs 13.9 us, QKV 21.0 vs 20.4, 25.2 vs 24.9 ms per demo-pair call; profiles/r06_c14_x2_ring_five_stages_*.
 // The ~1 us per split-precision k-tile that remains is not the L2 round trip.)
 rap_tuning_t g_rap_ring_blocks = 256;
-template <int EPI, int DT, bool X2 = false>
-static int launch_small(hipStream_t stream, const GemmParamsH& p, int splits = 1) {
+static int small_stages(const GemmParamsH& p, int splits) {
   const long blocks = (long)((p.M + 127) / 128) * (p.N / 128) * splits;
-  if (blocks <= (long)g_rap_ring_blocks) return launch_cfg<EPI, DT, 2, 2, 2, 2, X2, 4>(stream, p, splits);
+  return blocks <= (long)g_rap_ring_blocks ? 4 : 2;
+}
+template <int EPI, int DT, bool X2 = false>
+static int launch_small(hipStream_t stream, const GemmParamsH& p, int stages, int splits = 1) {
+  if (stages == 4) return launch_cfg<EPI, DT, 2, 2, 2, 2, X2, 4>(stream, p, splits);
   return launch_cfg<EPI, DT, 2, 2, 2, 2, X2, 2>(stream, p, splits);
 }
 
@@ -1372,10 +1375,10 @@ int gemm_h16_splits_by_shape(int M, int N, int K) {
 int gemm_h16_splits(int M, int N, int K) { return g_rap_gemm_splitk ? gemm_h16_splits_by_shape(M, N, K) : 1; }
 
 template <int DT>
-static int launch_splitk(hipStream_t stream, int epilogue, const GemmParamsH& p, int splits) {
+static int launch_splitk(hipStream_t stream, int epilogue, const GemmParamsH& p, int stages, int splits) {
   GemmParamsH q = p;
   q.C = p.splitk_ws; q.ldc = p.N; q.bias = nullptr; q.resid = nullptr; q.resid_h = nullptr; q.splitk_ws = nullptr;
-  if (int rc = launch_small<EPI_H_BIAS_RESID_F32, DT>(stream, q, splits)) return rc;
+  if (int rc = launch_small<EPI_H_BIAS_RESID_F32, DT>(stream, q, stages, splits)) return rc;
   if (p.defer_combine) return RAP_OK;      // the caller's combine + LayerNorm pass consumes the planes (launch_resid_combine_ln_h16)
   const long n8 = (long)p.M * (p.N / 8);
   const dim3 grid((unsigned)((n8 + 255) / 256));
@@ -1397,75 +1400,109 @@ static bool use_persistent(const GemmParamsH& p) {
   return g_rap_gemm_h16_persistent && p.M % 256 == 0 && p.N % 256 == 0 && p.K >= 128 && p.K <= 2048 && (long)(p.M / 256) * (p.N / 256) >= 512 &&
          p.lda <= (1 << 20) && p.ldw <= (1 << 20);
 }
-
-template <int EPI, int DT>
-static int launch_variant(hipStream_t stream, const GemmParamsH& p) {
-  const bool big = p.N % 256 == 0 && p.K >= 128;
-#ifdef RAP_ABLATION_BUILD
-  if (g_rap_gemm_h16_variant == 0) return launch_cfg<EPI, DT, 2, 2, 2, 2>(stream, p);
-  if (g_rap_gemm_h16_variant == 1 && big) return launch_cfg<EPI, DT, 2, 4, 4, 2>(stream, p);
-#endif
-  // persistent form when every row tile is full and there are at least two rounds of tiles for a 256-CU part; the one-tile-per-block
-  // form for ragged M (it clamps rows) and for few tiles
-  if (big && use_persistent(p)) return launch_php<EPI, DT>(stream, p);
-  // fewer 256 x 256 tiles than CUs (few-token calls): 128 x 128 tiles, two blocks per CU, fill the chip better -- one pair of
-  // 2 x 1024 points x 10 steps 26.6 -> 21.6 ms in bf16, 2 x 4096 x 20 steps 102.5 -> 94.0 ms, unchanged from 4 pairs up (r03 call 31)
-  if (big && (long)((p.M + 255) / 256) * (p.N / 256) >= 256) return launch_ph<EPI, DT, 0, 1>(stream, p);
-  return launch_small<EPI, DT>(stream, p);
-}
-
-template <int DT>
-static int launch_dt(hipStream_t stream, int epilogue, const GemmParamsH& p) {
-  if ((epilogue == EPI_H_BIAS_RESID_F32 || epilogue == EPI_H_BIAS_RESID_H16) && p.splitk_ws) {
-    const int splits = p.force_splits > 0 ? p.force_splits : gemm_h16_splits(p.M, p.N, p.K);
-    if (splits < 1 || (p.K / 64) % splits != 0) return RAP_ERR_INVALID;
-    if (splits > 1 || p.defer_combine) {      // (defer_combine: partial planes -- one when there is no split -- for the caller's combine + LayerNorm pass)
-      if ((p.ldc & 7) || (p.ldr & 7) || (epilogue == EPI_H_BIAS_RESID_H16 && !p.resid_h)) return RAP_ERR_INVALID;
-      return launch_splitk<DT>(stream, epilogue, p, splits);
-    }
-  }
-  switch (epilogue) {
-    case EPI_H_BIAS: return launch_variant<EPI_H_BIAS, DT>(stream, p);
-    case EPI_H_BIAS_RESID_F32: return launch_variant<EPI_H_BIAS_RESID_F32, DT>(stream, p);
-    case EPI_H_BIAS_RESID_H16:
-      if (!p.resid_h || (p.ldc & 7) || (p.ldr & 7)) return RAP_ERR_INVALID;
-      return launch_variant<EPI_H_BIAS_RESID_H16, DT>(stream, p);
-    case EPI_H_GEGLU: return launch_variant<EPI_H_GEGLU, DT>(stream, p);
-    case EPI_H_QKV_NORM:
-      if (p.N != 3 * p.heads * 64 || !p.vt || p.vt_nblk * 64 < (p.M + 255) / 256 * 256 || !p.gamma_q || !p.gamma_k || p.K < 128) return RAP_ERR_INVALID;
-      if (use_persistent(p)) return launch_php<EPI_H_QKV_NORM, DT>(stream, p);
-      // few-token calls (fewer 256 x 256 tiles than CUs): the fused epilogue on 128 x 128 tiles (round 6; the r03 note in api.hip: GEMM + qk-norm as
-      // two kernels used to win there because the fused form existed only in the 256 x 256 kernels)
-      if ((long)((p.M + 255) / 256) * (p.N / 256) < 256) return launch_small<EPI_H_QKV_NORM, DT>(stream, p);
-      return launch_ph<EPI_H_QKV_NORM, DT, 0, 1>(stream, p);
-    case EPI_H_QKV:
-      if (p.N != 3 * p.heads * 64 || !p.vt || p.vt_nblk * 64 < (p.M + 255) / 256 * 256) return RAP_ERR_INVALID;
-      return launch_variant<EPI_H_QKV, DT>(stream, p);
-    default: return RAP_ERR_INVALID;
-  }
-}
-
 // Split precision (RAP_DT_F32X2): p.K, lda, ldw (and ldc of the GEGLU output) are PHYSICAL fp16 counts = 2 x the logical ones; p.N and the fp32
 // outputs are logical.  The three epilogues of the model path on the phase-split kernels (persistent where the shape allows); any M
 // (rows are clamped by the one-tile kernel), N % 256 == 0, K_physical >= 128.
 static bool use_persistent_x2(const GemmParamsH& p) {
   return g_rap_gemm_h16_persistent && p.M % 256 == 0 && p.K <= 8192 && (long)(p.M / 256) * (p.N / 256) >= 512 && p.lda <= (1 << 20) && p.ldw <= (1 << 20);
 }
-template <int EPI>
-static int launch_x2_variant(hipStream_t stream, const GemmParamsH& p) {
-  if (use_persistent_x2(p)) return launch_php<EPI, RAP_DT_F16, true>(stream, p);
-  return launch_ph<EPI, RAP_DT_F16, 0, 1, true>(stream, p);
+// Few-token calls.  Fewer 256 x 256 tiles than CUs: 128 x 128 tiles (two blocks per CU) fill the chip up to four times better -- one pair of
+// 2 x 1024 points x 10 steps 26.6 -> 21.6 ms in bf16, 2 x 4096 x 20 steps 102.5 -> 94.0 ms, unchanged from 4 pairs up (r03 call 31); in split
+// precision the N = 512 residual GEMMs below ~32 k tokens (64 tiles at 8 000 tokens), the QKV projection and ff1 below ~10 k / ~4 k.  The
+// long-K residual GEMM (ff2) of a call with at most 128 such tiles is a latency-bound chain per block: K is split over 2 / 4 blocks per tile
+// that write fp32 partial tiles (scaled, in split precision), and the combine pass forms residual + (bias + partials) in a fixed order
+// (gemm_h16_splits_by_shape, on the physical K in split precision; tuning key 6).
+static bool few_tiles(const GemmParamsH& p) { return (long)((p.M + 255) / 256) * (p.N / 256) < 256; }
+
+// The dispatch decision as host arithmetic (kernels.h: the form codes).  launch_gemm_h16 switches on the result;
+// tests/test_gemm_cases_host.py pins it through rap_gemm_h16_form.
+static int form_small(const GemmParamsH& p, int splits) { return rap_gemm_form(RAP_FORM_128, small_stages(p, splits), splits); }
+int gemm_h16_form(int dtype, int epilogue, const GemmParamsH& p, bool* planes_to_ws) {
+  if (planes_to_ws) *planes_to_ws = false;
+  if (p.M <= 0) return 0;
+  if (p.N % 128 != 0 || p.K % 64 != 0 || p.K <= 0) return RAP_ERR_INVALID;      // K % 64: two 32-wide ring slices / one 64-wide tile
+  if ((p.lda & 7) || (p.ldw & 7) || p.lda < p.K || p.ldw < p.K) return RAP_ERR_INVALID;
+  const bool x2 = dtype == RAP_DT_F32X2;
+  if (!x2 && dtype != RAP_DT_BF16 && dtype != RAP_DT_F16) return RAP_ERR_INVALID;
+  if (x2) {
+    if (p.N % 256 != 0 || p.K < 128) return RAP_ERR_INVALID;
+    if (epilogue != EPI_H_BIAS_RESID_F32 && epilogue != EPI_H_GEGLU && epilogue != EPI_H_QKV_NORM) return RAP_ERR_INVALID;
+  } else if (epilogue != EPI_H_BIAS && epilogue != EPI_H_BIAS_RESID_F32 && epilogue != EPI_H_BIAS_RESID_H16 && epilogue != EPI_H_GEGLU &&
+             epilogue != EPI_H_QKV && epilogue != EPI_H_QKV_NORM) {
+    return RAP_ERR_INVALID;
+  }
+  if (!x2 && epilogue == EPI_H_QKV_NORM && p.K < 128) return RAP_ERR_INVALID;
+  // split K (and the partial planes left for the caller's combine + LayerNorm pass: one plane when there is no split)
+  if ((epilogue == EPI_H_BIAS_RESID_F32 || epilogue == EPI_H_BIAS_RESID_H16) && p.splitk_ws) {
+    const int splits = p.force_splits > 0 ? p.force_splits : gemm_h16_splits(p.M, p.N, p.K);
+    if (splits < 1 || (p.K / 64) % splits != 0) return RAP_ERR_INVALID;
+    if (splits > 1 || p.defer_combine) {
+      if (planes_to_ws) *planes_to_ws = true;
+      return form_small(p, splits);
+    }
+  }
+  if (x2) {
+    if (few_tiles(p)) return form_small(p, 1);
+    return rap_gemm_form(use_persistent_x2(p) ? RAP_FORM_256P : RAP_FORM_256, 0, 1);
+  }
+  const bool big = p.N % 256 == 0 && p.K >= 128;
+#ifdef RAP_ABLATION_BUILD
+  if (epilogue != EPI_H_QKV_NORM) {
+    if (g_rap_gemm_h16_variant == 0) return rap_gemm_form(RAP_FORM_128, 2, 1);
+    if (g_rap_gemm_h16_variant == 1 && big) return rap_gemm_form(RAP_FORM_256_2S, 2, 1);
+  }
+#endif
+  // persistent form when every row tile is full and there are at least two rounds of tiles for a 256-CU part; the one-tile-per-block
+  // form for ragged M (it clamps rows); 128 x 128 tiles for shapes the phase-split kernel cannot tile (N % 256 != 0 or K < 128) and few tiles
+  // (the fused qk-norm exists on 128 x 128 tiles since round 6; the r03 note in api.hip: GEMM + qk-norm as two kernels used to win there
+  // because the fused form existed only in the 256 x 256 kernels)
+  if (big && use_persistent(p)) return rap_gemm_form(RAP_FORM_256P, 0, 1);
+  if (big && !few_tiles(p)) return rap_gemm_form(RAP_FORM_256, 0, 1);
+  return form_small(p, 1);
 }
-// Few-token split-precision calls.  Fewer 256 x 256 tiles than CUs: 128 x 128 tiles (two blocks per CU) fill the chip up to four times
-// better -- the N = 512 residual GEMMs below ~32 k tokens (64 tiles at 8 000 tokens), the QKV projection and ff1 below ~10 k / ~4 k.  The
-// long-K residual GEMM (ff2: 64 k-tiles of 64 physical columns) of a call with at most 128 such tiles is a latency-bound chain per block:
-// K is split over 2 / 4 blocks per tile that write scaled fp32 partial tiles, and the 16-bit path's combine pass forms
-// residual + (bias + partials) in a fixed order (gemm_h16_splits_by_shape on the physical K; tuning key 6).
-static bool x2_small(const GemmParamsH& p) { return (long)((p.M + 255) / 256) * (p.N / 256) < 256; }
-static int launch_x2_splitk(hipStream_t stream, const GemmParamsH& p, int splits) {
+
+template <int EPI, int DT, bool X2 = false>
+static int launch_form(hipStream_t stream, const GemmParamsH& p, int form) {
+  switch (form / 100) {
+    case RAP_FORM_256P: return launch_php<EPI, DT, X2>(stream, p);
+    case RAP_FORM_256: return launch_ph<EPI, DT, 0, 1, X2>(stream, p);
+    case RAP_FORM_128: return launch_small<EPI, DT, X2>(stream, p, (form / 10) % 10);
+#ifdef RAP_ABLATION_BUILD
+    case RAP_FORM_256_2S:
+      if constexpr (!X2 && EPI != EPI_H_QKV_NORM) return launch_cfg<EPI, DT, 2, 4, 4, 2>(stream, p);
+      return RAP_ERR_INVALID;
+#endif
+    default: return RAP_ERR_INVALID;
+  }
+}
+
+template <int DT>
+static int launch_dt(hipStream_t stream, int epilogue, const GemmParamsH& p, int form, bool planes_to_ws) {
+  if (planes_to_ws) {
+    if ((p.ldc & 7) || (p.ldr & 7) || (epilogue == EPI_H_BIAS_RESID_H16 && !p.resid_h)) return RAP_ERR_INVALID;
+    return launch_splitk<DT>(stream, epilogue, p, (form / 10) % 10, form % 10);
+  }
+  switch (epilogue) {
+    case EPI_H_BIAS: return launch_form<EPI_H_BIAS, DT>(stream, p, form);
+    case EPI_H_BIAS_RESID_F32: return launch_form<EPI_H_BIAS_RESID_F32, DT>(stream, p, form);
+    case EPI_H_BIAS_RESID_H16:
+      if (!p.resid_h || (p.ldc & 7) || (p.ldr & 7)) return RAP_ERR_INVALID;
+      return launch_form<EPI_H_BIAS_RESID_H16, DT>(stream, p, form);
+    case EPI_H_GEGLU: return launch_form<EPI_H_GEGLU, DT>(stream, p, form);
+    case EPI_H_QKV_NORM:
+      if (p.N != 3 * p.heads * 64 || !p.vt || p.vt_nblk * 64 < (p.M + 255) / 256 * 256 || !p.gamma_q || !p.gamma_k) return RAP_ERR_INVALID;
+      return launch_form<EPI_H_QKV_NORM, DT>(stream, p, form);
+    case EPI_H_QKV:
+      if (p.N != 3 * p.heads * 64 || !p.vt || p.vt_nblk * 64 < (p.M + 255) / 256 * 256) return RAP_ERR_INVALID;
+      return launch_form<EPI_H_QKV, DT>(stream, p, form);
+    default: return RAP_ERR_INVALID;
+  }
+}
+
+static int launch_x2_splitk(hipStream_t stream, const GemmParamsH& p, int stages, int splits) {
   GemmParamsH q = p;
   q.C = p.splitk_ws; q.ldc = p.N; q.bias = nullptr; q.resid = nullptr; q.splitk_ws = nullptr;      // (acc_scale stays: the partials are in true units)
-  if (int rc = launch_small<EPI_H_BIAS_RESID_F32, RAP_DT_F16, true>(stream, q, splits)) return rc;
+  if (int rc = launch_small<EPI_H_BIAS_RESID_F32, RAP_DT_F16, true>(stream, q, stages, splits)) return rc;
   if (p.defer_combine) return RAP_OK;
   const long n8 = (long)p.M * (p.N / 8);
   hipLaunchKernelGGL(gemm_h16_splitk_combine_kernel<false>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, p.splitk_ws, splits, p.M, p.N,
@@ -1473,43 +1510,34 @@ static int launch_x2_splitk(hipStream_t stream, const GemmParamsH& p, int splits
   RAP_LAUNCH_CHECK();
   return RAP_OK;
 }
-static int launch_x2(hipStream_t stream, int epilogue, const GemmParamsH& p) {
-  if (p.N % 256 != 0 || p.K < 128 || p.K % 64 != 0) return RAP_ERR_INVALID;
+static int launch_x2(hipStream_t stream, int epilogue, const GemmParamsH& p, int form, bool planes_to_ws) {
   switch (epilogue) {
     case EPI_H_BIAS_RESID_F32:
-      if (p.splitk_ws) {
-        const int splits = p.force_splits > 0 ? p.force_splits : gemm_h16_splits(p.M, p.N, p.K);
-        if (splits < 1 || (p.K / 64) % splits != 0) return RAP_ERR_INVALID;
-        if (splits > 1 || p.defer_combine) {
-          if ((p.ldc & 7) || (p.ldr & 7)) return RAP_ERR_INVALID;
-          return launch_x2_splitk(stream, p, splits);
-        }
+      if (planes_to_ws) {
+        if ((p.ldc & 7) || (p.ldr & 7)) return RAP_ERR_INVALID;
+        return launch_x2_splitk(stream, p, (form / 10) % 10, form % 10);
       }
-      if (x2_small(p)) return launch_small<EPI_H_BIAS_RESID_F32, RAP_DT_F16, true>(stream, p);
-      return launch_x2_variant<EPI_H_BIAS_RESID_F32>(stream, p);
+      return launch_form<EPI_H_BIAS_RESID_F32, RAP_DT_F16, true>(stream, p, form);
     case EPI_H_GEGLU:
       if (p.ldc & 7) return RAP_ERR_INVALID;
-      if (x2_small(p)) return launch_small<EPI_H_GEGLU, RAP_DT_F16, true>(stream, p);
-      return launch_x2_variant<EPI_H_GEGLU>(stream, p);
+      return launch_form<EPI_H_GEGLU, RAP_DT_F16, true>(stream, p, form);
     case EPI_H_QKV_NORM:
       if (p.N != 3 * p.heads * 64 || !p.vt || p.vt_nblk * 64 < (p.M + 255) / 256 * 256 || ((p.gamma_q == nullptr) != (p.gamma_k == nullptr))) return RAP_ERR_INVALID;
-      if (x2_small(p)) return launch_small<EPI_H_QKV_NORM, RAP_DT_F16, true>(stream, p);
-      return launch_x2_variant<EPI_H_QKV_NORM>(stream, p);
+      return launch_form<EPI_H_QKV_NORM, RAP_DT_F16, true>(stream, p, form);
     default: return RAP_ERR_INVALID;
   }
 }
 
 int launch_gemm_h16(hipStream_t stream, int dtype, int epilogue, const GemmParamsH& p) {
-  if (p.M <= 0) return RAP_OK;
-  if (p.N % 128 != 0 || p.K % 64 != 0 || p.K <= 0) return RAP_ERR_INVALID;      // K % 64: two 32-wide ring slices / one 64-wide tile
-  if ((p.lda & 7) || (p.ldw & 7) || p.lda < p.K || p.ldw < p.K) return RAP_ERR_INVALID;
+  bool planes_to_ws = false;
+  const int form = gemm_h16_form(dtype, epilogue, p, &planes_to_ws);
+  if (form <= 0) return form;      // nothing to do (M <= 0) or a refused shape
   // output / residual rows are stored as whole 16-byte pieces: four fp32 or eight 16-bit columns
   if (epilogue == EPI_H_BIAS_RESID_F32 && ((p.ldc & 3) || p.ldc < p.N || (p.resid && ((p.ldr & 3) || p.ldr < p.N)))) return RAP_ERR_INVALID;
   if ((epilogue == EPI_H_BIAS || epilogue == EPI_H_GEGLU) && (p.ldc & 7)) return RAP_ERR_INVALID;
-  if (dtype == RAP_DT_F32X2) return launch_x2(stream, epilogue, p);
-  if (dtype == RAP_DT_BF16) return launch_dt<RAP_DT_BF16>(stream, epilogue, p);
-  if (dtype == RAP_DT_F16) return launch_dt<RAP_DT_F16>(stream, epilogue, p);
-  return RAP_ERR_INVALID;
+  if (dtype == RAP_DT_F32X2) return launch_x2(stream, epilogue, p, form, planes_to_ws);
+  if (dtype == RAP_DT_BF16) return launch_dt<RAP_DT_BF16>(stream, epilogue, p, form, planes_to_ws);
+  return launch_dt<RAP_DT_F16>(stream, epilogue, p, form, planes_to_ws);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -39,6 +39,20 @@ struct GemmParams {
   int geglu_fast;  // set by launch_gemm_f32 (tuning key 9): 1 = GEGLU on the packed fp32 pipe with the 1.5e-7 erfc (half.h geglu_pairs), 0 = erff
 };
 int launch_gemm_f32(hipStream_t stream, int epilogue, const GemmParams& p);
+// The dispatch decision of a GEMM call as host arithmetic (include/rapflow.h: rap_gemm_f32_form / rap_gemm_h16_form): a FORM code
+// 100 * kernel + 10 * LDS stages + K splits, 0 when there is nothing to launch (M <= 0), RAP_ERR_INVALID for a refused shape.  The launchers
+// switch on it and derive nothing again.
+enum GemmFormKernel {
+  RAP_FORM_128 = 1,    // 128 x 128 tiles (stages: 2, or 4 for the 16-bit four-stage ring; the only kernel that splits K)
+  RAP_FORM_256 = 2,    // 256 x 256, one tile per block (rows clamped, stores predicated: any M); stages reported as 0
+  RAP_FORM_256P = 3,   // 256 x 256, persistent: one block per CU walks its share of the tiles (M % 256 == 0); stages reported as 0
+  RAP_FORM_256_2S = 4, // RAP_ABLATION_BUILD only: the two-stage 256 x 256 kernel of the 16-bit path
+};
+static inline int rap_gemm_form(int kernel, int stages, int splits) { return 100 * kernel + 10 * stages + splits; }
+int gemm_f32_form(int epilogue, const GemmParams& p);       // reads M, N, K, lda, ldw, ldc, ldr, splitk_ws (given or not), splitk_planes
+// the K splits of the fp32 few-row rule from the shape alone (tuning key 6 and the strides gate the launch, not a reservation): 4 for bias +
+// residual, `planes` (2 or 4) for bias + SiLU, 1 = no split
+int gemm_f32_splits_by_shape(int epilogue, int M, int N, int K, int planes);
 
 // ---------------------------------------------------------------------------------------------
 // K7: variable-length, non-causal softmax attention on head-major q/k/v ([3][H][TP][64] fp32).
@@ -156,6 +170,10 @@ int gemm_h16_splits(int M, int N, int K);
 // the same rule without tuning key 6: what a workspace has to reserve (the key only gates the launch)
 int gemm_h16_splits_by_shape(int M, int N, int K);
 int launch_gemm_h16(hipStream_t stream, int dtype, int epilogue, const GemmParamsH& p);
+// the form code (above) of a 16-bit / split-precision call: reads M, N, K, lda, ldw, splitk_ws (given or not), force_splits, defer_combine
+// *planes_to_ws (optional): the GEMM leaves fp32 partial planes in splitk_ws -- K is split, or defer_combine asks for the one plane of an
+// unsplit call -- instead of running its epilogue (the one thing the code cannot say: a deferred unsplit call has the code of a plain one)
+int gemm_h16_form(int dtype, int epilogue, const GemmParamsH& p, bool* planes_to_ws = nullptr);
 int launch_convert_h16(hipStream_t stream, int dtype, const float* src, uint16_t* dst, size_t n);
 // attention on q,k half [2][H][TP][64] + transposed-blocked v (vt); out half (TP, H*64)
 // bound: optional per-head upper bounds (device, H floats) on the logits q.k/8 -- enables the bounded-softmax kernel (bf16)

@@ -34,6 +34,19 @@ int main(void) {
   if (rap_x2_attention_split((const uint16_t*)sentinel, (const uint16_t*)sentinel, 4, (const int32_t*)sentinel, 1, (uint16_t*)sentinel, 256, 257, 8, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("x2 split attention n_tokens above TP\n"); ++fails; }
   if (rap_x2_attention_split((const uint16_t*)sentinel, (const uint16_t*)sentinel, 3, (const int32_t*)sentinel, 1, (uint16_t*)sentinel, 256, 0, 8, 2, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("x2 split attention short V^T image\n"); ++fails; }
   if (rap_x2_attention_split((const uint16_t*)sentinel, (const uint16_t*)sentinel, 4, (const int32_t*)sentinel, 1, (uint16_t*)sentinel, 256, 0, 8, 4, sentinel, rap_attention_split_workspace_bytes(256, 1, 8, 4) - 1, NULL) != RAP_ERR_WORKSPACE) { printf("x2 split attention short workspace\n"); ++fails; }
+  /* the GEMM dispatch decision and the fp32 split-K entry point: host arithmetic, refusals before any launch */
+  if (rap_gemm_f32_form(0, 300, 512, 512, 512, 512, 512, 0, 0, 0) != 121 || rap_gemm_f32_form(0, 16129, 2048, 256, 256, 256, 2048, 0, 0, 0) != 201 ||
+      rap_gemm_f32_form(0, 16384, 2048, 256, 256, 256, 2048, 0, 0, 0) != 301 || rap_gemm_f32_form(1, 2048, 512, 512, 512, 512, 512, 512, 1, 0) != 124 ||
+      rap_gemm_f32_form(0, 300, 500, 512, 512, 512, 500, 0, 0, 0) != RAP_ERR_INVALID || rap_gemm_f32_form(0, 0, 512, 512, 512, 512, 512, 0, 0, 0) != 0) { printf("fp32 gemm form\n"); ++fails; }
+  if (rap_gemm_h16_form(1, 0, 300, 256, 512, 512, 512, 0) != 141 || rap_gemm_h16_form(2, 0, 8200, 512, 64, 64, 64, 0) != 121 ||
+      rap_gemm_h16_form(1, 0, 7937, 2048, 128, 128, 128, 0) != 201 || rap_gemm_h16_form(3, 1, 16384, 2048, 128, 128, 128, 0) != 301 ||
+      rap_gemm_h16_form(1, 1, 2048, 512, 1024, 1024, 1024, 1) != 144 || rap_gemm_h16_form(1, 6, 300, 256, 512, 512, 512, 0) != RAP_ERR_INVALID) { printf("16-bit gemm form\n"); ++fails; }
+  if (rap_gemm_f32_splitk_workspace_bytes(1, 2048, 512, 544, 0) != (size_t)4 * 2048 * 512 * 4 || rap_gemm_f32_splitk_workspace_bytes(1, 2049, 512, 544, 0) != 0 ||
+      rap_gemm_f32_splitk_workspace_bytes(2, 257, 384, 576, 2) != (size_t)2 * 257 * 384 * 4 || rap_gemm_f32_splitk_workspace_bytes(2, 257, 384, 544, 2) != 0) { printf("fp32 split-K workspace query\n"); ++fails; }
+  if (rap_gemm_f32_splitk(1, NULL, 512, (const float*)sentinel, 512, (float*)sentinel, 512, 100, 512, 512, NULL, (const float*)sentinel, 512, 0, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("fp32 split-K NULL A\n"); ++fails; }
+  if (rap_gemm_f32_splitk(0, (const float*)sentinel, 512, (const float*)sentinel, 512, (float*)sentinel, 512, 100, 512, 512, NULL, (const float*)sentinel, 512, 0, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("fp32 split-K epilogue 0\n"); ++fails; }
+  if (rap_gemm_f32_splitk(2, (const float*)sentinel, 512, (const float*)sentinel, 512, (float*)sentinel, 128, 100, 128, 512, NULL, NULL, 0, 3, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("fp32 split-K planes 3\n"); ++fails; }
+  if (rap_gemm_f32_splitk(1, (const float*)sentinel, 512, (const float*)sentinel, 512, (float*)sentinel, 512, 100, 512, 512, NULL, (const float*)sentinel, 512, 0, sentinel, (size_t)4 * 100 * 512 * 4 - 1, NULL) != RAP_ERR_WORKSPACE) { printf("fp32 split-K short workspace\n"); ++fails; }
   if (rap_model_set_compute_dtype(NULL, 3, NULL) != RAP_ERR_INVALID) { printf("NULL model\n"); ++fails; }
   printf("c consumer: %d failure(s), ABI version %d\n", fails, rap_version());
   return fails;

@@ -196,6 +196,12 @@ def test_splitk_rule_of_the_16bit_residual_gemm_is_host_arithmetic():
     assert q(100, 1024, 4096) == 4 * plane(100, 1024)          # d = 1024 models
     assert q(100, 576, 2048) == 0                              # N not a multiple of 128
     assert q(0, 512, 2048) == 0 and q(-5, 512, 2048) == 0
+    # both edges of the rule at the shortest K it takes, at 20 k-tiles, and at 17 (not a multiple of 4: never split) -- the rows of the
+    # split-K sweep of tests/test_gemm_edges_gpu.py
+    for K, on in ((1024, True), (1280, True), (1088, False), (960, False)):
+        assert q(1, 512, K) == (4 * plane(1, 512) if on else 0), K
+        assert q(2048, 512, K) == (4 * plane(2048, 512) if on else 0) and q(2049, 512, K) == (2 * plane(2049, 512) if on else 0), K      # 64 | 68 tiles
+        assert q(4096, 512, K) == (2 * plane(4096, 512) if on else 0) and q(4097, 512, K) == 0, K                                        # 128 | 132 tiles
     try:
         assert lib.rap_set_tuning(6, 0) == 0
         assert q(2048, 512, 2048) == 4 * plane(2048, 512)      # still reserved: the key only gates the launch

@@ -258,3 +258,50 @@ def test_model_entry_points_refuse_a_short_workspace_without_writing(dev):
     for g in guards:
         g.check()
         assert g.untouched(), g.name
+
+
+# ---------------------------------------------------------------------------------------------
+# rap_gemm_f32_splitk at exactly rap_gemm_f32_splitk_workspace_bytes
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("epi,planes", [(1, 0), (2, 2), (2, 4)], ids=["resid", "silu-2-planes", "silu-4-planes"])
+def test_gemm_f32_splitk_stays_inside_its_exact_workspace(dev, epi, planes):
+    """The fp32 split-K entry point (kernel-level, like tests/test_guards_gpu.py: every output and the workspace between guard bytes, every
+    input between 0x00 and then 0xFF neighbours) over the row counts of that file: the partial planes fill the reported workspace exactly
+    -- 17 k-tiles over 4 blocks for the residual form, so the last share is the long one -- and one byte less is refused with nothing
+    written."""
+    import ctypes
+    import torch.nn.functional as F
+    import test_guards_gpu as TG
+    import test_kernels_gpu as TK
+    lib = _lib.load()
+    N, K = (512, 544) if epi == 1 else (384, 512)
+    for M in TG.MS:
+        need = lib.rap_gemm_f32_splitk_workspace_bytes(epi, M, N, K, planes)
+        assert need == (4 if epi == 1 else planes) * M * N * 4
+        g = torch.Generator().manual_seed(47 + M)
+        A = torch.randn(M, K, generator=g); W = torch.randn(N, K, generator=g) / K ** 0.5
+        bias = torch.randn(N, generator=g); h = torch.randn(M, N, generator=g)
+        u = A.double() @ W.double().T + bias.double()
+        ref = h.double() + u if epi == 1 else F.silu(u)
+
+        def call(c, ws_bytes):
+            C = c.out_view(torch.float32, (M, N), "C")
+            ws = c.out(need, pitch=N * 4, name="split-K workspace")
+            Ad, Wd, bd = c.inp(A, "A"), c.inp(W, "W"), c.inp(bias, "bias")
+            hd = c.inp(h, "resid") if epi == 1 else None
+            rc = lib.rap_gemm_f32_splitk(epi, _lib.ptr(Ad), K, _lib.ptr(Wd), K, _lib.ptr(C), N, M, N, K, _lib.ptr(bd), _lib.ptr(hd), N if epi == 1 else 0,
+                                         planes, ctypes.c_void_p(ws.ptr), ws_bytes, _lib.current_stream(dev))
+            torch.cuda.synchronize()
+            return rc, C
+
+        def run(c):
+            rc, C = call(c, need)
+            assert rc == 0
+            assert (C.cpu().double() - ref).abs().max().item() < TK.GEMM_BOUND, M          # NaN (an element never written) fails this too
+            return [C]
+        TG.run_both(dev, run)
+        c = TG.Case(dev, 0x00)                                                      # one byte short: refused, nothing written
+        rc, C = call(c, need - 1)
+        assert rc == TG.RAP_ERR_WORKSPACE
+        c.check()
+        assert bool(torch.isnan(C).all())
