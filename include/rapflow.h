@@ -513,6 +513,31 @@ int rap_layernorm_mod_h16(int32_t dtype, const float* x, uint16_t* out, int64_t 
                           int64_t mod_stride, const int32_t* token_row, void* stream);
 int rap_layernorm_affine_h16(int32_t dtype, const float* x, uint16_t* out, int64_t TP, int32_t d, const float* gain,
                              const float* shift, void* stream);
+/* Kernel-level access to the residual-stream side of the 16-bit block, for the parity tests (no kernel of their own).
+ * rap_layernorm_mod_h16_stream / rap_layernorm_affine_h16_stream: the two calls above with the residual-stream dtype exposed: x is fp32
+ *   (TP, d) when x_f16 = 0 -- then they ARE the calls above, bit for bit -- or fp16 (TP, d) when x_f16 = 1 (dtype 1, 2 only).
+ * rap_resid_combine_layernorm_h16: the combine pass of a split-K residual GEMM and the LayerNorm that follows it in one launch, as few-token
+ *   model calls run them (tuning key 19).  part: `splits` (1..8) fp32 planes [splits][rows][d]; bias: d floats or NULL; h: the residual
+ *   stream (rows, d), fp32 (h_f16 = 0) or fp16 (h_f16 = 1; dtype 1, 2 only), updated IN PLACE:
+ *     h = ((0 + part[0] + part[1] + ...) + bias) + h   in fp32, in this order; an fp16 stream takes ONE rounding of that sum, saturating at
+ *     +-65504 (+-inf -> +-65504, NaN stays NaN);
+ *   out = LayerNorm of the STORED h (eps 1e-5), modulated as rap_layernorm_mod_h16 does when mod != NULL (mod_stride, token_row as there),
+ *   else affine with gain and shift (both required then) -- bit-identical to the combine pass followed by the plain LayerNorm.  out is
+ *   (rows, d) in the operand type, (rows, 2 d) paired for dtype 3.  Nothing but h[:rows] and out[:rows] is written.
+ * rap_convert_f16_sat: dst fp16 [n] = round-to-nearest-even(clamp(src fp32 [n], -65504, 65504)), NaN stays NaN; n % 4 == 0.
+ * rap_convert_f16_to_f32: dst fp32 [n] = src fp16 [n], exact (a signalling NaN leaves quiet, payload kept); n % 8 == 0.
+ * Refused with RAP_ERR_INVALID before any launch, WHATEVER the row count: a NULL required operand; dtype outside 1..3; dtype 3 with an fp16
+ * stream; x_f16 / h_f16 outside {0, 1}; d not one of 256, 512, 768, 1024; splits outside 1..8; neither mod nor both of gain and shift;
+ * a negative row count or n; n % 4 != 0 (sat) / n % 8 != 0 (to_f32).  rows = 0 / n = 0 with valid arguments: RAP_OK, nothing written. */
+int rap_layernorm_mod_h16_stream(int32_t dtype, const void* x, int32_t x_f16, uint16_t* out, int64_t TP, int32_t d, const float* mod,
+                                 int64_t mod_stride, const int32_t* token_row, void* stream);
+int rap_layernorm_affine_h16_stream(int32_t dtype, const void* x, int32_t x_f16, uint16_t* out, int64_t TP, int32_t d, const float* gain,
+                                    const float* shift, void* stream);
+int rap_resid_combine_layernorm_h16(int32_t dtype, const float* part, int32_t splits, const float* bias, void* h, int32_t h_f16,
+                                    uint16_t* out, int64_t rows, int32_t d, const float* mod, int64_t mod_stride, const int32_t* token_row,
+                                    const float* gain, const float* shift, void* stream);
+int rap_convert_f16_sat(const float* src, uint16_t* dst, int64_t n, void* stream);
+int rap_convert_f16_to_f32(const uint16_t* src, float* dst, int64_t n, void* stream);
 int rap_qknorm_h16(int32_t dtype, uint16_t* qk, int64_t TP, int32_t heads, const float* gamma_q, const float* gamma_k,
                    void* stream);
 

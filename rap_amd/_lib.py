@@ -132,6 +132,11 @@ SIGNATURES = {
     "rap_attention_h16": (c_int32, [c_int32, _P, _P, c_int32, _P, c_int32, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
     "rap_layernorm_mod_h16": (c_int32, [c_int32, _P, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "rap_layernorm_affine_h16": (c_int32, [c_int32, _P, _P, c_int64, c_int32, _P, _P, _P]),
+    "rap_layernorm_mod_h16_stream": (c_int32, [c_int32, _P, c_int32, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
+    "rap_layernorm_affine_h16_stream": (c_int32, [c_int32, _P, c_int32, _P, c_int64, c_int32, _P, _P, _P]),
+    "rap_resid_combine_layernorm_h16": (c_int32, [c_int32, _P, c_int32, _P, _P, c_int32, _P, c_int64, c_int32, _P, c_int64, _P, _P, _P, _P]),
+    "rap_convert_f16_sat": (c_int32, [_P, _P, c_int64, _P]),
+    "rap_convert_f16_to_f32": (c_int32, [_P, _P, c_int64, _P]),
     "rap_qknorm_h16": (c_int32, [c_int32, _P, c_int64, c_int32, _P, _P, _P]),
     "rap_x2_pack": (c_int32, [_P, c_int64, c_int64, c_int32, c_float, _P, _P]),
     "rap_x2_unpack": (c_int32, [_P, c_int64, c_int32, c_float, _P, _P]),

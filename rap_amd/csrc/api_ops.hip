@@ -226,6 +226,42 @@ extern "C" int rap_layernorm_affine_h16(int32_t dtype, const float* x, uint16_t*
   if (!x || !out || !gain || !shift) return RAP_ERR_INVALID;
   return launch_layernorm_affine_h16((hipStream_t)stream, dtype, x, 0, out, (int)TP, d, gain, shift);
 }
+// The same two kernels with the residual-stream dtype exposed, the fused combine + LayerNorm of few-token calls (tuning key 19) and the
+// two stream conversions, for the parity tests.  The launchers answer RAP_OK to an empty row count before they look at anything else:
+// every argument is checked HERE, whatever the row count.
+static bool ln_stream_args_ok(int32_t dtype, int32_t stream_f16, int64_t rows, int32_t d) {
+  if (dtype != RAP_DT_BF16 && dtype != RAP_DT_F16 && dtype != RAP_DT_F32X2) return false;
+  if (stream_f16 != 0 && stream_f16 != 1) return false;
+  if (dtype == RAP_DT_F32X2 && stream_f16) return false;      // the split mode keeps the residual stream in fp32
+  if (d != 256 && d != 512 && d != 768 && d != 1024) return false;
+  return rows >= 0 && rows <= 0x7fffffffLL - 3;                // the launchers take the row count as an int and round it up to 4
+}
+extern "C" int rap_layernorm_mod_h16_stream(int32_t dtype, const void* x, int32_t x_f16, uint16_t* out, int64_t TP, int32_t d,
+                                            const float* mod, int64_t mod_stride, const int32_t* token_row, void* stream) {
+  if (!x || !out || !mod || !ln_stream_args_ok(dtype, x_f16, TP, d)) return RAP_ERR_INVALID;
+  return launch_layernorm_mod_h16((hipStream_t)stream, dtype, x, x_f16, out, (int)TP, d, mod, (long)mod_stride, token_row);
+}
+extern "C" int rap_layernorm_affine_h16_stream(int32_t dtype, const void* x, int32_t x_f16, uint16_t* out, int64_t TP, int32_t d,
+                                               const float* gain, const float* shift, void* stream) {
+  if (!x || !out || !gain || !shift || !ln_stream_args_ok(dtype, x_f16, TP, d)) return RAP_ERR_INVALID;
+  return launch_layernorm_affine_h16((hipStream_t)stream, dtype, x, x_f16, out, (int)TP, d, gain, shift);
+}
+extern "C" int rap_resid_combine_layernorm_h16(int32_t dtype, const float* part, int32_t splits, const float* bias, void* h, int32_t h_f16,
+                                               uint16_t* out, int64_t rows, int32_t d, const float* mod, int64_t mod_stride,
+                                               const int32_t* token_row, const float* gain, const float* shift, void* stream) {
+  if (!part || !h || !out || splits < 1 || splits > 8 || !ln_stream_args_ok(dtype, h_f16, rows, d)) return RAP_ERR_INVALID;
+  if (!mod && (!gain || !shift)) return RAP_ERR_INVALID;
+  return launch_resid_combine_ln_h16((hipStream_t)stream, dtype, part, splits, bias, h, h_f16, out, (int)rows, d, mod, (long)mod_stride,
+                                     token_row, gain, shift);
+}
+extern "C" int rap_convert_f16_sat(const float* src, uint16_t* dst, int64_t n, void* stream) {
+  if (!src || !dst || n < 0 || n % 4 != 0) return RAP_ERR_INVALID;
+  return launch_convert_f16_sat((hipStream_t)stream, src, dst, (size_t)n);
+}
+extern "C" int rap_convert_f16_to_f32(const uint16_t* src, float* dst, int64_t n, void* stream) {
+  if (!src || !dst || n < 0 || n % 8 != 0) return RAP_ERR_INVALID;
+  return launch_convert_f16_to_f32((hipStream_t)stream, src, dst, (size_t)n);
+}
 extern "C" int rap_qknorm_h16(int32_t dtype, uint16_t* qk, int64_t TP, int32_t heads, const float* gamma_q,
                               const float* gamma_k, void* stream) {
   if (!qk || !gamma_q || !gamma_k) return RAP_ERR_INVALID;

@@ -47,6 +47,24 @@ int main(void) {
   if (rap_gemm_f32_splitk(0, (const float*)sentinel, 512, (const float*)sentinel, 512, (float*)sentinel, 512, 100, 512, 512, NULL, (const float*)sentinel, 512, 0, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("fp32 split-K epilogue 0\n"); ++fails; }
   if (rap_gemm_f32_splitk(2, (const float*)sentinel, 512, (const float*)sentinel, 512, (float*)sentinel, 128, 100, 128, 512, NULL, NULL, 0, 3, sentinel, (size_t)1 << 30, NULL) != RAP_ERR_INVALID) { printf("fp32 split-K planes 3\n"); ++fails; }
   if (rap_gemm_f32_splitk(1, (const float*)sentinel, 512, (const float*)sentinel, 512, (float*)sentinel, 512, 100, 512, 512, NULL, (const float*)sentinel, 512, 0, sentinel, (size_t)4 * 100 * 512 * 4 - 1, NULL) != RAP_ERR_WORKSPACE) { printf("fp32 split-K short workspace\n"); ++fails; }
+  /* the residual-stream LayerNorm / fused combine + LayerNorm / stream conversion entry points: every argument is checked before any
+   * launch, an empty row count included (the launchers behind them would answer RAP_OK to 0 rows without looking at d) */
+  if (rap_layernorm_mod_h16_stream(2, NULL, 1, (uint16_t*)sentinel, 4, 512, (const float*)sentinel, 0, NULL, NULL) != RAP_ERR_INVALID) { printf("stream LN NULL x\n"); ++fails; }
+  if (rap_layernorm_mod_h16_stream(3, sentinel, 1, (uint16_t*)sentinel, 4, 512, (const float*)sentinel, 0, NULL, NULL) != RAP_ERR_INVALID) { printf("stream LN dtype 3 on an fp16 stream\n"); ++fails; }
+  if (rap_layernorm_mod_h16_stream(2, sentinel, 1, (uint16_t*)sentinel, 0, 384, (const float*)sentinel, 0, NULL, NULL) != RAP_ERR_INVALID) { printf("stream LN d 384 at 0 rows\n"); ++fails; }
+  if (rap_layernorm_affine_h16_stream(1, sentinel, 2, (uint16_t*)sentinel, 4, 512, (const float*)sentinel, (const float*)sentinel, NULL) != RAP_ERR_INVALID) { printf("stream LN x_f16 2\n"); ++fails; }
+  if (rap_layernorm_affine_h16_stream(1, sentinel, 0, (uint16_t*)sentinel, 4, 512, (const float*)sentinel, NULL, NULL) != RAP_ERR_INVALID) { printf("stream LN NULL shift\n"); ++fails; }
+  if (rap_layernorm_affine_h16_stream(0, sentinel, 0, (uint16_t*)sentinel, 0, 512, (const float*)sentinel, (const float*)sentinel, NULL) != RAP_ERR_INVALID) { printf("stream LN dtype 0 at 0 rows\n"); ++fails; }
+  if (rap_resid_combine_layernorm_h16(2, NULL, 2, NULL, sentinel, 1, (uint16_t*)sentinel, 4, 512, (const float*)sentinel, 0, NULL, NULL, NULL, NULL) != RAP_ERR_INVALID) { printf("combine LN NULL part\n"); ++fails; }
+  if (rap_resid_combine_layernorm_h16(2, (const float*)sentinel, 9, NULL, sentinel, 1, (uint16_t*)sentinel, 0, 512, (const float*)sentinel, 0, NULL, NULL, NULL, NULL) != RAP_ERR_INVALID) { printf("combine LN splits 9 at 0 rows\n"); ++fails; }
+  if (rap_resid_combine_layernorm_h16(2, (const float*)sentinel, 0, NULL, sentinel, 1, (uint16_t*)sentinel, 4, 512, (const float*)sentinel, 0, NULL, NULL, NULL, NULL) != RAP_ERR_INVALID) { printf("combine LN splits 0\n"); ++fails; }
+  if (rap_resid_combine_layernorm_h16(2, (const float*)sentinel, 2, NULL, sentinel, 1, (uint16_t*)sentinel, 4, 512, NULL, 0, NULL, (const float*)sentinel, NULL, NULL) != RAP_ERR_INVALID) { printf("combine LN neither mod nor gain and shift\n"); ++fails; }
+  if (rap_resid_combine_layernorm_h16(3, (const float*)sentinel, 2, NULL, sentinel, 1, (uint16_t*)sentinel, 4, 512, (const float*)sentinel, 0, NULL, NULL, NULL, NULL) != RAP_ERR_INVALID) { printf("combine LN dtype 3 on an fp16 stream\n"); ++fails; }
+  if (rap_resid_combine_layernorm_h16(2, (const float*)sentinel, 2, NULL, sentinel, 1, (uint16_t*)sentinel, -1, 512, (const float*)sentinel, 0, NULL, NULL, NULL, NULL) != RAP_ERR_INVALID) { printf("combine LN negative rows\n"); ++fails; }
+  if (rap_convert_f16_sat(NULL, (uint16_t*)sentinel, 8, NULL) != RAP_ERR_INVALID || rap_convert_f16_sat((const float*)sentinel, (uint16_t*)sentinel, 6, NULL) != RAP_ERR_INVALID ||
+      rap_convert_f16_sat((const float*)sentinel, (uint16_t*)sentinel, -4, NULL) != RAP_ERR_INVALID) { printf("saturating conversion\n"); ++fails; }
+  if (rap_convert_f16_to_f32((const uint16_t*)sentinel, NULL, 8, NULL) != RAP_ERR_INVALID || rap_convert_f16_to_f32((const uint16_t*)sentinel, (float*)sentinel, 12, NULL) != RAP_ERR_INVALID ||
+      rap_convert_f16_to_f32((const uint16_t*)sentinel, (float*)sentinel, -8, NULL) != RAP_ERR_INVALID) { printf("fp16 -> fp32 conversion\n"); ++fails; }
   if (rap_model_set_compute_dtype(NULL, 3, NULL) != RAP_ERR_INVALID) { printf("NULL model\n"); ++fails; }
   printf("c consumer: %d failure(s), ABI version %d\n", fails, rap_version());
   return fails;

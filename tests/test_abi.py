@@ -217,3 +217,27 @@ def test_splitk_rule_of_the_16bit_residual_gemm_is_host_arithmetic():
     assert lib.rap_gemm_h16(1, 6, one, 512, one, 512, one, 512, 256, 512, 512, N, one, 512, 0, N, 0, N) == -1
     assert lib.rap_version() == _lib.ABI_VERSION == 6
     assert lib.rap_poison_on_flag(N, one, 4, N) == -1 and lib.rap_poison_on_flag(one, N, 4, N) == -1
+
+
+def test_residual_stream_entry_points_check_every_argument_before_the_row_count():
+    """rap_layernorm_*_h16_stream, rap_resid_combine_layernorm_h16 and the two stream conversions sit over launchers that answer RAP_OK to an
+    empty call before they look at anything else: the entry points refuse a bad argument at 0 rows as at 4, and with x_f16 = 0 they take
+    exactly the arguments of rap_layernorm_*_h16 (tests/test_ln_stream_cases_host.py walks the whole list of refusals)."""
+    import ctypes
+    from rap_amd import _lib
+    lib = _lib.load()
+    N, one = ctypes.c_void_p(0), ctypes.c_void_p(256)
+    for rows in (4, 0):
+        assert lib.rap_layernorm_mod_h16_stream(2, one, 1, one, rows, 384, one, 0, N, N) == -1                 # d
+        assert lib.rap_layernorm_mod_h16_stream(3, one, 1, one, rows, 512, one, 0, N, N) == -1                 # split mode, fp16 stream
+        assert lib.rap_layernorm_affine_h16_stream(1, one, 2, one, rows, 512, one, one, N) == -1               # x_f16
+        assert lib.rap_layernorm_affine_h16_stream(1, one, 0, one, rows, 512, one, N, N) == -1                 # NULL shift
+        assert lib.rap_resid_combine_layernorm_h16(2, one, 9, N, one, 1, one, rows, 512, one, 0, N, N, N, N) == -1      # splits
+        assert lib.rap_resid_combine_layernorm_h16(2, one, 2, N, one, 1, one, rows, 512, N, 0, N, one, N, N) == -1      # gain without shift
+        assert lib.rap_resid_combine_layernorm_h16(4, one, 2, N, one, 0, one, rows, 512, one, 0, N, N, N, N) == -1      # dtype
+    assert lib.rap_layernorm_mod_h16_stream(1, one, 0, one, 0, 1024, one, 0, N, N) == 0
+    assert lib.rap_resid_combine_layernorm_h16(3, one, 8, N, one, 0, one, 0, 256, N, 0, N, one, one, N) == 0
+    assert lib.rap_convert_f16_sat(one, one, 6, N) == -1 and lib.rap_convert_f16_to_f32(one, one, 12, N) == -1
+    assert lib.rap_convert_f16_sat(one, one, -4, N) == -1 and lib.rap_convert_f16_to_f32(N, one, 0, N) == -1
+    assert lib.rap_convert_f16_sat(one, one, 0, N) == 0 and lib.rap_convert_f16_to_f32(one, one, 0, N) == 0
+    assert lib.rap_version() == _lib.ABI_VERSION == 6          # kernel-level additions for the parity tests leave the ABI version alone
