@@ -578,9 +578,11 @@ int rap_x2_attention_split(const uint16_t* qk, const uint16_t* vt, int32_t vt_nb
  * |coordinate| -- then global centring; per part the centred cloud (cond), its pose (R = I, t = centroid; anchor: t = -gt_trans),
  * the anchor masks, and the collated cu_seqlens.  fp64 arithmetic like numpy, fp32 results.
  *   points (TP,3) fp32 or fp64 (points_are_f64), parts of a sample contiguous, samples contiguous; points_per_part (B,P) int64 on
- *   the device, 0 = padding; every sample needs at least one point.
+ *   the device, 0 = padding (anywhere in the row: zero rotation / translation rows, never the anchor); every sample needs at least
+ *   one point to be usable -- one without any gets scale 0, global translation 0, zero rows and no anchor, and does not disturb the others.
  *   order: NULL, or (TP,) int64 -- for every output point its source index INSIDE its part (what np.random.permutation returned
- *   for that part, dataset.py:819); order_flag: NULL or a device int32 the call ORs 1 into when an index is out of range.
+ *   for that part, dataset.py:819); order_flag: NULL or a device int32 the call ORs 1 into when an index is out of range (such an
+ *   index is clamped into its part before it is used: the outputs are then not a permutation, but nothing outside the part is read).
  *   outputs: cond, gt (TP,3) f32; feat_out (TP,F) f32 (feat_in gathered the same way; F may be 0); anchor_indices (TP,) u8;
  *   part_indices (TP,) i64; rotations (B,P,3,3), translations (B,P,3), scales (B,), anchor_parts (B,P) u8,
  *   global_translation (B,3) f32 (mean of the raw sample, original units), cu_seqlens (B+1,) i64.

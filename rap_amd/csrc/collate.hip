@@ -10,6 +10,8 @@
 //   per part     trans_i = centroid of the part in that frame, cond = pts_gt - trans_i, shuffled inside the part with the caller's
 //                permutation (:802-830; np.random.permutation in the reference); the anchor (= primary) part keeps its pose:
 //                cond = pts_gt + gt_trans, trans = -gt_trans (:860-870); rotations = I, zero rows for padded parts (pad_data)
+// An empty part may sit anywhere in a sample's row: zero rotation / translation rows, never the anchor.  A sample without any point
+// gets scale 0, global translation 0, zero rows, no anchor and a repeated cu_seqlens entry; the other samples are not affected.
 // Arithmetic is fp64 like numpy's and cast to fp32 at the end, so the result differs from the reference's only through the
 // summation order of the means (1e-16 relative) -- far below one fp32 rounding.
 // Kernels: HBM-bound, 12 or 24 B read per point per pass, three passes over the points (part sums, primary-part extent, apply).
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(COL_THREADS) void collate_frame_kernel(const void* 
       cx = (psum[3 * part] * inv - px) / scale - qx; cy = (psum[3 * part + 1] * inv - py) / scale - qy; cz = (psum[3 * part + 2] * inv - pz) / scale - qz;
     }
     ptrans[3 * part] = cx; ptrans[3 * part + 1] = cy; ptrans[3 * part + 2] = cz;
-    const bool anch = i == primary;
+    const bool anch = i == primary && n > 0;            // a sample without any point has no anchor: all of its parts are padding
     float* R = rotations + 9 * (size_t)part; float* t = translations + 3 * (size_t)part;
     for (int k = 0; k < 9; ++k) R[k] = (n > 0 && (k == 0 || k == 4 || k == 8)) ? 1.f : 0.f;
     t[0] = n > 0 ? (anch ? (float)(-qx) : (float)cx) : 0.f;
@@ -136,7 +138,12 @@ __global__ __launch_bounds__(COL_THREADS) void collate_apply_kernel(const void* 
   }
   const int part = lo, b = part / P, i = part - b * P;
   const int a = off[part];
-  const long src = order ? (long)a + (long)order[j] : j;
+  long src = j;
+  if (order) {                          // an index outside the part is reported by collate_check_order_kernel; it must not be read through
+    const long n = (long)off[part + 1] - a;
+    const long o = (long)order[j];
+    src = (long)a + (o < 0 ? 0 : o >= n ? n - 1 : o);
+  }
   const double* f = frame + 8 * b;
   const double3 p = load_pt(pts, f64, src);
   const double scale = f[3];
