@@ -455,6 +455,10 @@ int rap_attention_f32(const float* qkv_headmajor, const int32_t* cu_seqlens, int
 size_t rap_attention_split_workspace_bytes(int64_t TP, int32_t nseg, int32_t heads, int32_t splits);
 int rap_attention_f32_split(const float* qkv_headmajor, const int32_t* cu_seqlens, int32_t nseg, float* out, int64_t TP,
                             int32_t heads, const float* logit_bound, int32_t splits, void* ws, size_t ws_bytes, void* stream);
+/* The fp32 kernels that run between the GEMMs of a flow step.  Every argument is checked before any launch, whatever the row count:
+ * RAP_ERR_INVALID for a NULL required operand, a negative row count or one that does not fit the launchers' int (never truncated), d not
+ * one of 256, 512, 768, 1024, heads <= 0, feat_dim outside {0, 4, ..., 40} or feat == NULL with feat_dim > 0, inner <= 0 / inner % 32 != 0 /
+ * K <= 0 for rap_geglu_interleave.  Zero rows with valid arguments: RAP_OK, nothing written. */
 int rap_layernorm_mod(const float* x, float* out, int64_t TP, int32_t d, const float* mod, int64_t mod_stride,
                       const int32_t* token_row, void* stream);
 int rap_layernorm_affine(const float* x, float* out, int64_t TP, int32_t d, const float* gain, const float* shift,
@@ -464,6 +468,19 @@ int rap_posenc_x(const float* x, float* ax, int64_t TP, void* stream);
 int rap_posenc_static(const float* cond, const float* scales, const int32_t* token_sample, const float* feat,
                       int32_t feat_dim, float* astatic, int64_t TP, void* stream);
 int rap_token_sample(const int32_t* cu_batch, int32_t B, int32_t* token_sample, void* stream);
+/* The small kernels of rap_sample / rap_model_create that have no other entry point (for the parity tests; same launchers, same checks
+ * as above).
+ * rap_head_out3: v (TP, 3) = y (TP, K; row stride ldy >= K, ldy % 4 == 0) W (3, K)^T, the last layer of the output head; K one of 128, 256,
+ *   384, 512.
+ * rap_max_abs: *out = max(*out, max_i |x[i]|) as fp32 bits -- *out must hold +0 before the call; NaN entries are ignored, n = 0 leaves it.
+ * rap_qk_logit_bound: out[h] = 8 max|gamma_q[h]| max|gamma_k[h]| * 1.001 for gamma (heads, 64): the logit bound rap_sample hands the
+ *   bounded-softmax attention after qk-norm (see rap_attention_h16 for what it guarantees).
+ * rap_sanitize_cu: out[i] = max_{j <= i} clamp(cu[j], 0, limit) for i < n: a segment table made safe to index with (a consistent table is
+ *   returned unchanged); 0 <= limit <= INT32_MAX. */
+int rap_head_out3(const float* y, int32_t ldy, const float* W, float* v, int64_t TP, int32_t K, void* stream);
+int rap_max_abs(const float* x, int64_t n, float* out, void* stream);
+int rap_qk_logit_bound(const float* gamma_q, const float* gamma_k, int32_t heads, float* out, void* stream);
+int rap_sanitize_cu(const int32_t* cu, int32_t n, int64_t limit, int32_t* out, void* stream);
 /* adaLN (scale|shift) table for model `m`: t (rows,), out (rows, 2*num_layers, 2*embed_dim);
  * scratch >= rows*(256 + 4*num_layers*embed_dim) floats. */
 int rap_adaln_table(const rap_model* m, const float* t, int32_t rows, float* scratch, float* out, void* stream);
@@ -497,6 +514,9 @@ int rap_gemm_h16_splitk(int32_t dtype, int32_t epilogue, const uint16_t* A, int3
  * logit_bound: NULL, or H device floats B[h] with q.k/8 <= B[h] <= 40 for every query/key pair of head h GUARANTEED by
  * the caller (after the reference's qk-norm B = 8 max|gamma_q| max|gamma_k|): selects the bounded-softmax kernel
  * (p = exp(s - B), no running maximum; bf16 only -- other dtypes ignore it).  Same softmax, different evaluation order.
+ * What rap_qk_logit_bound's B = 8 max|gamma_q| max|gamma_k| * 1.001 guarantees for the q, k the qk-norm kernels WRITE: q.k/8 <= B when
+ * they are fp32 or fp16 (two operand roundings of at most 2^-11 fit the 0.1 % slack); in bf16 the two roundings of up to 2^-8 can carry
+ * q.k/8 up to B (1 + 2^-7) -- harmless here (exp(s - B) <= exp(0.31) at B = 40, nowhere near overflow), so the slack is not widened.
  * (Inside rap_sample / rap_dit_forward the bf16 path additionally has qk-norm write q pre-scaled by log2(e)/8 and drops the
  * offset: p = exp2(q'.k); this entry point keeps the un-scaled q convention.) */
 /* The QKV projection with the reference's MultiHeadRMSNorm (flow_model/norm.py:28-33) fused into its epilogue -- what rap_sample /

@@ -121,6 +121,10 @@ SIGNATURES = {
     "rap_posenc_x": (c_int32, [_P, _P, c_int64, _P]),
     "rap_posenc_static": (c_int32, [_P, _P, _P, _P, c_int32, _P, c_int64, _P]),
     "rap_token_sample": (c_int32, [_P, c_int32, _P, _P]),
+    "rap_head_out3": (c_int32, [_P, c_int32, _P, _P, c_int64, c_int32, _P]),
+    "rap_max_abs": (c_int32, [_P, c_int64, _P, _P]),
+    "rap_qk_logit_bound": (c_int32, [_P, _P, c_int32, _P, _P]),
+    "rap_sanitize_cu": (c_int32, [_P, c_int32, c_int64, _P, _P]),
     "rap_adaln_table": (c_int32, [_P, _P, c_int32, _P, _P, _P]),
     "rap_convert_h16": (c_int32, [c_int32, _P, _P, c_int64, _P]),
     "rap_gemm_h16": (c_int32, [c_int32, c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P,

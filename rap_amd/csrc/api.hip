@@ -902,7 +902,7 @@ extern "C" int rap_dit_forward_latent(const rap_model* m, const float* x_t, cons
 
 // kernel-level: the adaLN modulation table of this model for `rows` timesteps
 extern "C" int rap_adaln_table(const rap_model* m, const float* t, int32_t rows, float* scratch, float* out, void* stream) {
-  if (!m || !t || !scratch || !out) return RAP_ERR_INVALID;
+  if (!m || !t || !scratch || !out || rows < 0) return RAP_ERR_INVALID;
   return launch_adaln_table((hipStream_t)stream, t, rows, 2 * m->L, m->d, m->adaW1, m->adab1, m->adaW2, m->adab2, m->adaW3,
                             m->adab3, scratch, out);
 }

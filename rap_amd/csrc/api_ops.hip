@@ -57,7 +57,7 @@ extern "C" int rap_gemm_f32_splitk(int32_t epilogue, const float* A, int32_t lda
 
 extern "C" int rap_geglu_interleave(const float* W, const float* b, float* Wp, float* bp, int32_t inner, int32_t K,
                                     void* stream) {
-  if (!W || !b || !Wp || !bp) return RAP_ERR_INVALID;
+  if (!W || !b || !Wp || !bp || inner <= 0 || inner % 32 != 0 || K <= 0) return RAP_ERR_INVALID;
   return launch_geglu_interleave((hipStream_t)stream, W, b, Wp, bp, inner, K);
 }
 
@@ -130,29 +130,57 @@ extern "C" int rap_attention_f32_split(const float* qkv_headmajor, const int32_t
                               splits, cu_s, nseg);
 }
 
+// The launchers below take the row count as an int and answer RAP_OK to an empty call before they look at anything else: the entry
+// points check every argument first, whatever the row count, and refuse a count the int would truncate (2^32 + 4 rows are not 4 rows).
+static bool rows_fit_int(int64_t rows, int64_t round_up_to = 1) { return rows >= 0 && rows <= 0x7fffffffLL - (round_up_to - 1); }
+static bool model_width_ok(int32_t d) { return d == 256 || d == 512 || d == 768 || d == 1024; }
 extern "C" int rap_layernorm_mod(const float* x, float* out, int64_t TP, int32_t d, const float* mod, int64_t mod_stride,
                                  const int32_t* token_row, void* stream) {
-  if (!x || !out || !mod) return RAP_ERR_INVALID;
+  if (!x || !out || !mod || !model_width_ok(d) || !rows_fit_int(TP, 4)) return RAP_ERR_INVALID;
   return launch_layernorm_mod((hipStream_t)stream, x, out, (int)TP, d, mod, (long)mod_stride, token_row);
 }
 extern "C" int rap_layernorm_affine(const float* x, float* out, int64_t TP, int32_t d, const float* gain, const float* shift,
                                     void* stream) {
-  if (!x || !out || !gain || !shift) return RAP_ERR_INVALID;
+  if (!x || !out || !gain || !shift || !model_width_ok(d) || !rows_fit_int(TP, 4)) return RAP_ERR_INVALID;
   return launch_layernorm_affine((hipStream_t)stream, x, out, (int)TP, d, gain, shift);
+}
+// heads x TP rows per plane, `rows_per_block` of them to a block: the row count fits an int and the grid fits the launch limit
+static bool qknorm_shape_ok(int64_t TP, int32_t heads, int rows_per_block) {
+  return heads > 0 && rows_fit_int(TP) && 2 * (int64_t)heads * TP / rows_per_block < 0x7fffffffLL;
 }
 extern "C" int rap_qknorm(float* qkv_headmajor, int64_t TP, int32_t heads, const float* gamma_q, const float* gamma_k,
                           void* stream) {
-  if (!qkv_headmajor || !gamma_q || !gamma_k) return RAP_ERR_INVALID;
+  if (!qkv_headmajor || !gamma_q || !gamma_k || !qknorm_shape_ok(TP, heads, 16)) return RAP_ERR_INVALID;
   return launch_qknorm((hipStream_t)stream, qkv_headmajor, (int)TP, heads, gamma_q, gamma_k);
 }
 extern "C" int rap_posenc_x(const float* x, float* ax, int64_t TP, void* stream) {
-  if (!x || !ax) return RAP_ERR_INVALID;
+  if (!x || !ax || !rows_fit_int(TP)) return RAP_ERR_INVALID;
   return launch_posenc_x((hipStream_t)stream, x, ax, (int)TP);
 }
 extern "C" int rap_posenc_static(const float* cond, const float* scales, const int32_t* token_sample, const float* feat,
                                  int32_t feat_dim, float* astatic, int64_t TP, void* stream) {
-  if (!cond || !scales || !token_sample || !astatic) return RAP_ERR_INVALID;
+  if (!cond || !scales || !token_sample || !astatic || !rows_fit_int(TP)) return RAP_ERR_INVALID;
+  if (feat_dim < 0 || feat_dim > 40 || feat_dim % 4 != 0 || (feat_dim > 0 && !feat)) return RAP_ERR_INVALID;
   return launch_posenc_static((hipStream_t)stream, cond, scales, token_sample, feat, feat_dim, astatic, (int)TP);
+}
+// The small kernels between the GEMMs that had no entry point of their own (the head tail, the weight-scale maximum, the logit bound
+// of the bounded softmax, the segment-table sanitiser), for the parity tests: the launchers rap_sample / rap_model_create call.
+extern "C" int rap_head_out3(const float* y, int32_t ldy, const float* W, float* v, int64_t TP, int32_t K, void* stream) {
+  if (!y || !W || !v || !rows_fit_int(TP, 4)) return RAP_ERR_INVALID;
+  if ((K != 128 && K != 256 && K != 384 && K != 512) || ldy < K || ldy % 4 != 0) return RAP_ERR_INVALID;
+  return launch_head_out3((hipStream_t)stream, y, ldy, W, v, (int)TP, K);
+}
+extern "C" int rap_max_abs(const float* x, int64_t n, float* out, void* stream) {
+  if (!x || !out || n < 0) return RAP_ERR_INVALID;
+  return launch_max_abs((hipStream_t)stream, x, (size_t)n, out);
+}
+extern "C" int rap_qk_logit_bound(const float* gamma_q, const float* gamma_k, int32_t heads, float* out, void* stream) {
+  if (!gamma_q || !gamma_k || !out || heads <= 0) return RAP_ERR_INVALID;
+  return launch_qk_logit_bound((hipStream_t)stream, gamma_q, gamma_k, heads, out);
+}
+extern "C" int rap_sanitize_cu(const int32_t* cu, int32_t n, int64_t limit, int32_t* out, void* stream) {
+  if (!cu || !out || n < 0 || limit < 0 || limit > 0x7fffffffLL) return RAP_ERR_INVALID;
+  return launch_sanitize_cu((hipStream_t)stream, cu, n, (long)limit, out);
 }
 extern "C" int rap_token_sample(const int32_t* cu_batch, int32_t B, int32_t* token_sample, void* stream) {
   if (!cu_batch || !token_sample) return RAP_ERR_INVALID;
@@ -161,7 +189,7 @@ extern "C" int rap_token_sample(const int32_t* cu_batch, int32_t B, int32_t* tok
 
 // ---- reduced-precision kernel-level entry points (dtype: 1 = bf16, 2 = fp16; 16-bit tensors as uint16_t*) ----
 extern "C" int rap_convert_h16(int32_t dtype, const float* src, uint16_t* dst, int64_t n, void* stream) {
-  if (!src || !dst || n < 0) return RAP_ERR_INVALID;
+  if (!src || !dst || n < 0 || n % 4 != 0 || (dtype != RAP_DT_BF16 && dtype != RAP_DT_F16)) return RAP_ERR_INVALID;
   return launch_convert_h16((hipStream_t)stream, dtype, src, dst, (size_t)n);
 }
 // the operand / output / shape fields every 16-bit GEMM entry point below fills the same way (the rest keeps GemmParamsH's defaults)
@@ -264,17 +292,17 @@ extern "C" int rap_convert_f16_to_f32(const uint16_t* src, float* dst, int64_t n
 }
 extern "C" int rap_qknorm_h16(int32_t dtype, uint16_t* qk, int64_t TP, int32_t heads, const float* gamma_q,
                               const float* gamma_k, void* stream) {
-  if (!qk || !gamma_q || !gamma_k) return RAP_ERR_INVALID;
+  if (!qk || !gamma_q || !gamma_k || (dtype != RAP_DT_BF16 && dtype != RAP_DT_F16) || !qknorm_shape_ok(TP, heads, 32)) return RAP_ERR_INVALID;
   return launch_qknorm_h16((hipStream_t)stream, dtype, qk, (int)TP, heads, gamma_q, gamma_k, 8.0f);
 }
 
 // ---- split-precision kernel-level entry points (compute dtype 3; paired fp16 head / tail operands, see include/rapflow.h) ----
 extern "C" int rap_x2_pack(const float* src, int64_t ld_src, int64_t rows, int32_t cols, float scale, uint16_t* dst, void* stream) {
-  if (!src || !dst || rows < 0 || cols < 0 || ld_src < cols) return RAP_ERR_INVALID;
+  if (!src || !dst || rows < 0 || cols < 0 || cols % 32 != 0 || ld_src < cols || (ld_src & 3)) return RAP_ERR_INVALID;
   return launch_x2_pack((hipStream_t)stream, src, (long)ld_src, (long)rows, cols, scale, dst);
 }
 extern "C" int rap_x2_unpack(const uint16_t* src, int64_t rows, int32_t cols, float inv_scale, float* dst, void* stream) {
-  if (!src || !dst || rows < 0 || cols < 0) return RAP_ERR_INVALID;
+  if (!src || !dst || rows < 0 || cols < 0 || cols % 32 != 0) return RAP_ERR_INVALID;
   return launch_x2_unpack((hipStream_t)stream, src, (long)rows, cols, inv_scale, dst);
 }
 extern "C" int rap_x2_gemm(int32_t epilogue, const uint16_t* A, int32_t lda, const uint16_t* W, int32_t ldw, void* C, int32_t ldc, int32_t M,

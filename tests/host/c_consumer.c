@@ -65,6 +65,28 @@ int main(void) {
       rap_convert_f16_sat((const float*)sentinel, (uint16_t*)sentinel, -4, NULL) != RAP_ERR_INVALID) { printf("saturating conversion\n"); ++fails; }
   if (rap_convert_f16_to_f32((const uint16_t*)sentinel, NULL, 8, NULL) != RAP_ERR_INVALID || rap_convert_f16_to_f32((const uint16_t*)sentinel, (float*)sentinel, 12, NULL) != RAP_ERR_INVALID ||
       rap_convert_f16_to_f32((const uint16_t*)sentinel, (float*)sentinel, -8, NULL) != RAP_ERR_INVALID) { printf("fp16 -> fp32 conversion\n"); ++fails; }
+  /* the kernels between the GEMMs: a row count beyond an int is refused, never truncated (2^32 + 4 is not 4), and so is every other bad
+   * argument at 0 rows; the four entry points of the small kernels check theirs the same way */
+  if (rap_layernorm_mod((const float*)sentinel, (float*)sentinel, ((int64_t)1 << 32) + 4, 512, (const float*)sentinel, 0, NULL, NULL) != RAP_ERR_INVALID ||
+      rap_layernorm_affine((const float*)sentinel, (float*)sentinel, 0, 384, (const float*)sentinel, (const float*)sentinel, NULL) != RAP_ERR_INVALID ||
+      rap_layernorm_affine((const float*)sentinel, (float*)sentinel, 0, 768, (const float*)sentinel, (const float*)sentinel, NULL) != RAP_OK) { printf("fp32 LayerNorm arguments\n"); ++fails; }
+  if (rap_qknorm((float*)sentinel, ((int64_t)1 << 32) + 4, 8, (const float*)sentinel, (const float*)sentinel, NULL) != RAP_ERR_INVALID ||
+      rap_qknorm((float*)sentinel, 4, 0, (const float*)sentinel, (const float*)sentinel, NULL) != RAP_ERR_INVALID ||
+      rap_qknorm_h16(1, (uint16_t*)sentinel, 0, -1, (const float*)sentinel, (const float*)sentinel, NULL) != RAP_ERR_INVALID) { printf("qk-norm arguments\n"); ++fails; }
+  if (rap_posenc_x((const float*)sentinel, (float*)sentinel, ((int64_t)1 << 32) + 4, NULL) != RAP_ERR_INVALID ||
+      rap_posenc_static((const float*)sentinel, (const float*)sentinel, (const int32_t*)sentinel, NULL, 8, (float*)sentinel, 4, NULL) != RAP_ERR_INVALID ||
+      rap_posenc_static((const float*)sentinel, (const float*)sentinel, (const int32_t*)sentinel, NULL, 0, (float*)sentinel, 0, NULL) != RAP_OK) { printf("posenc arguments\n"); ++fails; }
+  if (rap_head_out3(NULL, 256, (const float*)sentinel, (float*)sentinel, 4, 256, NULL) != RAP_ERR_INVALID ||
+      rap_head_out3((const float*)sentinel, 256, (const float*)sentinel, (float*)sentinel, 4, 192, NULL) != RAP_ERR_INVALID ||
+      rap_head_out3((const float*)sentinel, 128, (const float*)sentinel, (float*)sentinel, 4, 256, NULL) != RAP_ERR_INVALID ||
+      rap_head_out3((const float*)sentinel, 256, (const float*)sentinel, (float*)sentinel, 0, 256, NULL) != RAP_OK) { printf("head tail arguments\n"); ++fails; }
+  if (rap_max_abs(NULL, 4, (float*)sentinel, NULL) != RAP_ERR_INVALID || rap_max_abs((const float*)sentinel, -1, (float*)sentinel, NULL) != RAP_ERR_INVALID ||
+      rap_max_abs((const float*)sentinel, 0, (float*)sentinel, NULL) != RAP_OK) { printf("max |x| arguments\n"); ++fails; }
+  if (rap_qk_logit_bound((const float*)sentinel, (const float*)sentinel, 0, (float*)sentinel, NULL) != RAP_ERR_INVALID ||
+      rap_qk_logit_bound((const float*)sentinel, NULL, 8, (float*)sentinel, NULL) != RAP_ERR_INVALID) { printf("logit bound arguments\n"); ++fails; }
+  if (rap_sanitize_cu(NULL, 4, 100, (int32_t*)sentinel, NULL) != RAP_ERR_INVALID || rap_sanitize_cu((const int32_t*)sentinel, -1, 100, (int32_t*)sentinel, NULL) != RAP_ERR_INVALID ||
+      rap_sanitize_cu((const int32_t*)sentinel, 4, -1, (int32_t*)sentinel, NULL) != RAP_ERR_INVALID ||
+      rap_sanitize_cu((const int32_t*)sentinel, 0, 100, (int32_t*)sentinel, NULL) != RAP_OK) { printf("segment-table sanitiser arguments\n"); ++fails; }
   if (rap_model_set_compute_dtype(NULL, 3, NULL) != RAP_ERR_INVALID) { printf("NULL model\n"); ++fails; }
   printf("c consumer: %d failure(s), ABI version %d\n", fails, rap_version());
   return fails;

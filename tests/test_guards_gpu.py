@@ -815,3 +815,87 @@ def test_adaln_table_stays_inside_its_table_and_its_documented_scratch(lib, dev)
             assert (got[:, 2 * i + a] - ref).abs().max().item() < TK.ADALN_BOUND, (i, a)
         return [out]
     run_both(dev, run)
+
+
+# ---------------------------------------------------------------------------------------------
+# the small kernels between the GEMMs: rap_head_out3, rap_max_abs, rap_qk_logit_bound, rap_sanitize_cu (cases and references of
+# tests/ring_cases.py, the bounds of tests/test_ring_edges_gpu.py)
+# ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("extra", [0, 64], ids=["ldy=K", "ldy=K+64"])
+@pytest.mark.parametrize("TP,K", [(1, 128), (5, 384), (333, 512)])
+def test_head_out3_writes_only_its_tp_rows_of_3(lib, dev, TP, K, extra):
+    import ring_cases as RC
+    y, W = RC.head_inputs(TP, K, extra)
+    y[:, K:] = 0.0                                               # (the row gaps of the guarded input take the pad byte below)
+    ref = RC.head_ref64(y, W)
+
+    def run(c):
+        v = c.out_view(F32, (TP, 3), "v")
+        g = G.Guarded(TP * (K + extra) * 4, dev, fill=0, pitch=(K + extra) * 4, guard=c.pad, name="y")
+        c.guards.append(g)
+        yd = g.strided(F32, TP, K, K + extra)                    # the ldy - K floats after every row hold the pad byte: 0x00, then NaN
+        yd.copy_(y[:, :K])
+        Wd = c.inp(W, "W")
+        _lib.check(lib.rap_head_out3(ctypes.c_void_p(yd.data_ptr()), K + extra, _lib.ptr(Wd), _lib.ptr(v), TP, K, stream(dev)), "head_out3")
+        torch.cuda.synchronize()
+        assert (v.cpu().double() - ref).abs().max().item() < TK.GEMM_BOUND
+        return [v]
+    run_both(dev, run)
+
+
+@pytest.mark.parametrize("n", [1, 65, 999])
+def test_max_abs_writes_one_float_and_reads_n(lib, dev, n):
+    import ring_cases as RC
+    x = RC.maxabs_input(RC.MaxAbsCase(n, "last", True))
+    want = RC.maxabs_ref_bits(x)
+
+    def run(c):
+        g = c.out(4, name="max")
+        g.interior.zero_()                                       # the contract: *out holds +0 before the call
+        out = g.view(F32, (1,))
+        xd = c.inp(x, "x")                                       # (pads of 0xFF are NaN beyond x: ignored if read, never a maximum)
+        _lib.check(lib.rap_max_abs(_lib.ptr(xd), n, _lib.ptr(out), stream(dev)), "max_abs")
+        torch.cuda.synchronize()
+        assert int(out.view(I32).cpu()[0]) == want
+        return [out]
+    run_both(dev, run)
+
+
+@pytest.mark.parametrize("H", [1, 12])
+def test_qk_logit_bound_writes_one_float_per_head(lib, dev, H):
+    import ring_cases as RC
+    gq, gk = RC.bound_gammas(H, False)
+    ref = RC.bound_ref64(gq, gk)
+
+    def run(c):
+        out = c.out_view(F32, (H,), "logit bound")
+        gqd, gkd = c.inp(gq, "gamma_q"), c.inp(gk, "gamma_k")
+        _lib.check(lib.rap_qk_logit_bound(_lib.ptr(gqd), _lib.ptr(gkd), H, _lib.ptr(out), stream(dev)), "qk_logit_bound")
+        torch.cuda.synchronize()
+        got = out.cpu().double()
+        assert bool((got >= ref).all()) and bool((got <= ref * RC.BOUND_SLACK * (1 + 2.0 ** -22)).all())
+        return [out]
+    run_both(dev, run)
+
+
+@pytest.mark.parametrize("n", [1, 1025, 5001])
+def test_sanitize_cu_writes_n_entries(lib, dev, n):
+    import ring_cases as RC
+    cu, limit = RC.san_table(n, "dip_on_boundary" if n > 1 else "negative")
+    ref = RC.san_ref(cu, limit)
+
+    def run(c):
+        out = c.out_view(I32, (n,), "sanitised")
+        cud = c.inp(cu, "cu_seqlens")
+        _lib.check(lib.rap_sanitize_cu(_lib.ptr(cud), n, limit, _lib.ptr(out), stream(dev)), "sanitize_cu")
+        torch.cuda.synchronize()
+        assert torch.equal(out.cpu(), ref)
+        return [out]
+    run_both(dev, run)
+    # a refused call writes nothing
+    c = Case(dev, 0x00)
+    out = c.out_view(I32, (n,), "sanitised")
+    cud = c.inp(cu, "cu_seqlens")
+    assert lib.rap_sanitize_cu(_lib.ptr(cud), n, -1, _lib.ptr(out), stream(dev)) == RAP_ERR_INVALID
+    c.check()
+    assert c.guards[0].untouched()
