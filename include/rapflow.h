@@ -34,7 +34,7 @@ extern "C" {
  * rap_icp_workspace_bytes and rap_icp (batched ICP); rap_icp_grid_workspace_bytes, rap_icp_grid, rap_nn_grid_workspace_bytes and
  * rap_nearest_neighbors (the same search over a uniform-grid index); rap_attention_split_workspace_bytes, rap_attention_f32_split and
  * rap_x2_attention_split (kernel-level access to the split-KV attention of few-token calls); rap_gemm_f32_form and rap_gemm_h16_form (the
- * GEMM dispatch decision as host arithmetic), rap_gemm_f32_splitk_workspace_bytes and rap_gemm_f32_splitk (kernel-level access to the
+ * GEMM dispatch decision as host arithmetic), rap_call_plan (every shape-dependent decision of a model call, likewise), rap_gemm_f32_splitk_workspace_bytes and rap_gemm_f32_splitk (kernel-level access to the
  * split-K form of the fp32 residual and SiLU GEMMs of few-token calls). */
 #define RAPFLOW_ABI_VERSION 6
 
@@ -408,6 +408,24 @@ int rap_geglu_interleave(const float* W, const float* b, float* Wp, float* bp, i
 int rap_gemm_f32_form(int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t ldc, int32_t ldr,
                       int32_t has_ws, int32_t planes);
 int rap_gemm_h16_form(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int32_t K, int32_t lda, int32_t ldw, int32_t has_ws);
+/* What a model call of a given shape does, as pure host arithmetic: no model handle, no device.  The launch path itself runs by the function
+ * this reports (api.hip: plan_call), so the answer cannot drift from the call.  The current tuning keys are honoured (5, 6, 7, 11, 12, 17 - 20).
+ *   compute_dtype / resid_dtype: as rap_model_set_compute_dtype / rap_model_set_residual_dtype; d, heads, num_layers, in_dim: the model
+ *   (qk-norm on); TP tokens, B samples, nseg_part part segments (empty ones counted: B x P of rap_sample, VP of rap_dit_forward);
+ *   rows: rows of the adaLN table (flow steps of rap_sample, B of rap_dit_forward: the workspace size depends on it, nothing else does);
+ *   bounded != 0: the attention launches take the bounded softmax (rap_model_bounded_attention_launches counts them).
+ * out[0 .. RAP_CALL_PLAN_FIELDS - 1] (n_out >= RAP_CALL_PLAN_FIELDS):
+ *    0 arithmetic of the call (a split-precision model below tuning key 17: 0)   1 TQ = align_up(TP, 256)
+ *    2 query rows per attention work item   3 key groups per block of the 16-bit attention
+ *    4 / 5 work-list sizes of the per-part / per-sample branch   6 / 7 their key ranges (fp32 and split precision; 1 = unsplit)
+ *    8 / 9 fp32: that branch's split launch keeps every CU to one block   10 combine + LayerNorm fusion on   11 split-K planes reserved
+ *   12 .. 19 form codes (rap_gemm_f32_form / rap_gemm_h16_form) of the static-embedding, x_t-embedding, QKV, out-projection, ff1, ff2 and
+ *      the two head GEMMs (head: M = TQ; a rap_dit_forward call of the fp16 stream with a feature output runs them at M = TP)
+ *   20 workspace bytes (rap_workspace_bytes of such a model: the larger of the two layouts for a split-precision one)
+ * Bad arguments (a NULL or short out, an unknown dtype, a width rap_model_create refuses, TP / B / rows <= 0): RAP_ERR_INVALID, out untouched. */
+#define RAP_CALL_PLAN_FIELDS 21
+int rap_call_plan(int32_t compute_dtype, int32_t resid_dtype, int32_t d, int32_t heads, int32_t num_layers, int32_t in_dim, int64_t TP,
+                  int32_t B, int32_t nseg_part, int32_t rows, int32_t bounded, int64_t* out, int32_t n_out);
 /* Epilogues 1 (bias + residual) and 2 (bias + SiLU) of rap_gemm_f32 with the split-K form rap_sample uses on few-token calls (tuning key
  * 6).  Counting tiles of 128 x 128 and k-tiles of 32 columns:
  *   epilogue 1: K >= 1024 and at most 128 tiles, or K >= 512 and at most 64 tiles: K over 4 blocks per tile (block y takes k-tiles

@@ -106,6 +106,7 @@ SIGNATURES = {
                                _P, _P, c_int32, _P]),
     "rap_gemm_f32_form": (c_int32, [c_int32] * 10),
     "rap_gemm_h16_form": (c_int32, [c_int32] * 8),
+    "rap_call_plan": (c_int32, [c_int32] * 6 + [c_int64] + [c_int32] * 4 + [c_void_p, c_int32]),
     "rap_gemm_f32_splitk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "rap_gemm_f32_splitk": (c_int32, [c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int32, c_int32,
                                       _P, c_size_t, _P]),

@@ -485,8 +485,126 @@ extern "C" int rap_model_qk_norm(const rap_model* m) { return m ? (m->qk_norm ? 
 // workspace
 // ---------------------------------------------------------------------------------------------
 // the arithmetic a call of `rows` token rows actually runs in (see g_rap_x2_min_rows)
-static int eff_dtype(const rap_model* m, size_t rows) {
-  return (m->dtype == RAP_DT_F32X2 && (long)rows < (long)g_rap_x2_min_rows) ? RAP_DT_F32 : m->dtype;
+static int eff_dtype(int model_dtype, size_t rows) {
+  return (model_dtype == RAP_DT_F32X2 && (long)rows < (long)g_rap_x2_min_rows) ? RAP_DT_F32 : model_dtype;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The plan of a model call: EVERY decision that follows from the call's shape, the model's configuration and the tuning keys -- the
+// arithmetic, the padded row count, the attention work-list geometry, the split-K planes the layout reserves, the combine + LayerNorm
+// fusion, and the shape fields (with "workspace given or not") of each of the eight GEMMs of a forward.  plan_call is the one place that
+// states them: carve_workspace lays the buffers out by it, prepare_static / block_f32 / block_h16 / forward_step fill their GemmParams from
+// it (gemm_into), and rap_call_plan reports it, so that a test can hold a call of a given size to the kernels it is meant to reach.
+// The tuning keys are read once, when the call is planned.
+// ---------------------------------------------------------------------------------------------
+struct CallShape {
+  int dtype, resid_dtype;      // the MODEL's compute / residual dtype (the call's arithmetic: CallPlan::dtype)
+  int d, H, L, Ks;
+  bool qk_norm;
+  int64_t TP;
+  int B, nseg_part, rows;      // rows: rows of the adaLN table (flow steps of rap_sample, B of rap_dit_forward)
+};
+enum PlanGemm { PG_STATIC = 0, PG_EMBED, PG_QKV, PG_OUT, PG_FF1, PG_FF2, PG_HEAD0, PG_HEAD1, PG_COUNT };
+struct GemmShape {
+  int epi = 0, M = 0, N = 0, K = 0, lda = 0, ldw = 0, ldc = 0, ldr = 0;
+  bool ws = false;             // a split-K workspace is handed in (which buffer: the launch site's business)
+  int planes = 0;              // GemmParams::splitk_planes
+  int defer = 0, force_splits = 0;      // GemmParamsH::defer_combine / force_splits
+};
+struct CallPlan {
+  int dtype;                   // the arithmetic this call runs in (eff_dtype)
+  bool x2, h16_stream;         // split precision; the residual stream is held in fp16
+  int TQ;                      // align_up(TP, 256): rows of every token-row buffer
+  int attn_bq, attn_kg;        // query rows per attention work item; key groups per block of the 16-bit attention
+  int max_items_part, max_items_batch;
+  int splitk_planes;           // (TQ, d) fp32 planes reserved for the 16-bit / split-precision residual GEMMs (0: no buffer)
+  bool fused;                  // every residual GEMM leaves its planes to the combine + LayerNorm kernel
+  GemmShape g[PG_COUNT];       // PG_QKV .. PG_FF2 in the call's arithmetic (GemmParams or GemmParamsH), the others fp32
+};
+
+static CallPlan plan_call(const CallShape& s, int force_dtype = -1) {
+  CallPlan p{};
+  const int d = s.d, TP = (int)s.TP;
+  const size_t Tz = align_up((size_t)s.TP, 256);
+  const int T = p.TQ = (int)Tz;
+  const int dtype = p.dtype = force_dtype >= 0 ? force_dtype : eff_dtype(s.dtype, Tz);
+  const bool f32 = dtype == RAP_DT_F32, x2 = p.x2 = dtype == RAP_DT_F32X2;
+  const bool half = dtype == RAP_DT_BF16 || dtype == RAP_DT_F16;
+  p.h16_stream = half && s.resid_dtype == RAP_DT_F16;
+  // query rows per attention work item: 256, or 64 / 128 for few-token calls of the 16-bit modes (attention_h16_block_queries)
+  p.attn_bq = half ? attention_h16_block_queries(dtype, (long)T) : RAP_ATTN_BQ;
+  p.attn_kg = half ? attention_h16_key_groups(dtype, (long)T) : 1;
+  p.max_items_batch = (int)(s.TP / p.attn_bq) + s.B + 1;
+  p.max_items_part = (int)(s.TP / p.attn_bq) + s.nseg_part + 1;
+  // ff2: the one layer GEMM with K >= 1024.  Reserved by SHAPE alone (tuning key 6 only gates the launch), so that the size
+  // rap_workspace_bytes reports cannot change between the query and the call
+  if (!f32) {
+    const int splits = gemm_h16_splits_by_shape(T, d, (x2 ? 8 : 4) * d);   // (split precision: the physical K of ff2 is 8 d)
+    p.splitk_planes = splits > 1 ? splits : 0;
+  }
+  // Few-token calls of the 16-bit / split-precision blocks (round 6; the reference's everyday batch_size: 1, RAP_inference.yaml:30-36): every
+  // residual GEMM leaves fp32 partial planes (split-K where gemm_h16_splits says so, one plane otherwise) and ONE kernel forms the new
+  // residual-stream value and the LayerNorm that follows it (launch_resid_combine_ln_h16) -- 11 launches per layer instead of 14.  The planes
+  // live in the split-K buffer, which exists exactly for the calls this is meant for (<= 128 tiles of 128 x 128 in the N = d GEMMs).
+  p.fused = g_rap_small_fused && !f32 && p.splitk_planes > 0 && g_rap_gemm_splitk;
+
+  auto shape = [](int epi, int M, int N, int K, int lda, int ldw, int ldc, int ldr) {
+    GemmShape g; g.epi = epi; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr; return g;
+  };
+  // (the count is fixed HERE: the GEMM and the pass that reads its planes cannot disagree)
+  auto defer_combine = [](GemmShape& g) { const int sp = gemm_h16_splits(g.M, g.N, g.K); g.defer = 1; g.force_splits = sp > 1 ? sp : 1; };
+  // fp32 in every mode: the step-invariant embedding part over the TP real rows, PE(x_t) Wx^T + base and the head over TQ rows
+  p.g[PG_STATIC] = shape(EPI_BIAS_ANCHOR, TP, d, s.Ks, s.Ks, s.Ks, d, 0);
+  p.g[PG_EMBED] = shape(EPI_BIAS_RESID, T, d, 64, 64, 64, d, d);
+  // few-token calls: K of the two hidden layers of the head over 2 / 4 blocks per tile (gemm_f32_form decides by the tile count); the partial
+  // planes live in the FFN buffer of the fp32 layout (4 T d floats, idle there) resp. the split-K planes of the 16-bit layouts
+  p.g[PG_HEAD0] = shape(EPI_BIAS_SILU, T, d, d, d, d, d, 0);
+  p.g[PG_HEAD1] = shape(EPI_BIAS_SILU, T, d / 2, d, d, d, d / 2, 0);
+  for (int k = PG_HEAD0; k <= PG_HEAD1; ++k) { p.g[k].ws = f32 || p.splitk_planes > 0; p.g[k].planes = f32 ? 4 : p.splitk_planes; }
+  if (f32) {
+    p.g[PG_QKV] = shape(EPI_QKV_HEADMAJOR, T, 3 * d, d, d, d, 0, 0);
+    p.g[PG_OUT] = shape(EPI_BIAS_RESID, T, d, d, d, d, d, d);
+    p.g[PG_OUT].ws = true;       // the FFN buffer, idle between the FFNs (the split attention's partial planes are consumed by then): 4 (T,d) planes
+    p.g[PG_FF1] = shape(EPI_GEGLU, T, 8 * d, d, d, d, 4 * d, 0);
+    p.g[PG_FF2] = shape(EPI_BIAS_RESID, T, d, 4 * d, 4 * d, 4 * d, d, d);
+    p.g[PG_FF2].ws = true;       // qkv (3 T d) and att (T d), idle during the FFN and adjacent: 4 (T,d) planes
+  } else {
+    const int pl = x2 ? 2 : 1;   // planes per value: K, lda, ldw (and ldc of the GEGLU output) are physical 16-bit counts
+    const int epi_resid = p.h16_stream ? EPI_H_BIAS_RESID_H16 : EPI_H_BIAS_RESID_F32;
+    // qk-norm in the QKV epilogue (tuning key 7; always in split precision): one kernel, q / k normalised from the fp32 accumulators
+    p.g[PG_QKV] = shape((x2 || (g_rap_fuse_qknorm && s.qk_norm)) ? EPI_H_QKV_NORM : EPI_H_QKV, T, 3 * d, pl * d, pl * d, pl * d, 0, 0);
+    p.g[PG_OUT] = shape(epi_resid, T, d, pl * d, pl * d, pl * d, d, d);
+    if (p.fused) { p.g[PG_OUT].ws = true; defer_combine(p.g[PG_OUT]); }
+    p.g[PG_FF1] = shape(EPI_H_GEGLU, T, 8 * d, pl * d, pl * d, pl * d, pl * 4 * d, 0);
+    p.g[PG_FF2] = shape(epi_resid, T, d, pl * 4 * d, pl * 4 * d, pl * 4 * d, d, d);
+    p.g[PG_FF2].ws = p.splitk_planes > 0;      // few-token calls: K = 4d (physical 8d in split precision) over 2 / 4 blocks per tile
+    // ... and its combine pass is the first LayerNorm of the next layer (the last layer's ff2 combines itself: block_h16)
+    if (p.fused && s.L > 1) defer_combine(p.g[PG_FF2]);
+  }
+  return p;
+}
+static float g_ws_given;      // (never dereferenced: a form only asks whether a workspace was handed in)
+static void gemm_into(const GemmShape& s, GemmParams& g, float* ws) {
+  g.M = s.M; g.N = s.N; g.K = s.K; g.lda = s.lda; g.ldw = s.ldw; g.ldc = s.ldc; g.ldr = s.ldr;
+  g.splitk_ws = s.ws ? ws : nullptr; g.splitk_planes = s.planes;
+}
+static void gemm_into(const GemmShape& s, GemmParamsH& g, float* ws) {
+  g.M = s.M; g.N = s.N; g.K = s.K; g.lda = s.lda; g.ldw = s.ldw; g.ldc = s.ldc; g.ldr = s.ldr;
+  g.splitk_ws = s.ws ? ws : nullptr; g.defer_combine = s.defer; g.force_splits = s.force_splits;
+}
+// the form code (kernels.h) of GEMM k of the plan
+static int plan_form(const CallPlan& p, int k) {
+  if (p.dtype == RAP_DT_F32 || k < PG_QKV || k > PG_FF2) { GemmParams g{}; gemm_into(p.g[k], g, &g_ws_given); return gemm_f32_form(p.g[k].epi, g); }
+  GemmParamsH g{}; gemm_into(p.g[k], g, &g_ws_given); return gemm_h16_form(p.dtype, p.g[k].epi, g);
+}
+// the key ranges of one attention launch (branch 0: per part, 1: per sample) and whether the split launch keeps every CU to one block.
+// bounded: every head of that launch has a logit bound (fp32: only the bounded kernel can add partial results; 16-bit: never split)
+struct AttnPlan { int splits; bool one_per_cu; };
+static AttnPlan plan_attention(const CallPlan& p, int H, int branch, bool bounded) {
+  const int max_items = branch == 0 ? p.max_items_part : p.max_items_batch;
+  if (p.dtype == RAP_DT_F32) { const int sp = attention_f32_splits(max_items, H, bounded); return {sp, attention_f32_one_per_cu(max_items, H, sp)}; }
+  if (p.x2) return {attention_x2_splits(max_items, H), false};
+  return {1, false};
 }
 
 struct Workspace {
@@ -509,24 +627,34 @@ struct Workspace {
   int max_items_batch, max_items_part;
   int attn_bq;                          // query rows per work item of this call's attention lists
   int attn_kg;                          // key groups per block of the 16-bit attention (1, or 2 / 4 for few-token calls)
+  CallPlan plan;                        // what the fields above were laid out by, and what the launches of this call follow
   size_t total;
 };
 
-static Workspace carve_workspace(const rap_model* m, int64_t TP, int B, int nseg_part, int rows, char* basep, int force_dtype = -1) {
+static CallShape call_shape(const rap_model* m, int64_t TP, int B, int nseg_part, int rows) {
+  CallShape s{};
+  s.dtype = m->dtype; s.resid_dtype = m->resid_dtype; s.d = m->d; s.H = m->H; s.L = m->L; s.Ks = m->Ks; s.qk_norm = m->qk_norm;
+  s.TP = TP; s.B = B; s.nseg_part = nseg_part; s.rows = rows;
+  return s;
+}
+static Workspace carve_workspace(const CallShape& s, char* basep, int force_dtype = -1) {
   Workspace w;
-  const size_t d = m->d, L = m->L;
+  const CallPlan& plan = w.plan = plan_call(s, force_dtype);
+  const size_t d = s.d, L = s.L;
+  const int64_t TP = s.TP;
+  const int B = s.B, nseg_part = s.nseg_part, rows = s.rows;
   Carver c(basep);
   // Every token-row buffer is carved at TQ = align_up(TP, 256) rows (round 4): the layer kernels run over TQ rows, so the persistent
   // 256-row-tile GEMMs serve ANY token count (ragged batches are the reference's real regime, RAP_inference.yaml:30-36); rows
   // TP .. TQ-1 are finite filler nobody reads (rows are independent in every kernel but attention, whose work lists and key
   // ranges stop at the true segment ends).  See forward_step.
-  const size_t T = align_up((size_t)TP, 256);
-  w.rows = (int)T;
-  const int dtype = w.dtype = force_dtype >= 0 ? force_dtype : eff_dtype(m, T);
-  w.qk_norm = m->qk_norm;
+  const size_t T = (size_t)plan.TQ;
+  w.rows = plan.TQ;
+  const int dtype = w.dtype = plan.dtype;
+  w.qk_norm = s.qk_norm;
   w.base = (float*)c.take(T * d * 4);
-  const bool x2 = dtype == RAP_DT_F32X2;    // split precision: fp32 residual stream, every 16-bit activation buffer holds heads AND tails
-  const bool h16 = dtype != RAP_DT_F32 && !x2 && m->resid_dtype == RAP_DT_F16;
+  const bool x2 = plan.x2;                  // split precision: fp32 residual stream, every 16-bit activation buffer holds heads AND tails
+  const bool h16 = plan.h16_stream;
   w.h = h16 ? nullptr : (float*)c.take(T * d * 4);
   w.h16 = h16 ? (u16*)c.take(T * d * 2) : nullptr;
   w.xn = w.qkv = w.att = w.ffmid = nullptr;
@@ -549,15 +677,13 @@ static Workspace carve_workspace(const rap_model* m, int64_t TP, int B, int nseg
     w.atth = (u16*)c.take(T * d * 2 * pl);
     // >= 8*T*d bytes: also hosts the fp32 head hidden layers and the static feature matrix (T,Ks) fp32 = 4*T*Ks bytes, which is the
     // larger of the two at d = 256 with in_dim > 384 in the 16-bit modes (pl = 1)
-    const size_t ffmid_bytes = T * 4 * d * 2 * pl, static_bytes = T * (size_t)m->Ks * 4;
+    const size_t ffmid_bytes = T * 4 * d * 2 * pl, static_bytes = T * (size_t)s.Ks * 4;
     w.ffmidh = (u16*)c.take(ffmid_bytes > static_bytes ? ffmid_bytes : static_bytes);
     w.hid1 = (float*)w.ffmidh;                 // (T,d) fp32   = 4*T*d bytes
     w.hid2 = w.hid1 + T * d;                   // (T,d/2) fp32 = 2*T*d bytes
     w.astatic = (float*)w.ffmidh;
-    // ff2: the one layer GEMM with K >= 1024.  Reserved by SHAPE alone (tuning key 6 only gates the launch), so that the size
-    // rap_workspace_bytes reports cannot change between the query and the call
-    const int splits = gemm_h16_splits_by_shape((int)T, (int)d, (int)((x2 ? 8 : 4) * d));   // (split precision: the physical K of ff2 is 8 d)
-    if (splits > 1) { w.splitk_h = (float*)c.take((size_t)splits * T * d * 4); w.splitk_planes = splits; }
+    // the fp32 partial planes of few-token calls (plan_call: by the shape of ff2 alone)
+    if (plan.splitk_planes > 0) { w.splitk_h = (float*)c.take((size_t)plan.splitk_planes * T * d * 4); w.splitk_planes = plan.splitk_planes; }
   }
   w.ax = (float*)c.take(T * 64 * 4);
   w.v = (float*)c.take(T * 3 * 4);
@@ -570,11 +696,8 @@ static Workspace carve_workspace(const rap_model* m, int64_t TP, int B, int nseg
   w.cu_batch_s = (int32_t*)c.take(((size_t)B + 1) * 4);
   w.cu_part_s = (int32_t*)c.take(((size_t)nseg_part + 1) * 4);
   w.cu_part_live = w.part_offsets; w.nseg_part = nseg_part; w.nseg_batch = B;
-  // query rows per attention work item: 256, or 64 / 128 for few-token calls of the 16-bit modes (attention_h16_block_queries)
-  w.attn_bq = (dtype == RAP_DT_BF16 || dtype == RAP_DT_F16) ? attention_h16_block_queries(dtype, (long)T) : RAP_ATTN_BQ;
-  w.attn_kg = (dtype == RAP_DT_BF16 || dtype == RAP_DT_F16) ? attention_h16_key_groups(dtype, (long)T) : 1;
-  w.max_items_batch = (int)(TP / w.attn_bq) + B + 1;
-  w.max_items_part = (int)(TP / w.attn_bq) + nseg_part + 1;
+  w.attn_bq = plan.attn_bq; w.attn_kg = plan.attn_kg;
+  w.max_items_batch = plan.max_items_batch; w.max_items_part = plan.max_items_part;
   // (reserved for the smallest work items whatever tuning key 20 says: the size rap_workspace_bytes reports does not depend on the key)
   w.items_batch = (AttnWorkItem*)c.take(((size_t)(TP / 64) + B + 1) * sizeof(AttnWorkItem));
   w.items_part = (AttnWorkItem*)c.take(((size_t)(TP / 64) + nseg_part + 1) * sizeof(AttnWorkItem));
@@ -586,6 +709,14 @@ static Workspace carve_workspace(const rap_model* m, int64_t TP, int B, int nseg
   return w;
 }
 
+static size_t workspace_bytes_of(const CallShape& s) {
+  if (s.dtype == RAP_DT_F32X2) {      // both layouts: see rap_workspace_bytes
+    const size_t a = carve_workspace(s, nullptr, RAP_DT_F32).total;
+    const size_t b = carve_workspace(s, nullptr, RAP_DT_F32X2).total;
+    return a > b ? a : b;
+  }
+  return carve_workspace(s, nullptr).total;
+}
 extern "C" size_t rap_workspace_bytes(const rap_model* m, int64_t TP, int32_t B, int32_t nseg_part, int32_t rows) {
   if (!m || TP < 0 || B < 0 || nseg_part < 0 || rows < 0) return 0;
   std::lock_guard<std::mutex> lock(m->cfg_mu);
@@ -593,12 +724,33 @@ extern "C" size_t rap_workspace_bytes(const rap_model* m, int64_t TP, int32_t B,
   // split layout adds the split-K planes of few-token calls).  The size reported covers BOTH, so that a change of the process-global
   // threshold between this query and the call -- __graft_entry__.smoke() and the tests do toggle it -- cannot turn a valid call into
   // RAP_ERR_WORKSPACE (the comment here used to claim the two layouts need the same bytes).
-  if (m->dtype == RAP_DT_F32X2) {
-    const size_t a = carve_workspace(m, TP, B, nseg_part, rows, nullptr, RAP_DT_F32).total;
-    const size_t b = carve_workspace(m, TP, B, nseg_part, rows, nullptr, RAP_DT_F32X2).total;
-    return a > b ? a : b;
-  }
-  return carve_workspace(m, TP, B, nseg_part, rows, nullptr).total;
+  return workspace_bytes_of(call_shape(m, TP, B, nseg_part, rows));
+}
+
+// What a model call of this shape does (include/rapflow.h): plan_call's own answer -- the function the launch path runs by -- plus the form
+// code of each GEMM and the workspace size.  Host arithmetic only: no model handle, no device.
+extern "C" int rap_call_plan(int32_t compute_dtype, int32_t resid_dtype, int32_t d, int32_t heads, int32_t num_layers, int32_t in_dim, int64_t TP,
+                             int32_t B, int32_t nseg_part, int32_t rows, int32_t bounded, int64_t* out, int32_t n_out) {
+  if (!out || n_out < RAP_CALL_PLAN_FIELDS) return RAP_ERR_INVALID;
+  if (compute_dtype < RAP_DT_F32 || compute_dtype > RAP_DT_F32X2 || (resid_dtype != RAP_DT_F32 && resid_dtype != RAP_DT_F16)) return RAP_ERR_INVALID;
+  rap_model_desc desc{};
+  desc.embed_dim = d; desc.num_heads = heads; desc.num_layers = num_layers;
+  if (!desc_ok(&desc) || !in_dim_ok(in_dim)) return RAP_ERR_INVALID;
+  if (TP <= 0 || TP > 0x7fffffffLL / 8 || B <= 0 || nseg_part < 0 || nseg_part > 65535 || rows <= 0) return RAP_ERR_INVALID;
+  CallShape s{};
+  s.dtype = compute_dtype; s.resid_dtype = resid_dtype; s.d = d; s.H = heads; s.L = num_layers; s.Ks = 128 + (int)align_up((size_t)in_dim, 32);
+  s.qk_norm = true;      // (every shipped configuration; without it no launch is bounded and the QKV epilogue of the 16-bit modes is the plain one)
+  s.TP = TP; s.B = B; s.nseg_part = nseg_part; s.rows = rows;
+  const CallPlan p = plan_call(s);
+  const AttnPlan ap = plan_attention(p, heads, 0, bounded != 0), ab = plan_attention(p, heads, 1, bounded != 0);
+  int64_t* o = out;
+  *o++ = p.dtype; *o++ = p.TQ; *o++ = p.attn_bq; *o++ = p.attn_kg; *o++ = p.max_items_part; *o++ = p.max_items_batch;
+  *o++ = ap.splits; *o++ = ab.splits; *o++ = ap.one_per_cu ? 1 : 0; *o++ = ab.one_per_cu ? 1 : 0;
+  *o++ = p.fused ? 1 : 0; *o++ = p.splitk_planes;
+  for (int k = 0; k < PG_COUNT; ++k) *o++ = plan_form(p, k);
+  *o++ = (int64_t)workspace_bytes_of(s);
+  static_assert(12 + PG_COUNT + 1 == RAP_CALL_PLAN_FIELDS, "rapflow.h: the fields of rap_call_plan");
+  return RAP_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -656,15 +808,16 @@ static int prepare_static(const rap_model* m, const Workspace& w, hipStream_t st
     if ((rc = launch_copy_cols(stream, latent, m->Din, 0, astatic, Ks, 128, TP, m->Din))) return rc;
   }
   GemmParams g{};
-  g.A = astatic; g.lda = Ks; g.W = m->Wstatic; g.ldw = Ks; g.C = w.base; g.ldc = m->d;
-  g.M = TP; g.N = m->d; g.K = Ks; g.bias = m->emb_bias; g.anchor = anchor; g.anchor_emb = m->anchor_emb;
-  return launch_gemm_f32(stream, EPI_BIAS_ANCHOR, g);
+  gemm_into(w.plan.g[PG_STATIC], g, nullptr);      // M = TP rows, K = Ks
+  g.A = astatic; g.W = m->Wstatic; g.C = w.base; g.bias = m->emb_bias; g.anchor = anchor; g.anchor_emb = m->anchor_emb;
+  return launch_gemm_f32(stream, w.plan.g[PG_STATIC].epi, g);
 }
 
 // ---- one transformer block in exact fp32 (layer i).  mod: see forward_step.
 static int block_f32(const rap_model* m, const Workspace& w, hipStream_t stream, int i, const float* mod, long mod_stride,
                      const int32_t* token_row) {
   const int d = m->d, H = m->H, TP = w.rows;
+  const CallPlan& plan = w.plan;
   const LayerW& lw = m->layers[i];
   int rc;
   for (int a = 0; a < 2; ++a) {   // a = 0: per-part attention, a = 1: per-sample attention (layer.py:152-160)
@@ -672,10 +825,11 @@ static int block_f32(const rap_model* m, const Workspace& w, hipStream_t stream,
     { ProfScope ps(stream, 3); rc = launch_layernorm_mod(stream, w.h, w.xn, TP, d, mod + (size_t)j * 2 * d, mod_stride, token_row); }
     if (rc) return rc;
     GemmParams g{};
-    g.A = w.xn; g.lda = d; g.W = lw.Wqkv[a]; g.ldw = d; g.C = w.qkv; g.M = TP; g.N = 3 * d; g.K = d; g.heads = H;
+    gemm_into(plan.g[PG_QKV], g, nullptr);
+    g.A = w.xn; g.W = lw.Wqkv[a]; g.C = w.qkv; g.heads = H;
     const bool fuse_qk = g_rap_fuse_qknorm != 0 && w.qk_norm;
     if (fuse_qk) { g.gamma_q = lw.gq[a]; g.gamma_k = lw.gk[a]; }        // qk-norm in the QKV epilogue (tuning key 7)
-    { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_QKV_HEADMAJOR, g); }
+    { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, plan.g[PG_QKV].epi, g); }
     if (rc) return rc;
     if (!fuse_qk && w.qk_norm && (rc = launch_qknorm(stream, w.qkv, TP, H, lw.gq[a], lw.gk[a]))) return rc;
     {
@@ -684,30 +838,28 @@ static int block_f32(const rap_model* m, const Workspace& w, hipStream_t stream,
       // few-token calls: split the keys of every work item over up to 4 blocks; the partial O planes live in the (idle) FFN
       // buffer (4 x TP x d floats), the partial row sums in the (idle) LN-output buffer
       const int max_items = a == 0 ? w.max_items_part : w.max_items_batch;
-      const int splits = attention_f32_splits(max_items, H, bound != nullptr);
+      const int splits = plan_attention(plan, H, a, bound != nullptr).splits;
       rc = launch_attention_f32(stream, w.qkv, w.att, TP, H, a == 0 ? w.items_part : w.items_batch, max_items, bound, w.ffmid, w.xn,
                                 splits, a == 0 ? w.cu_part_live : w.cu_batch_s, a == 0 ? w.nseg_part : w.nseg_batch);
     }
     if (rc) return rc;
     GemmParams o{};
-    o.A = w.att; o.lda = d; o.W = lw.Wout[a]; o.ldw = d; o.C = w.h; o.ldc = d; o.M = TP; o.N = d; o.K = d;
-    o.bias = lw.bout[a]; o.resid = w.h; o.ldr = d;
-    o.splitk_ws = w.ffmid;     // idle between the FFNs (the split attention's partial planes are consumed by now): 4 partial (T,d) planes
-    { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_BIAS_RESID, o); }
+    gemm_into(plan.g[PG_OUT], o, w.ffmid);     // idle between the FFNs (the split attention's partial planes are consumed by now): 4 partial (T,d) planes
+    o.A = w.att; o.W = lw.Wout[a]; o.C = w.h; o.bias = lw.bout[a]; o.resid = w.h;
+    { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, plan.g[PG_OUT].epi, o); }
     if (rc) return rc;
   }
   { ProfScope ps(stream, 3); rc = launch_layernorm_affine(stream, w.h, w.xn, TP, d, lw.ffn_g, lw.ffn_b); }
   if (rc) return rc;
   GemmParams f1{};
-  f1.A = w.xn; f1.lda = d; f1.W = lw.Wff1p; f1.ldw = d; f1.C = w.ffmid; f1.ldc = 4 * d; f1.M = TP; f1.N = 8 * d; f1.K = d;
-  f1.bias = lw.bff1p;
-  { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_GEGLU, f1); }
+  gemm_into(plan.g[PG_FF1], f1, nullptr);
+  f1.A = w.xn; f1.W = lw.Wff1p; f1.C = w.ffmid; f1.bias = lw.bff1p;
+  { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, plan.g[PG_FF1].epi, f1); }
   if (rc) return rc;
   GemmParams f2{};
-  f2.A = w.ffmid; f2.lda = 4 * d; f2.W = lw.Wff2; f2.ldw = 4 * d; f2.C = w.h; f2.ldc = d; f2.M = TP; f2.N = d; f2.K = 4 * d;
-  f2.bias = lw.bff2; f2.resid = w.h; f2.ldr = d;
-  f2.splitk_ws = w.qkv;      // idle during the FFN; qkv (3 T d) and att (T d) are adjacent: 4 partial (T,d) planes
-  { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, EPI_BIAS_RESID, f2); }
+  gemm_into(plan.g[PG_FF2], f2, w.qkv);      // idle during the FFN; qkv (3 T d) and att (T d) are adjacent: 4 partial (T,d) planes
+  f2.A = w.ffmid; f2.W = lw.Wff2; f2.C = w.h; f2.bias = lw.bff2; f2.resid = w.h;
+  { ProfScope ps(stream, 2); rc = launch_gemm_f32(stream, plan.g[PG_FF2].epi, f2); }
   return rc;
 }
 
@@ -717,33 +869,31 @@ static int block_f32(const rap_model* m, const Workspace& w, hipStream_t stream,
 // per-tensor power-of-two scales, fp32 residual stream, qk-norm always fused, online softmax (probabilities must fit fp16).
 // fused: few-token calls (see forward_step) -- every LayerNorm but the first of the forward is then part of the combine pass before it.
 static int block_h16(const rap_model* m, const Workspace& w, hipStream_t stream, int i, const float* mod, long mod_stride,
-                     const int32_t* token_row, int TP_valid, bool fused) {
+                     const int32_t* token_row, int TP_valid) {
   const int d = m->d, H = m->H, TP = w.rows, dt = w.dtype;
-  const bool x2 = dt == RAP_DT_F32X2;
-  const int pl = x2 ? 2 : 1;                // planes per value
+  const CallPlan& plan = w.plan;
+  const bool x2 = plan.x2, fused = plan.fused;
   const LayerW& lw = m->layers[i];
   // the 16-bit modes leave every s_* / g_* of LayerWH at 1.f, which are GemmParamsH's own defaults: the scales below are split precision's
   const LayerWH& lh = m->half[dt].layers[i];
   void* const hres = w.h16 ? (void*)w.h16 : (void*)w.h;      // the residual stream as the 16-bit LayerNorms and the residual GEMMs see it
   const int hres_f16 = w.h16 ? 1 : 0;
-  const int epi_resid = w.h16 ? EPI_H_BIAS_RESID_H16 : EPI_H_BIAS_RESID_F32;
-  auto onto_resid = [&](GemmParamsH& g) { g.C = hres; g.ldc = d; g.ldr = d; if (w.h16) g.resid_h = w.h16; else g.resid = w.h; };
-  // (the count is fixed HERE: the GEMM and the pass that reads its planes cannot disagree)
-  auto defer_combine = [&](GemmParamsH& g) { const int sp = gemm_h16_splits(g.M, g.N, g.K); g.defer_combine = 1; g.force_splits = sp > 1 ? sp : 1; };
+  auto onto_resid = [&](GemmParamsH& g) { g.C = hres; if (w.h16) g.resid_h = w.h16; else g.resid = w.h; };
   int rc = RAP_OK;
   for (int a = 0; a < 2; ++a) {
     const int j = 2 * i + a;
     if (!fused || j == 0) { ProfScope ps(stream, 3); rc = launch_layernorm_mod_h16(stream, dt, hres, hres_f16, w.xnh, TP, d, mod + (size_t)j * 2 * d, mod_stride, token_row); }
     if (rc) return rc;
     GemmParamsH g{};
-    g.A = w.xnh; g.lda = pl * d; g.W = lh.Wqkv[a]; g.ldw = pl * d; g.C = w.qkh; g.M = TP; g.N = 3 * d; g.K = pl * d; g.heads = H;
+    gemm_into(plan.g[PG_QKV], g, nullptr);
+    g.A = w.xnh; g.W = lh.Wqkv[a]; g.C = w.qkh; g.heads = H;
     g.vt = w.vth; g.vt_nblk = w.vt_nblk; g.acc_scale = lh.s_qkv[a]; g.out_scale = lh.g_v[a];
     const bool bnd = !x2 && w.qk_norm && m->bounded[j] != 0;         // this launch's softmax kernel (per layer and branch)
     const bool prescale = attention_h16_wants_prescaled_q(dt, bnd);
     const float q_mul = prescale ? RAP_QMUL_PRESCALED : 8.0f;
     // (few-token calls: the fused epilogue exists on 128 x 128 tiles too since round 6 -- launch_gemm_h16 picks the tile; until then
     // such calls ran the projection and qk-norm as two kernels, r03 call 32)
-    if (x2 || (g_rap_fuse_qknorm && w.qk_norm)) {
+    if (plan.g[PG_QKV].epi == EPI_H_QKV_NORM) {
       // qk-norm in the QKV epilogue: one kernel, q / k normalised from the fp32 accumulators (no 16-bit round trip through HBM)
       if (w.qk_norm) { g.gamma_q = lw.gq[a]; g.gamma_k = lw.gk[a]; }      // (split precision) null gains: the epilogue splits q / k as projected
       g.q_mul = q_mul;
@@ -762,7 +912,7 @@ static int block_h16(const rap_model* m, const Workspace& w, hipStream_t stream,
         // few-token calls: the keys of every work item over 2 / 4 blocks; the partial O planes (4 x TQ x d floats) live in the idle FFN
         // buffer (16 TQ d bytes in this mode), the partial (max, row sum) pairs in the idle LayerNorm-output buffer
         rc = launch_attention_x2(stream, w.qkh, w.vth, w.vt_nblk, w.atth, TP, H, items, max_items, reinterpret_cast<float*>(w.ffmidh),
-                                 reinterpret_cast<float*>(w.xnh), attention_x2_splits(max_items, H), TP_valid,
+                                 reinterpret_cast<float*>(w.xnh), plan_attention(plan, H, a, bnd).splits, TP_valid,
                                  a == 0 ? w.cu_part_live : w.cu_batch_s, a == 0 ? w.nseg_part : w.nseg_batch);
       } else {
         rc = launch_attention_h16(stream, dt, w.qkh, w.vth, w.vt_nblk, w.atth, TP, H, items, max_items,
@@ -771,11 +921,11 @@ static int block_h16(const rap_model* m, const Workspace& w, hipStream_t stream,
     }
     if (rc) return rc;
     GemmParamsH o{};
-    o.A = w.atth; o.lda = pl * d; o.W = lh.Wout[a]; o.ldw = pl * d; o.M = TP; o.N = d; o.K = pl * d;
+    gemm_into(plan.g[PG_OUT], o, w.splitk_h);      // (fused: its planes stay in the split-K buffer for the pass below)
+    o.A = w.atth; o.W = lh.Wout[a];
     o.bias = lw.bout[a]; o.acc_scale = lh.s_out[a] / lh.g_v[a];      // (the attention output carries V's activation scale)
     onto_resid(o);
-    if (fused) { o.splitk_ws = w.splitk_h; defer_combine(o); }
-    { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, epi_resid, o); }
+    { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, plan.g[PG_OUT].epi, o); }
     if (rc) return rc;
     if (fused) {      // combine pass + the NEXT LayerNorm in one kernel: adaLN of the per-sample branch after a = 0, the FFN's affine LN after a = 1
       ProfScope ps(stream, 3);
@@ -787,18 +937,19 @@ static int block_h16(const rap_model* m, const Workspace& w, hipStream_t stream,
   if (!fused) { ProfScope ps(stream, 3); rc = launch_layernorm_affine_h16(stream, dt, hres, hres_f16, w.xnh, TP, d, lw.ffn_g, lw.ffn_b); }
   if (rc) return rc;
   GemmParamsH f1{};
-  f1.A = w.xnh; f1.lda = pl * d; f1.W = lh.Wff1p; f1.ldw = pl * d; f1.C = w.ffmidh; f1.ldc = pl * 4 * d; f1.M = TP; f1.N = 8 * d; f1.K = pl * d;
+  gemm_into(plan.g[PG_FF1], f1, nullptr);
+  f1.A = w.xnh; f1.W = lh.Wff1p; f1.C = w.ffmidh;
   f1.bias = lw.bff1p; f1.acc_scale = lh.s_ff1; f1.out_scale = lh.g_ff1;
-  { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, EPI_H_GEGLU, f1); }
+  { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, plan.g[PG_FF1].epi, f1); }
   if (rc) return rc;
   GemmParamsH f2{};
-  f2.A = w.ffmidh; f2.lda = pl * 4 * d; f2.W = lh.Wff2; f2.ldw = pl * 4 * d; f2.M = TP; f2.N = d; f2.K = pl * 4 * d;
+  gemm_into(plan.g[PG_FF2], f2, w.splitk_h);      // few-token calls: K split over 2 / 4 blocks per tile (no buffer otherwise)
+  f2.A = w.ffmidh; f2.W = lh.Wff2;
   f2.bias = lw.bff2; f2.acc_scale = lh.s_ff2 / lh.g_ff1;
   onto_resid(f2);
-  f2.splitk_ws = w.splitk_h;               // few-token calls: K = 4d (physical 8d in split precision) split over 2 / 4 blocks per tile (null otherwise)
-  const bool f2_fused = fused && i + 1 < m->L;      // ... and its combine pass is the first LayerNorm of the next layer
-  if (f2_fused) defer_combine(f2);
-  { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, epi_resid, f2); }
+  const bool f2_fused = fused && i + 1 < m->L;      // its combine pass is the first LayerNorm of the next layer; the last layer's ff2 combines itself
+  if (!f2_fused) { f2.defer_combine = 0; f2.force_splits = 0; }
+  { ProfScope ps(stream, 2); rc = launch_gemm_h16(stream, dt, plan.g[PG_FF2].epi, f2); }
   if (rc) return rc;
   if (f2_fused) {
     ProfScope ps(stream, 3);
@@ -822,20 +973,16 @@ static int forward_step(const rap_model* m, const Workspace& w, hipStream_t stre
   const int TP = w.rows;
   {
     GemmParams g{};
+    gemm_into(w.plan.g[PG_EMBED], g, nullptr);
     // 16-bit residual stream: the fp32 embedding lands in the (idle) FFN buffer and is rounded to fp16 once
-    g.A = w.ax; g.lda = 64; g.W = m->Wx; g.ldw = 64; g.C = w.h16 ? w.hid1 : w.h; g.ldc = d; g.M = TP; g.N = d; g.K = 64;
-    g.resid = w.base; g.ldr = d;
-    if ((rc = launch_gemm_f32(stream, EPI_BIAS_RESID, g))) return rc;
+    g.A = w.ax; g.W = m->Wx; g.C = w.h16 ? w.hid1 : w.h; g.resid = w.base;
+    if ((rc = launch_gemm_f32(stream, w.plan.g[PG_EMBED].epi, g))) return rc;
     if (w.h16 && (rc = launch_convert_f16_sat(stream, w.hid1, w.h16, (size_t)TP * d))) return rc;
   }
-  // Few-token calls of the 16-bit / split-precision blocks (round 6; the reference's everyday batch_size: 1, RAP_inference.yaml:30-36): every
-  // residual GEMM leaves fp32 partial planes (split-K where gemm_h16_splits says so, one plane otherwise) and ONE kernel forms the new
-  // residual-stream value and the LayerNorm that follows it (launch_resid_combine_ln_h16) -- 11 launches per layer instead of 14.  The planes
-  // live in the split-K buffer, which exists exactly for the calls this is meant for (<= 128 tiles of 128 x 128 in the N = d GEMMs).
-  const bool fused = g_rap_small_fused && w.dtype != RAP_DT_F32 && w.splitk_h != nullptr && g_rap_gemm_splitk;
+  // (few-token calls of the 16-bit / split-precision blocks fold every combine pass into the following LayerNorm: plan_call, CallPlan::fused)
   for (int i = 0; i < m->L; ++i) {
     rc = w.dtype == RAP_DT_F32 ? block_f32(m, w, stream, i, mod, mod_stride, token_row)
-                               : block_h16(m, w, stream, i, mod, mod_stride, token_row, TP_valid, fused);
+                               : block_h16(m, w, stream, i, mod, mod_stride, token_row, TP_valid);
     if (rc) return rc;
   }
   // 16-bit residual stream: the fp32 head (and the caller's transformer_features) read an fp32 image of it -- written into the
@@ -854,18 +1001,18 @@ static int forward_step(const rap_model* m, const Workspace& w, hipStream_t stre
     }
   }
   // final_mlp (point_cloud_dit.py:111-117): Lin+SiLU, Lin+SiLU, Lin(no bias)
-  GemmParams h0{};
-  h0.A = h_final; h0.lda = d; h0.W = m->hW0; h0.ldw = d; h0.C = w.hid1; h0.ldc = d; h0.M = head_rows; h0.N = d; h0.K = d; h0.bias = m->hb0;
-  // few-token calls: K of the two hidden layers over 2 / 4 blocks per tile (launch_gemm_f32 decides by the tile count); the partial planes
-  // live in the FFN buffer of the fp32 layout (4 T d floats, idle here) resp. the split-K planes of the 16-bit layouts
+  // few-token calls: K of the two hidden layers over 2 / 4 blocks per tile; the partial planes live in the FFN buffer of the fp32 layout
+  // (4 T d floats, idle here) resp. the split-K planes of the 16-bit layouts (plan_call).  The plan's M is TQ; head_rows differs from it only
+  // for a caller's feature buffer of the fp16 stream (ragged M = TP_valid on planes sized for TQ)
   float* const head_ws = w.dtype == RAP_DT_F32 ? w.ffmid : w.splitk_h;
-  const int head_planes = w.dtype == RAP_DT_F32 ? 4 : w.splitk_planes;
-  h0.splitk_ws = head_ws; h0.splitk_planes = head_planes;
-  if ((rc = launch_gemm_f32(stream, EPI_BIAS_SILU, h0))) return rc;
+  GemmParams h0{};
+  gemm_into(w.plan.g[PG_HEAD0], h0, head_ws);
+  h0.A = h_final; h0.W = m->hW0; h0.C = w.hid1; h0.M = head_rows; h0.bias = m->hb0;
+  if ((rc = launch_gemm_f32(stream, w.plan.g[PG_HEAD0].epi, h0))) return rc;
   GemmParams h2{};
-  h2.A = w.hid1; h2.lda = d; h2.W = m->hW2; h2.ldw = d; h2.C = w.hid2; h2.ldc = d / 2; h2.M = head_rows; h2.N = d / 2; h2.K = d;
-  h2.bias = m->hb2; h2.splitk_ws = head_ws; h2.splitk_planes = head_planes;
-  if ((rc = launch_gemm_f32(stream, EPI_BIAS_SILU, h2))) return rc;
+  gemm_into(w.plan.g[PG_HEAD1], h2, head_ws);
+  h2.A = w.hid1; h2.W = m->hW2; h2.C = w.hid2; h2.M = head_rows; h2.bias = m->hb2;
+  if ((rc = launch_gemm_f32(stream, w.plan.g[PG_HEAD1].epi, h2))) return rc;
   return launch_head_out3(stream, w.hid2, d / 2, m->hW4, v_out, TP_valid, d / 2);
 }
 
@@ -888,7 +1035,7 @@ extern "C" int rap_dit_forward_latent(const rap_model* m, const float* x_t, cons
   // the configuration (compute / residual dtype, qk_norm) is snapshotted into the workspace descriptor under the model's mutex; the enqueue
   // itself runs unlocked, so threads sharing a model do not serialise on a (possibly queue-bound) enqueue
   Workspace w;
-  { std::lock_guard<std::mutex> lock(m->cfg_mu); w = carve_workspace(m, TP, B, VP, B, (char*)ws); }
+  { std::lock_guard<std::mutex> lock(m->cfg_mu); w = carve_workspace(call_shape(m, TP, B, VP, B), (char*)ws); }
   if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
   w.cu_part_live = w.cu_part_s;             // prepare_static sanitises the caller's part table into it
   hipStream_t stream = (hipStream_t)stream_;
@@ -999,7 +1146,7 @@ extern "C" int rap_sample_latent(const rap_model* m, const float* cond, const fl
   const int np = B * P;
   if (!ws) return RAP_ERR_WORKSPACE;
   Workspace w;
-  { std::lock_guard<std::mutex> lock(m->cfg_mu); w = carve_workspace(m, TP, B, np, num_steps, (char*)ws); }      // see rap_dit_forward
+  { std::lock_guard<std::mutex> lock(m->cfg_mu); w = carve_workspace(call_shape(m, TP, B, np, num_steps), (char*)ws); }      // see rap_dit_forward
   if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   const int T = (int)TP;

@@ -458,6 +458,8 @@ int attention_f32_splits(int max_items, int heads, bool bounded) {
   const long blocks = (long)max_items * heads;
   return blocks <= 160 ? 4 : blocks <= 320 ? 2 : 1;
 }
+// ... and whether the split launch asks for one block per CU (launch_attention_f32: the grid holds at most ~1.5 blocks per CU)
+bool attention_f32_one_per_cu(int max_items, int heads, int splits) { return splits > 1 && (long)max_items * heads * splits <= 384; }
 
 int launch_attention_f32(hipStream_t stream, const float* qkv, float* out, int TP, int heads, const AttnWorkItem* items,
                          int max_items, const float* bound, float* part_o, float* part_l, int splits, const int32_t* cover_cu,
@@ -472,7 +474,7 @@ int launch_attention_f32(hipStream_t stream, const float* qkv, float* out, int T
     // per launch, 62.5 -> 55.3 ms per fp32 call at that size (r03 call 36; the same trick changes nothing for the 16-bit attention
     // and GEMM launches of such a call).
     unsigned dyn = 0;
-    if ((long)max_items * heads * splits <= 384) {
+    if (attention_f32_one_per_cu(max_items, heads, splits)) {
       dyn = 16384;
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_f32_kernel<4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess) {
         rap_set_last_hip_error((int)hipGetLastError());

@@ -74,6 +74,7 @@ int launch_attention_f32(hipStream_t stream, const float* qkv_headmajor, float* 
                          const AttnWorkItem* items, int max_items, const float* bound, float* part_o, float* part_l, int splits,
                          const int32_t* cover_cu = nullptr, int cover_nseg = 0);
 int attention_f32_splits(int max_items, int heads, bool bounded);
+bool attention_f32_one_per_cu(int max_items, int heads, int splits);      // the split launch keeps every CU to one block (16 KB of idle LDS)
 
 // ---------------------------------------------------------------------------------------------
 // memory-bound ring

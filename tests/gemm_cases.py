@@ -254,9 +254,10 @@ def form_of(lib, c, M=None):
 class tuned:
     """with tuned(lib, ((key, value), ...)): the keys are set inside and back at their defaults afterwards (the library has no getter;
     tests/test_gemm_cases_host.py checks DEFAULTS against the initialisers in the library's source)"""
-    DEFAULTS = {6: 1, 11: 1, 12: 1, 18: 256}
-    VARIABLES = {6: ("gemm_f32.hip", "g_rap_gemm_splitk"), 11: ("gemm_h16.hip", "g_rap_gemm_h16_persistent"),
-                 12: ("gemm_f32.hip", "g_rap_gemm_f32_persistent"), 18: ("gemm_h16.hip", "g_rap_ring_blocks")}
+    DEFAULTS = {5: 1, 6: 1, 11: 1, 12: 1, 17: 1024, 18: 256, 19: 1, 20: 1}
+    VARIABLES = {5: ("attn_f32.hip", "g_rap_attn_split"), 6: ("gemm_f32.hip", "g_rap_gemm_splitk"), 11: ("gemm_h16.hip", "g_rap_gemm_h16_persistent"),
+                 12: ("gemm_f32.hip", "g_rap_gemm_f32_persistent"), 17: ("api.hip", "g_rap_x2_min_rows"), 18: ("gemm_h16.hip", "g_rap_ring_blocks"),
+                 19: ("api.hip", "g_rap_small_fused"), 20: ("attn_h16.hip", "g_rap_attn_h16_small")}
 
     def __init__(self, lib, pairs):
         self.lib, self.pairs = lib, tuple(pairs)

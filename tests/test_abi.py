@@ -150,6 +150,17 @@ def test_new_entry_points_validate_arguments_without_a_gpu():
         assert lib.rap_set_tuning(20, v) == 0
     assert lib.rap_set_tuning(20, 1) == 0
     assert lib.rap_set_tuning(21, 1) == -1                     # (no such key)
+    # rap_call_plan (still version 6, additive): plain integers in, 21 integers out, every bad argument refused with `out` untouched
+    out = (ctypes.c_int64 * 21)(*([-7] * 21))
+    po = ctypes.cast(out, ctypes.c_void_p)
+    ok = dict(cdt=1, rdt=2, d=512, heads=8, layers=2, in_dim=0, TP=1100, B=2, nseg=6, rows=2, bounded=1, out=po, n=21)
+    call = lambda **kw: lib.rap_call_plan(*{**ok, **kw}.values())
+    for bad in (dict(out=N), dict(n=20), dict(cdt=4), dict(cdt=-1), dict(rdt=1), dict(rdt=3), dict(d=384), dict(d=1280), dict(heads=7), dict(layers=0),
+                dict(layers=65), dict(in_dim=6), dict(in_dim=516), dict(TP=0), dict(TP=-5), dict(TP=1 << 29), dict(B=0), dict(nseg=-1),
+                dict(nseg=65536), dict(rows=0)):
+        assert call(**bad) == -1 and list(out) == [-7] * 21, bad
+    assert call() == 0 and out[0] == 1 and out[1] == 1280 and out[20] > 0
+    assert call(TP=1 << 28) == -1 and call(TP=(1 << 28) - 1) == 0      # the calls themselves take TP <= (2^31 - 1) / 8
 
 
 def test_split_precision_entry_points_refuse_bad_shapes_without_a_gpu():

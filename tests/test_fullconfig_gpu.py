@@ -41,11 +41,11 @@ def dev():
     return torch.device("cuda:0")
 
 
-def _record(row):
+def _record(row, name="fullconfig_parity.jsonl"):
     out = os.path.join(ROOT, "gpurun_out")
     try:
         os.makedirs(out, exist_ok=True)
-        with open(os.path.join(out, "fullconfig_parity.jsonl"), "a") as f:
+        with open(os.path.join(out, name), "a") as f:
             f.write(json.dumps(row) + "\n")
     except OSError:
         pass
