@@ -27,6 +27,7 @@
 //  * grid = work items x heads with head = blockIdx % H (= the XCD: each XCD's L2 serves one head's K/V).
 #include "half.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 #define HKV 64
 #define HLD 72   // LDS row stride in 16-bit elements (144 B)
@@ -137,19 +138,13 @@ __global__ __launch_bounds__(512, 2) void attention_h16_kernel(const u16* __rest
   const int dls = ((tid & 7) ^ ((drow >> 1) & 7)) * 8;              // logical slot (in elements) this lane fetches
   const unsigned lds_k = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) u16*)Ks + (unsigned)(tid >> 6) * 1024u);
   const unsigned lds_v = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) u16*)Vs + (unsigned)(tid >> 6) * 1024u);
-#define HATT_DMA1(GSRC, LDSB)                                                                                 \
-  {                                                                                                           \
-    unsigned keep_;                                                                                           \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                 : "=&s"(keep_) : "v"(GSRC), "s"(LDSB) : "memory");                                           \
-  }
 #define HATT_DMA(T, BUF)                                                                             \
   {                                                                                                  \
     const int blk_ = b_first + (T);                                                                  \
     int tok_ = blk_ * 64 + drow;                                                                     \
     tok_ = tok_ < TP ? tok_ : TP - 1;                                                                \
-    HATT_DMA1(Kg + (size_t)tok_ * 64 + dls, lds_k + (unsigned)(BUF) * (HKV * 64 * 2))                \
-    HATT_DMA1(Vg + ((size_t)blk_ * 64 + drow) * 64 + dls, lds_v + (unsigned)(BUF) * (HKV * 64 * 2))  \
+    LDS_DMA_X4(Kg + (size_t)tok_ * 64 + dls, lds_k + (unsigned)(BUF) * (HKV * 64 * 2))                        \
+    LDS_DMA_X4(Vg + ((size_t)blk_ * 64 + drow) * 64 + dls, lds_v + (unsigned)(BUF) * (HKV * 64 * 2))          \
   }
 
   if (DMA) {
@@ -370,8 +365,8 @@ __global__ __launch_bounds__(512, 2) void attention_h16_kgroup_kernel(const u16*
       int tok_ = blk_ * 64 + drow;                                                                    \
       tok_ = tok_ < TP ? tok_ : TP - 1;                                                               \
       const unsigned slot_ = (unsigned)((((J) % NSTG) * KG + gg_) * (TILE * 2));                      \
-      HATT_DMA1(Kg + (size_t)tok_ * 64 + dls, lds_k + slot_)                                          \
-      HATT_DMA1(Vg + ((size_t)blk_ * 64 + drow) * 64 + dls, lds_v + slot_)                            \
+      LDS_DMA_X4(Kg + (size_t)tok_ * 64 + dls, lds_k + slot_)                                                 \
+      LDS_DMA_X4(Vg + ((size_t)blk_ * 64 + drow) * 64 + dls, lds_v + slot_)                                   \
     }                                                                                                 \
   }
 #pragma unroll

@@ -21,6 +21,7 @@
 // Few-token launches split every work item over 2 / 4 key ranges (SPLIT; attention_x2_combine_kernel merges the online-softmax partials).
 #include "half.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 #define XKV 64
 #define XSUB (64 * 64)         // 16-bit elements of one sub-tile (8 KB)
@@ -99,22 +100,16 @@ __global__ __launch_bounds__(512, WPE) void attention_x2_kernel(const u16* __res
   const int drow = wave * 8 + (lane >> 3);
   const int dls = ((lane & 7) ^ ((drow >> 1) & 7)) * 8;              // logical slot (in elements) this lane fetches
   const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) u16*)smem + (unsigned)wave * 1024u);
-#define XATT_DMA1(GSRC, LDSB)                                                                                 \
-  {                                                                                                           \
-    unsigned keep_;                                                                                           \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                 : "=&s"(keep_) : "v"(GSRC), "s"(LDSB) : "memory");                                           \
-  }
 #define XATT_DMA(T, BUF)                                                                                      \
   {                                                                                                           \
     const int blk_ = b_first + (T);                                                                           \
     int tok_ = blk_ * 64 + drow;                                                                              \
     tok_ = tok_ < TP ? tok_ : TP - 1;                                                                         \
     const unsigned st_ = lds_base + (unsigned)(BUF) * (4 * XSUB * 2);                                         \
-    XATT_DMA1(Kg + (size_t)tok_ * 64 + dls, st_)                                                              \
-    XATT_DMA1(Kg + ((size_t)TP + tok_) * 64 + dls, st_ + XSUB * 2)                                            \
-    XATT_DMA1(Vg + ((size_t)(2 * blk_) * 64 + drow) * 64 + dls, st_ + 2 * XSUB * 2)                           \
-    XATT_DMA1(Vg + ((size_t)(2 * blk_ + 1) * 64 + drow) * 64 + dls, st_ + 3 * XSUB * 2)                       \
+    LDS_DMA_X4(Kg + (size_t)tok_ * 64 + dls, st_)                                                             \
+    LDS_DMA_X4(Kg + ((size_t)TP + tok_) * 64 + dls, st_ + XSUB * 2)                                           \
+    LDS_DMA_X4(Vg + ((size_t)(2 * blk_) * 64 + drow) * 64 + dls, st_ + 2 * XSUB * 2)                          \
+    LDS_DMA_X4(Vg + ((size_t)(2 * blk_ + 1) * 64 + drow) * 64 + dls, st_ + 3 * XSUB * 2)                      \
   }
 
   if (ntile > 0) { XATT_DMA(0, 0) }

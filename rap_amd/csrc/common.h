@@ -30,6 +30,19 @@ typedef std::atomic<int> rap_tuning_t;
 
 void rap_set_last_hip_error(int e);
 
+// Launch of a kernel that takes its one parameter struct by value and needs more than the default 64 KB of dynamic LDS: raise the
+// kernel's limit (per device and cheap, so set unconditionally: a process may drive several GPUs), launch, check.
+template <typename P>
+static int rap_launch_dyn_lds(void (*kern)(P), dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const P& p) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {
+    rap_set_last_hip_error((int)hipGetLastError());
+    return RAP_ERR_HIP;
+  }
+  hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, p);
+  RAP_LAUNCH_CHECK();
+  return RAP_OK;
+}
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

@@ -21,6 +21,7 @@
 #include <type_traits>
 #include "half.h"
 #include "kernels.h"
+#include "lds_dma.h"
 
 #define GBM 128
 #define GBN 128
@@ -149,22 +150,14 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_dma_kernel(GemmParams p) {
   const int b_row = 2 * 4096 + (wn * 64 + l31) * 32;
   const int co0 = ((0 + hi) ^ sw) * 4, co1 = ((2 + hi) ^ sw) * 4, co2 = ((4 + hi) ^ sw) * 4, co3 = ((6 + hi) ^ sw) * 4;
 
-  // The DMA is issued from inline asm: through the builtin, hipcc (ROCm 7.2) treats the transfer as an LDS write that
-  // may alias every later ds_read and drains it (s_waitcnt vmcnt(0)) before the first fragment read of the SAME
-  // iteration, which serialises the whole pipeline.  Hidden in asm, the transfer is retired by the explicit
+  // The DMA is issued from inline asm, not through the builtin (lds_dma.h); the transfer is retired by the explicit
   // vmcnt(0) in front of the barrier that publishes the tile (DG_SYNC).
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float*)smem;
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);   // + chunk bytes below
-#define DG_DMA1(GSRC, LDSB)                                                                                   \
-  {                                                                                                           \
-    unsigned keep_;                                                                                           \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                 : "=&s"(keep_) : "v"(GSRC), "s"(LDSB) : "memory");                                           \
-  }
 #define DG_DMA(KT, BUF)                                                                                       \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                             \
-    DG_DMA1(a_src[i] + (size_t)(KT) * GBK, lds_wave + (unsigned)(((BUF) * 4096 + i * 1024) * 4))              \
-    DG_DMA1(w_src[i] + (size_t)(KT) * GBK, lds_wave + (unsigned)((8192 + (BUF) * 4096 + i * 1024) * 4))       \
+    LDS_DMA_X4(a_src[i] + (size_t)(KT) * GBK, lds_wave + (unsigned)(((BUF) * 4096 + i * 1024) * 4))           \
+    LDS_DMA_X4(w_src[i] + (size_t)(KT) * GBK, lds_wave + (unsigned)((8192 + (BUF) * 4096 + i * 1024) * 4))    \
   }
 #define DG_SYNC asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads();
 #define DG_RD(OFF) (*reinterpret_cast<const float4*>(&smem[OFF]))
@@ -514,17 +507,11 @@ __global__ __launch_bounds__(512) void gemm_f32_dma256_kernel(GemmParams p) {
   const int b_row = (wn * TN * 32 + l31) * 128;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem256;
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
-#define BG_DMA1(GSRC, LDSB)                                                                                   \
-  {                                                                                                           \
-    unsigned keep_;                                                                                           \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                 : "=&s"(keep_) : "v"(GSRC), "s"(LDSB) : "memory");                                           \
-  }
 #define BG_DMA(KT, BUF)                                                                                       \
   _Pragma("unroll") for (int i = 0; i < CA; ++i)                                                              \
-    BG_DMA1(a_src[i] + (size_t)(KT) * GBK, lds_wave + (unsigned)((BUF) * ABYTES + i * NT * 16))               \
+    LDS_DMA_X4(a_src[i] + (size_t)(KT) * GBK, lds_wave + (unsigned)((BUF) * ABYTES + i * NT * 16))            \
   _Pragma("unroll") for (int i = 0; i < CB; ++i)                                                              \
-    BG_DMA1(w_src[i] + (size_t)(KT) * GBK, lds_wave + (unsigned)(2 * ABYTES + (BUF) * BBYTES + i * NT * 16))
+    LDS_DMA_X4(w_src[i] + (size_t)(KT) * GBK, lds_wave + (unsigned)(2 * ABYTES + (BUF) * BBYTES + i * NT * 16))
 #define BG_SYNC asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads();
 #define BG_FENCE __builtin_amdgcn_sched_barrier(0);
 
@@ -640,17 +627,11 @@ __global__ __launch_bounds__(512) void gemm_f32_dma256p_kernel(GemmParams p) {
   const int b_row = (wn * TN * 32 + l31) * 128;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem256;
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
-#define BP_DMA1(VOFF, SBASE, LDSB)                                                                            \
-  {                                                                                                           \
-    unsigned keep_;                                                                                           \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0" \
-                 : "=&s"(keep_) : "v"(VOFF), "s"(LDSB), "s"(SBASE) : "memory");                                \
-  }
 #define BP_DMA(ABASE, WBASE, BUF)                                                                             \
   _Pragma("unroll") for (int i = 0; i < CA; ++i)                                                              \
-    BP_DMA1(a_off[i], ABASE, lds_wave + (unsigned)((BUF) * ABYTES + i * NT * 16))                             \
+    LDS_DMA_X4_SADDR(a_off[i], ABASE, lds_wave + (unsigned)((BUF) * ABYTES + i * NT * 16))                    \
   _Pragma("unroll") for (int i = 0; i < CB; ++i)                                                              \
-    BP_DMA1(w_off[i], WBASE, lds_wave + (unsigned)(2 * ABYTES + (BUF) * BBYTES + i * NT * 16))
+    LDS_DMA_X4_SADDR(w_off[i], WBASE, lds_wave + (unsigned)(2 * ABYTES + (BUF) * BBYTES + i * NT * 16))
   // raw barrier (no memory fence needed: LDS-DMA arrival is confirmed by this wave's vmcnt, fragment reads of the stage that the next
   // DMA overwrites by lgkmcnt -- they were issued one MFMA group earlier, so the wait is free)
 #define BP_SYNC asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0);
@@ -758,39 +739,31 @@ rap_tuning_t g_rap_gemm_variant = 48;
 
 rap_tuning_t g_rap_gemm_f32_persistent = 1;     // tuning key 12: the persistent 256 x 256 kernel for full-tile shapes (1, default) or one tile per block (0)
 
+// Grid of the persistent 256 x 256 kernels, here and in gemm_h16.hip (kernels.h)
+int rap_persistent_blocks(int tiles) {
+  static std::atomic<int> n_cu_cache[16] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  int n_cu = (dev >= 0 && dev < 16) ? n_cu_cache[dev].load() : 0;
+  if (n_cu == 0) {
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) return 0;
+    n_cu = n_cu >= 8 ? (n_cu / 8) * 8 : n_cu;     // a multiple of the XCD count: a block's virtual ids stay on its XCD
+    if (dev >= 0 && dev < 16) n_cu_cache[dev] = n_cu;
+  }
+  return tiles < n_cu ? tiles : n_cu;
+}
+
 template <int EPI>
 static int launch_gemm_variant(hipStream_t stream, const GemmParams& p, int form) {
-  const int mt = (p.M + GBM - 1) / GBM;
-  if (form / 100 == RAP_FORM_256P) {
-    constexpr int LDS = 2 * (256 + 256) * 128;
-    auto kern = gemm_f32_dma256p_kernel<EPI>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      rap_set_last_hip_error((int)hipGetLastError());
-      return RAP_ERR_HIP;
-    }
-    static std::atomic<int> n_cu_cache[16] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return RAP_ERR_HIP;
-    int n_cu = (dev >= 0 && dev < 16) ? n_cu_cache[dev].load() : 0;
-    if (n_cu == 0) {
-      if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) return RAP_ERR_HIP;
-      n_cu = n_cu >= 8 ? (n_cu / 8) * 8 : n_cu;
-      if (dev >= 0 && dev < 16) n_cu_cache[dev] = n_cu;
-    }
-    const int total = (p.M / 256) * (p.N / 256);
-    hipLaunchKernelGGL(kern, dim3(total < n_cu ? total : n_cu), dim3(512), LDS, stream, p);
-  } else if (form / 100 == RAP_FORM_256) {
-    constexpr int LDS = 2 * (256 + 256) * 128;
-    auto kern = gemm_f32_dma256_kernel<EPI>;
-    // per device and cheap: set unconditionally (a process may drive several GPUs)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      rap_set_last_hip_error((int)hipGetLastError());
-      return RAP_ERR_HIP;
-    }
-    hipLaunchKernelGGL(kern, dim3(((p.M + 255) / 256) * (p.N / 256)), dim3(512), LDS, stream, p);
-  } else {
-    hipLaunchKernelGGL(gemm_f32_dma_kernel<EPI>, dim3(mt * (p.N / GBN)), dim3(256), 0, stream, p);
+  constexpr int LDS256 = 2 * (256 + 256) * 128;
+  if (rap_form_kernel(form) == RAP_FORM_256P) {
+    const int blocks = rap_persistent_blocks((p.M / 256) * (p.N / 256));
+    if (blocks <= 0) return RAP_ERR_HIP;
+    return rap_launch_dyn_lds(gemm_f32_dma256p_kernel<EPI>, dim3(blocks), dim3(512), LDS256, stream, p);
   }
+  if (rap_form_kernel(form) == RAP_FORM_256)
+    return rap_launch_dyn_lds(gemm_f32_dma256_kernel<EPI>, dim3(((p.M + 255) / 256) * (p.N / 256)), dim3(512), LDS256, stream, p);
+  hipLaunchKernelGGL(gemm_f32_dma_kernel<EPI>, dim3(((p.M + GBM - 1) / GBM) * (p.N / GBN)), dim3(256), 0, stream, p);
   RAP_LAUNCH_CHECK();
   return RAP_OK;
 }
@@ -847,7 +820,7 @@ int launch_gemm_f32(hipStream_t stream, int epilogue, const GemmParams& p_in) {
   p.stagger = ((long)((p.M + GBM - 1) / GBM) * (p.N / GBN) >= 1024) ? g_rap_gemm_stagger.load() : 0;     // only when the chip is filled twice over
   const int form = gemm_f32_form(epilogue, p);
   if (form <= 0) return form;      // nothing to do (M <= 0) or a refused shape
-  const int splits = form % 10;
+  const int splits = rap_form_splits(form);
   if (splits > 1) {                // partial tiles to splitk_ws, then one combine pass (residual + bias + partials, or SiLU of bias + partials)
     hipLaunchKernelGGL(gemm_f32_dma_kernel<EPI_SPLITK_PART>, dim3(((p.M + GBM - 1) / GBM) * (p.N / GBN), splits), dim3(256), 0, stream, p);
     RAP_LAUNCH_CHECK();

@@ -21,452 +21,13 @@
 #include <type_traits>
 #include "half.h"
 #include "kernels.h"
+#include "lds_dma.h"
+#include "gemm_h16_epilogue.h"
 
-// exact-erf GELU through the Abramowitz-Stegun 7.1.26 complementary error function (|error| <= 1.5e-7, far below
-// one rounding of the 16-bit output): q = erfc(|g| / sqrt 2);  gelu(g) = g < 0 ? g q / 2 : g (1 - q / 2).
-// ~15 VALU instructions instead of erff's ~45 -- at 16x the fp32 MFMA rate the GEGLU epilogue was as long as the k-loop.
-__device__ __forceinline__ float gelu_erf_fast(float g) {
-  const float x = fabsf(g) * 0.70710678118654752440f;
-  const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, x, 1.0f));
-  float poly = __builtin_fmaf(t, 1.061405429f, -1.453152027f);
-  poly = __builtin_fmaf(t, poly, 1.421413741f);
-  poly = __builtin_fmaf(t, poly, -0.284496736f);
-  poly = __builtin_fmaf(t, poly, 0.254829592f);
-  poly *= t;
-  const float q = poly * __builtin_amdgcn_exp2f(-x * x * 1.44269504088896340736f);
-  return g < 0.f ? 0.5f * g * q : g * (1.0f - 0.5f * q);
-}
-
-// Two GEGLU outputs per call on the packed fp32 pipe (r02): the epilogue is VALU-bound -- r01's ablation prices it at 0.42 ms of the
-// 1.6 ms ff1 GEMM, and the disassembly showed ~24 scalar VALU instructions per output (nothing packed).  Here every multiply / FMA of
-// the polynomial handles two outputs (v_pk_mul_f32 / v_pk_fma_f32: twice the fp32 rate when no MFMA is in flight), the branch of
-// gelu_erf_fast becomes Phi(g) = 1/2 + copysign(1/2 - q/2, g), and the two results leave as ONE v_cvt_pk: ~13 instructions per output.
-// ---------------- epilogue (shared by the kernels below) ----------------
-// acc[i][j][r] = C[mw + 32 i + crow(r, hi)][nw + 32 j + l31]: a lane owns ONE column, so direct stores would be
-// 2- or 4-byte scatters (measured: the out-projection ran at 147 TF, 4x its HBM floor).  Every wave therefore
-// transposes its tile through a private LDS slab `stg` (the operand buffers are dead by now; the caller has
-// synchronised the block) and writes whole rows with 16-byte stores; the fp32 residual is read the same way.
-#define H16_STG_BYTES (64 * 144)   // largest slab: the V^T image of 64 tokens (64 d rows of 144 bytes)
-// RAP_MUTATION (scripts/mutation_check.sh only, never in the shipped library): a deliberately injected extra rounding to the OPERAND type
-// in the residual epilogues -- 1: of the epilogue's result (the new residual-stream value), 2: of the GEMM output before the residual is
-// added -- to show that the tightened 16-bit deviation bounds of the test-suite notice a precision regression.
-#ifdef RAP_MUTATION
-template <int DT> __device__ __forceinline__ float rap_mut_round(float x) { return h16_to_f32<DT>(h16_from_f32<DT>(x)); }
-#define RAP_MUT_OUT(DT, x) (RAP_MUTATION == 2 ? rap_mut_round<DT>(x) : (x))
-#define RAP_MUT_SUM(DT, x) (RAP_MUTATION == 1 ? rap_mut_round<DT>(x) : (x))
-#else
-#define RAP_MUT_OUT(DT, x) (x)
-#define RAP_MUT_SUM(DT, x) (x)
-#endif
-template <int EPI, int DT, int TM>
-__device__ __forceinline__ void gemm_h16_epilogue(const GemmParamsH& p, f32x16 (&acc)[TM][2], unsigned char* stg, int mw, int nw,
-                                                  int lane) {
-  const int hi = lane >> 5, l31 = lane & 31;
-  if constexpr (EPI == EPI_H_GEGLU) {
-    u16* C = reinterpret_cast<u16*>(p.C);
-    u16* sh = reinterpret_cast<u16*>(stg);       // [32 rows][32 outputs]
-    const float bh = p.bias ? p.bias[nw + l31] : 0.f;
-    const float bg = p.bias ? p.bias[nw + 32 + l31] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      f32x2 h2[8], g2[8], o2[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        h2[j] = f32x2{acc[i][0][2 * j], acc[i][0][2 * j + 1]} + f32x2{bh, bh};
-        g2[j] = f32x2{acc[i][1][2 * j], acc[i][1][2 * j + 1]} + f32x2{bg, bg};
-      }
-      geglu_pairs<8>(h2, g2, o2);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const unsigned pk = __builtin_bit_cast(unsigned, __builtin_convertvector(o2[j], typename H16<DT>::T2));   // one v_cvt_pk for both
-        sh[mfma32_crow(2 * j, hi) * 32 + l31] = (u16)(pk & 0xffffu);
-        sh[mfma32_crow(2 * j + 1, hi) * 32 + l31] = (u16)(pk >> 16);
-      }
-#pragma unroll
-      for (int it = 0; it < 2; ++it) {
-        const int row = it * 16 + (lane >> 2), col = (lane & 3) * 8;
-        const uint4 v = *reinterpret_cast<const uint4*>(sh + row * 32 + col);
-        const int m = mw + i * 32 + row;
-        if (m < p.M) *reinterpret_cast<uint4*>(C + (size_t)m * p.ldc + (nw >> 1) + col) = v;
-      }
-    }
-    return;
-  }
-  if constexpr (EPI == EPI_H_BIAS_RESID_F32) {
-    // (r02 call 39: requesting the residual rows of slab i + 1 while slab i is transposed and stored -- rolling through one register
-    // set, or two sets -- pushes this 225-VGPR kernel over 256 and spills in the epilogue: out-projection 0.32 -> 0.33 ms, ff2 unchanged.
-    // Both GEMMs are bound by this fp32 read-modify-write of the residual stream, 1.34 / 2.4 GB per call at 4.2 / 3.8 TB/s.)
-    float* C = reinterpret_cast<float*>(p.C);
-    float* sf = reinterpret_cast<float*>(stg);   // [32 rows][64 columns]
-    const float b0 = p.bias ? p.bias[nw + l31] : 0.f;
-    const float b1 = p.bias ? p.bias[nw + 32 + l31] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      float4 rr[8];
-      if (p.resid) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          int m = mw + i * 32 + it * 4 + (lane >> 4);
-          m = m < p.M ? m : p.M - 1;
-          rr[it] = *reinterpret_cast<const float4*>(p.resid + (size_t)m * p.ldr + nw + (lane & 15) * 4);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        sf[mfma32_crow(r, hi) * 64 + l31] = RAP_MUT_OUT(DT, acc[i][0][r] + b0);
-        sf[mfma32_crow(r, hi) * 64 + 32 + l31] = RAP_MUT_OUT(DT, acc[i][1][r] + b1);
-      }
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int row = it * 4 + (lane >> 4), col = (lane & 15) * 4;
-        float4 v = *reinterpret_cast<const float4*>(sf + row * 64 + col);
-        if (p.resid) { v.x += rr[it].x; v.y += rr[it].y; v.z += rr[it].z; v.w += rr[it].w; }
-        v.x = RAP_MUT_SUM(DT, v.x); v.y = RAP_MUT_SUM(DT, v.y); v.z = RAP_MUT_SUM(DT, v.z); v.w = RAP_MUT_SUM(DT, v.w);
-        const int m = mw + i * 32 + row;
-        if (m < p.M) *reinterpret_cast<float4*>(C + (size_t)m * p.ldc + nw + col) = v;
-      }
-    }
-    return;
-  }
-  if constexpr (EPI == EPI_H_BIAS_RESID_H16) {
-    // The residual GEMMs of the 16-bit residual stream (round 3): C fp16 = fp16(resid_h + acc + bias), the sum formed in fp32 from the
-    // fp32 accumulators and rounded ONCE.  Half the bytes of the fp32 read-modify-write that bounds EPI_H_BIAS_RESID_F32.  fp32
-    // transposition slab as above; a lane then owns 8 consecutive columns of a row: two float4 from the slab, one 16-byte piece of the
-    // fp16 residual in, one 16-byte piece out.  ALL residual pieces of the wave tile (TM x 4 x 16 bytes per lane = 64 VGPRs, the
-    // registers the operand fragments occupied during the k-loop) are requested before the first slab is transposed, so the HBM
-    // latency is paid once per tile, not once per 32-row slab (the fp32 form needs 128 registers for that and spilled, r02 call 39).
-    u16* C = reinterpret_cast<u16*>(p.C);
-    float* sf = reinterpret_cast<float*>(stg);   // [32 rows][68 floats]: 64 columns + 4 pad (the 8-lanes-per-row reads stay off each other's banks)
-    const float b0 = p.bias ? p.bias[nw + l31] : 0.f;
-    const float b1 = p.bias ? p.bias[nw + 32 + l31] : 0.f;
-    // the (L2-hot) bias has landed before the residual requests go out: the slab writes below then wait for nothing, and every
-    // residual piece is waited for with its own counted vmcnt
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int col = (lane & 7) * 8;
-    uint4 rr[TM][4];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        int m = mw + i * 32 + it * 8 + (lane >> 3);
-        m = m < p.M ? m : p.M - 1;
-        rr[i][it] = *reinterpret_cast<const uint4*>(p.resid_h + (size_t)m * p.ldr + nw + col);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        sf[mfma32_crow(r, hi) * 68 + l31] = RAP_MUT_OUT(DT, acc[i][0][r] + b0);
-        sf[mfma32_crow(r, hi) * 68 + 32 + l31] = RAP_MUT_OUT(DT, acc[i][1][r] + b1);
-      }
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3);
-        const float4 a0 = *reinterpret_cast<const float4*>(sf + row * 68 + col);
-        const float4 a1 = *reinterpret_cast<const float4*>(sf + row * 68 + col + 4);
-        float rv[8];
-        h16_unpack8<RAP_DT_F16>(rr[i][it], rv);
-        const typename H16<RAP_DT_F16>::T8 o8 = f16_pack8_sat(RAP_MUT_SUM(DT, a0.x + rv[0]), RAP_MUT_SUM(DT, a0.y + rv[1]), RAP_MUT_SUM(DT, a0.z + rv[2]),
-                                                             RAP_MUT_SUM(DT, a0.w + rv[3]), RAP_MUT_SUM(DT, a1.x + rv[4]), RAP_MUT_SUM(DT, a1.y + rv[5]),
-                                                             RAP_MUT_SUM(DT, a1.z + rv[6]), RAP_MUT_SUM(DT, a1.w + rv[7]));
-        const int m = mw + i * 32 + row;
-        if (m < p.M) *reinterpret_cast<uint4*>(C + (size_t)m * p.ldc + nw + col) = __builtin_bit_cast(uint4, o8);
-      }
-    }
-    return;
-  }
-  if constexpr (EPI == EPI_H_BIAS || EPI == EPI_H_QKV) {
-    u16* sh = reinterpret_cast<u16*>(stg);
-    int c = 0, h = 0;
-    if constexpr (EPI == EPI_H_QKV) {
-      const int dmodel = p.heads * 64;
-      c = nw / dmodel;                             // wave-uniform: the 64-column wave tile is one head of q, k or v
-      h = (nw - c * dmodel) >> 6;
-    }
-    if (EPI == EPI_H_QKV && c == 2) {
-      // V goes out TRANSPOSED and blocked by 64 tokens: vt[h][token >> 6][d][vt_pos(token & 63)].  Two 32-token slabs
-      // (= one block) are staged as [64 d][64 pos] (row stride 144 B) and written as one contiguous 8 KiB block.
-      // Rows >= M (tile padding) are zeros: masked keys must contribute 0 * finite in the P*V product.
-#pragma unroll
-      for (int ip = 0; ip < TM / 2; ++ip) {
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const int i = 2 * ip + ii;
-              const int mb = mw + i * 32 + 8 * g + 4 * hi;          // first of 4 consecutive tokens
-              float v0 = acc[i][j][4 * g + 0], v1 = acc[i][j][4 * g + 1], v2 = acc[i][j][4 * g + 2], v3 = acc[i][j][4 * g + 3];
-              v0 = (mb + 0 < p.M) ? v0 : 0.f; v1 = (mb + 1 < p.M) ? v1 : 0.f;
-              v2 = (mb + 2 < p.M) ? v2 : 0.f; v3 = (mb + 3 < p.M) ? v3 : 0.f;
-              const int pos0 = 32 * ii + 16 * (g >> 1) + 8 * hi + 4 * (g & 1);   // = vt_pos(32 ii + 8 g + 4 hi)
-              *reinterpret_cast<uint2*>(sh + (j * 32 + l31) * 72 + pos0) = h16_pack4<DT>(v0, v1, v2, v3);
-            }
-          }
-        }
-        u16* dst = p.vt + ((size_t)h * p.vt_nblk + ((mw + 64 * ip) >> 6)) * (64 * 64);
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int d = it * 8 + (lane >> 3), ch = (lane & 7) * 8;
-          *reinterpret_cast<uint4*>(dst + d * 64 + ch) = *reinterpret_cast<const uint4*>(sh + d * 72 + ch);
-        }
-      }
-      return;
-    }
-    const float b0 = (EPI == EPI_H_BIAS && p.bias) ? p.bias[nw + l31] : 0.f;
-    const float b1 = (EPI == EPI_H_BIAS && p.bias) ? p.bias[nw + 32 + l31] : 0.f;
-    u16* C = reinterpret_cast<u16*>(p.C);
-    // q / k plane [c][h][m][64]: the wave's rows are contiguous 128-byte lines; EPI_H_BIAS: row-major (M, ldc)
-    const size_t row_stride = (EPI == EPI_H_QKV) ? 64 : (size_t)p.ldc;
-    u16* base = (EPI == EPI_H_QKV) ? C + ((size_t)(c * p.heads + h) * p.M) * 64 : C + nw;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        sh[mfma32_crow(r, hi) * 64 + l31] = h16_from_f32<DT>(acc[i][0][r] + b0);
-        sh[mfma32_crow(r, hi) * 64 + 32 + l31] = h16_from_f32<DT>(acc[i][1][r] + b1);
-      }
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3), col = (lane & 7) * 8;
-        const uint4 v = *reinterpret_cast<const uint4*>(sh + row * 64 + col);
-        const int m = mw + i * 32 + row;
-        if (m < p.M) *reinterpret_cast<uint4*>(base + (size_t)m * row_stride + col) = v;
-      }
-    }
-  }
-}
-
-// ---------------- fused q / k epilogue of EPI_H_QKV_NORM (swapped product) ----------------
-// acc[i][j][r] = C[mw + 32 i + l31][nw + 32 j + crow(r, hi)]: the lane owns token row mw + 32 i + l31 and, of the head's 64 columns,
-// those with bit 2 equal to hi.  MultiHeadRMSNorm (flow_model/norm.py:28-33: F.normalize(x, dim=-1) * gamma * sqrt(64)) needs the
-// row's sum of squares: 32 lane-local terms + the partner lane's (lane ^ 32, one v_permlane32_swap).  q additionally carries
-// q_mul / 8 (the attention kernel's pre-scaled form, see launch_qknorm_h16).  Output plane [c][h][m][64]: register groups 2t and
-// 2t+1 of the two half-waves are exchanged (v_permlane32_swap) so that a lane holds 8 CONSECUTIVE columns = one 16-byte store;
-// the four stores of a row tile cover whole 128-byte rows -- no LDS transpose.
-template <int DT, int TM>
-__device__ __forceinline__ void gemm_h16_qknorm_epilogue(const GemmParamsH& p, f32x16 (&acc)[TM][2], int mw, int nw, int lane) {
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int dmodel = p.heads * 64;
-  const int c = nw / dmodel;                      // 0 = q, 1 = k (wave-uniform)
-  const int h = (nw - c * dmodel) >> 6;
-  const float* gam = (c == 0 ? p.gamma_q : p.gamma_k) + h * 64;
-  const float mul = c == 0 ? p.q_mul : 8.0f;
-  float g[2][16];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) g[j][r] = gam[32 * j + mfma32_crow(r, hi)] * mul;
-  u16* plane = reinterpret_cast<u16*>(p.C) + ((size_t)(c * p.heads + h) * p.M) * 64;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ss = __builtin_fmaf(acc[i][j][r], acc[i][j][r], ss);
-    {
-      const auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(ss), __float_as_uint(ss), false, false);
-      ss = __uint_as_float(sw2[0]) + __uint_as_float(sw2[1]);
-    }
-    const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
-    const int m = mw + 32 * i + l31;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        float x[4], y[4];                          // groups 2t and 2t+1: columns 16t + 4hi + {0..3} and 16t + 8 + 4hi + {0..3}
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float vx = acc[i][j][8 * t + e] * inv * g[j][8 * t + e];
-          const float vy = acc[i][j][8 * t + 4 + e] * inv * g[j][8 * t + 4 + e];
-          const auto s2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(vx), __float_as_uint(vy), false, false);
-          x[e] = __uint_as_float(s2[0]); y[e] = __uint_as_float(s2[1]);
-        }
-        // hi = 0: x = own group 2t (cols 16t + 0..3), y = partner's group 2t (cols 16t + 4..7)      -> columns 16t + 0..7
-        // hi = 1: x = partner's group 2t+1 (cols 16t + 8..11), y = own group 2t+1 (cols 16t + 12..15) -> columns 16t + 8..15
-        const typename H16<DT>::T8 o8 = h16_pack8<DT>(x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]);
-        if (m < p.M) *reinterpret_cast<uint4*>(plane + (size_t)m * 64 + 32 * j + 16 * t + 8 * hi) = __builtin_bit_cast(uint4, o8);
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Split-precision epilogues (RAP_DT_F32X2, round 5; half.h).  The accumulators hold acc_scale^-1 times the fp32-accurate product
-// (weights are stored pre-multiplied by a power of two, see rap_model_set_compute_dtype); 16-bit outputs leave as fp16 head / tail
-// planes in the paired layout: the 64 physical columns of a wave tile's line are [32 heads | 32 tails] of ONE 32-column chunk.
-// Same transposition slabs as above (<= H16_STG_BYTES per wave).
-//   EPI_H_BIAS_RESID_F32: C fp32 (M,N) = resid + acc * scale + bias                       (out-projection, ff2)
-//   EPI_H_GEGLU:          C paired (M, 2 * N/2) = split((h + bh) * gelu_erf(g + bg))      (ff1; wave tile = 32 outputs = one chunk)
-//   EPI_H_QKV (c == 2):   vt paired [H][blk][2 chunks][64 d][32 heads | 32 tails] in vt_pos order (chunk = bit 5 of the token index)
-// ---------------------------------------------------------------------------------------------
-template <int EPI, int TM>
-__device__ __forceinline__ void gemm_x2_epilogue(const GemmParamsH& p, f32x16 (&acc)[TM][2], unsigned char* stg, int mw, int nw, int lane) {
-  const int hi = lane >> 5, l31 = lane & 31;
-  const float sc = p.acc_scale;
-  if constexpr (EPI == EPI_H_GEGLU) {
-    u16* C = reinterpret_cast<u16*>(p.C);
-    u16* sh = reinterpret_cast<u16*>(stg);       // [32 rows][72]: heads in columns 0..31, tails in 32..63
-    const float bh = p.bias ? p.bias[nw + l31] : 0.f;
-    const float bg = p.bias ? p.bias[nw + 32 + l31] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      f32x2 h2[8], g2[8], o2[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        h2[j] = __builtin_elementwise_fma(f32x2{acc[i][0][2 * j], acc[i][0][2 * j + 1]}, f32x2{sc, sc}, f32x2{bh, bh});
-        g2[j] = __builtin_elementwise_fma(f32x2{acc[i][1][2 * j], acc[i][1][2 * j + 1]}, f32x2{sc, sc}, f32x2{bg, bg});
-      }
-      geglu_pairs<8>(h2, g2, o2);
-      const float osc = p.out_scale;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const f32x2 s2 = {f16_sat(o2[j].x * osc), f16_sat(o2[j].y * osc)};
-        const typename H16<RAP_DT_F16>::T2 h16 = __builtin_convertvector(s2, typename H16<RAP_DT_F16>::T2);
-        const typename H16<RAP_DT_F16>::T2 l16 = __builtin_convertvector(s2 - __builtin_convertvector(h16, f32x2), typename H16<RAP_DT_F16>::T2);
-        const unsigned ph = __builtin_bit_cast(unsigned, h16), pl = __builtin_bit_cast(unsigned, l16);
-        sh[mfma32_crow(2 * j, hi) * 72 + l31] = (u16)(ph & 0xffffu);
-        sh[mfma32_crow(2 * j + 1, hi) * 72 + l31] = (u16)(ph >> 16);
-        sh[mfma32_crow(2 * j, hi) * 72 + 32 + l31] = (u16)(pl & 0xffffu);
-        sh[mfma32_crow(2 * j + 1, hi) * 72 + 32 + l31] = (u16)(pl >> 16);
-      }
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const int row = it * 8 + (lane >> 3), col = (lane & 7) * 8;
-        const uint4 v = *reinterpret_cast<const uint4*>(sh + row * 72 + col);
-        const int m = mw + i * 32 + row;
-        if (m < p.M) *reinterpret_cast<uint4*>(C + (size_t)m * p.ldc + nw + col) = v;     // physical columns of chunk nw >> 6: [nw, nw + 64)
-      }
-    }
-    return;
-  }
-  if constexpr (EPI == EPI_H_BIAS_RESID_F32) {
-    float* C = reinterpret_cast<float*>(p.C);
-    float* sf = reinterpret_cast<float*>(stg);   // [32 rows][64 columns]
-    const float b0 = p.bias ? p.bias[nw + l31] : 0.f;
-    const float b1 = p.bias ? p.bias[nw + 32 + l31] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      float4 rr[8];
-      if (p.resid) {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          int m = mw + i * 32 + it * 4 + (lane >> 4);
-          m = m < p.M ? m : p.M - 1;
-          rr[it] = *reinterpret_cast<const float4*>(p.resid + (size_t)m * p.ldr + nw + (lane & 15) * 4);
-        }
-      }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        sf[mfma32_crow(r, hi) * 64 + l31] = __builtin_fmaf(acc[i][0][r], sc, b0);
-        sf[mfma32_crow(r, hi) * 64 + 32 + l31] = __builtin_fmaf(acc[i][1][r], sc, b1);
-      }
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int row = it * 4 + (lane >> 4), col = (lane & 15) * 4;
-        float4 v = *reinterpret_cast<const float4*>(sf + row * 64 + col);
-        if (p.resid) { v.x += rr[it].x; v.y += rr[it].y; v.z += rr[it].z; v.w += rr[it].w; }
-        const int m = mw + i * 32 + row;
-        if (m < p.M) *reinterpret_cast<float4*>(C + (size_t)m * p.ldc + nw + col) = v;
-      }
-    }
-    return;
-  }
-  if constexpr (EPI == EPI_H_QKV) {
-    // the V column tiles of the fused QKV projection (normal product: a lane owns a column d and 16 of every 32 tokens)
-    u16* sh = reinterpret_cast<u16*>(stg);       // [64 d][72]: one chunk (32 tokens) of one 64-token block: 32 heads | 32 tails
-    const int dmodel = p.heads * 64;
-    const int h = (nw - 2 * dmodel) >> 6;
-    const float sc = p.acc_scale * p.out_scale;  // (shadows the function-level scale: the V planes carry out_scale, see GemmParamsH)
-#pragma unroll
-    for (int ip = 0; ip < TM / 2; ++ip) {
-#pragma unroll
-      for (int ii = 0; ii < 2; ++ii) {
-        const int i = 2 * ip + ii;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int mb = mw + i * 32 + 8 * g + 4 * hi;          // first of 4 consecutive tokens
-            float v0 = acc[i][j][4 * g + 0] * sc, v1 = acc[i][j][4 * g + 1] * sc, v2 = acc[i][j][4 * g + 2] * sc, v3 = acc[i][j][4 * g + 3] * sc;
-            v0 = (mb + 0 < p.M) ? v0 : 0.f; v1 = (mb + 1 < p.M) ? v1 : 0.f;
-            v2 = (mb + 2 < p.M) ? v2 : 0.f; v3 = (mb + 3 < p.M) ? v3 : 0.f;
-            const int inpos = 16 * (g >> 1) + 8 * hi + 4 * (g & 1);   // = vt_pos(32 ii + 8 g + 4 hi) - 32 ii
-            uint2 ph, pl;
-            x2_split4(v0, v1, v2, v3, ph, pl);
-            *reinterpret_cast<uint2*>(sh + (j * 32 + l31) * 72 + inpos) = ph;
-            *reinterpret_cast<uint2*>(sh + (j * 32 + l31) * 72 + 32 + inpos) = pl;
-          }
-        }
-        u16* dst = p.vt + (((size_t)h * p.vt_nblk + ((mw + 64 * ip) >> 6)) * 2 + ii) * (64 * 64);
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int d = it * 8 + (lane >> 3), ch = (lane & 7) * 8;
-          *reinterpret_cast<uint4*>(dst + d * 64 + ch) = *reinterpret_cast<const uint4*>(sh + d * 72 + ch);
-        }
-      }
-    }
-    return;
-  }
-}
-
-// q / k column tiles of the fused QKV projection in split precision (swapped product, cf. gemm_h16_qknorm_epilogue): the row norm in
-// fp32 from the (re-scaled) accumulators, then head / tail planes; plane [c][h][chunk][m][64 physical] (chunk = 32 head dims).
-template <int TM>
-__device__ __forceinline__ void gemm_x2_qknorm_epilogue(const GemmParamsH& p, f32x16 (&acc)[TM][2], int mw, int nw, int lane) {
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int dmodel = p.heads * 64;
-  const int c = nw / dmodel;                      // 0 = q, 1 = k (wave-uniform)
-  const int h = (nw - c * dmodel) >> 6;
-  const bool norm = p.gamma_q != nullptr;         // null gains (qk_norm = False, layer.py:103-104): q / k leave as projected
-  const float* gam = norm ? (c == 0 ? p.gamma_q : p.gamma_k) + h * 64 : nullptr;
-  const float mul = c == 0 ? p.q_mul : 8.0f;
-  const float sc = p.acc_scale;
-  float g[2][16];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) g[j][r] = norm ? gam[32 * j + mfma32_crow(r, hi)] * mul : 1.0f;
-  u16* plane = reinterpret_cast<u16*>(p.C) + (((size_t)(c * p.heads + h) * 2) * p.M) * 64;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { acc[i][j][r] *= sc; ss = __builtin_fmaf(acc[i][j][r], acc[i][j][r], ss); }
-    {
-      const auto sw2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(ss), __float_as_uint(ss), false, false);
-      ss = __uint_as_float(sw2[0]) + __uint_as_float(sw2[1]);
-    }
-    const float inv = norm ? 1.0f / fmaxf(sqrtf(ss), 1e-12f) : 1.0f;
-    const int m = mw + 32 * i + l31;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        float v8[8];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float vx = acc[i][j][8 * t + e] * inv * g[j][8 * t + e];
-          const float vy = acc[i][j][8 * t + 4 + e] * inv * g[j][8 * t + 4 + e];
-          const auto s2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(vx), __float_as_uint(vy), false, false);
-          v8[e] = __uint_as_float(s2[0]); v8[4 + e] = __uint_as_float(s2[1]);
-        }
-        x2_t8 h8, l8;
-        x2_split8(v8, h8, l8);
-        u16* dst = plane + ((size_t)j * p.M + m) * 64 + 16 * t + 8 * hi;      // chunk j of the head: dims 32 j + 16 t + 8 hi .. +7
-        if (m < p.M) {
-          *reinterpret_cast<uint4*>(dst) = __builtin_bit_cast(uint4, h8);
-          *reinterpret_cast<uint4*>(dst + 32) = __builtin_bit_cast(uint4, l8);
-        }
-      }
-    }
-  }
-}
+// Split precision (RAP_DT_F32X2, half.h): fragments 0, 1 of a k-tile are the head and 2, 3 the tail fragments of its two k-steps.  The six
+// kept products, as (A fragment, W fragment): (tail, head) and (head, tail) of both k-steps, then (head, head); OP(args..., ka, kb) each.
+#define X2_PRODUCTS(OP, ...) \
+  OP(__VA_ARGS__, 2, 0) OP(__VA_ARGS__, 0, 2) OP(__VA_ARGS__, 3, 1) OP(__VA_ARGS__, 1, 3) OP(__VA_ARGS__, 0, 0) OP(__VA_ARGS__, 1, 1)
 
 // X2 (round 5, the residual GEMMs of few-token split-precision calls): the paired-operand product of the phase-split kernels (three MFMAs
 // per fragment pair, see gemm_h16_ph_kernel) on this kernel's 128 x 128 tiles -- the four fragment sets of a k-tile (head k-steps 0, 1 and
@@ -546,21 +107,14 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 ? 1 : 2)) void gemm_h16_kerne
   const int a_row = (wm * TM * 32 + l31) * 128;                       // byte offsets inside one A / B buffer
   const int b_row = (wn * TN * 32 + l31) * 128;
 
-  // The DMA is issued from inline asm (see gemm_f32.hip: through the builtin hipcc drains it before the first
-  // fragment read of the same iteration).  m0 carries the wave-uniform LDS byte address of the 1 KiB piece.
+  // LDS-DMA (lds_dma.h) of the wave's 1 KiB pieces of a k-tile
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
-#define HG_DMA1(GSRC, LDSB)                                                                                   \
-  {                                                                                                           \
-    unsigned keep_;                                                                                           \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                 : "=&s"(keep_) : "v"(GSRC), "s"(LDSB) : "memory");                                           \
-  }
 #define HG_DMA(KT, BUF)                                                                                       \
   _Pragma("unroll") for (int i = 0; i < CA; ++i)                                                              \
-    HG_DMA1(a_src[i] + (size_t)(KT) * 64, lds_wave + (unsigned)((BUF) * ABYTES + i * NT * 16))                \
+    LDS_DMA_X4(a_src[i] + (size_t)(KT) * 64, lds_wave + (unsigned)((BUF) * ABYTES + i * NT * 16))             \
   _Pragma("unroll") for (int i = 0; i < CB; ++i)                                                              \
-    HG_DMA1(w_src[i] + (size_t)(KT) * 64, lds_wave + (unsigned)(NS * ABYTES + (BUF) * BBYTES + i * NT * 16))
+    LDS_DMA_X4(w_src[i] + (size_t)(KT) * 64, lds_wave + (unsigned)(NS * ABYTES + (BUF) * BBYTES + i * NT * 16))
 #define HG_SYNC asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads();
 #define HG_FENCE __builtin_amdgcn_sched_barrier(0);
 
@@ -575,28 +129,30 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 ? 1 : 2)) void gemm_h16_kerne
     for (int j = 0; j < TN; ++j)
       f.b[j] = *reinterpret_cast<const uint4*>(smem + NS * ABYTES + buf * BBYTES + b_row + j * 32 * 128 + co);
   };
-  auto mma = [&](const Frag& f) {
+  // acc += A rows of fa_ x W rows of fb_, or the SWAPPED product (swp_c true: the MFMA's A operand is the weight fragment)
+  auto mm = [&](auto swp_c, const Frag& fa_, const Frag& fb_) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
-      for (int j = 0; j < TN; ++j)
-        acc[i][j] = H16<DT>::mfma(__builtin_bit_cast(T8, f.a[i]), __builtin_bit_cast(T8, f.b[j]), acc[i][j]);
+      for (int j = 0; j < TN; ++j) {
+        if constexpr (decltype(swp_c)::value) acc[i][j] = H16<DT>::mfma(__builtin_bit_cast(T8, fb_.b[j]), __builtin_bit_cast(T8, fa_.a[i]), acc[i][j]);
+        else acc[i][j] = H16<DT>::mfma(__builtin_bit_cast(T8, fa_.a[i]), __builtin_bit_cast(T8, fb_.b[j]), acc[i][j]);
+      }
   };
+  auto mma = [&](const Frag& f) { mm(std::false_type{}, f, f); };
+#define HG_X2_MM(F, KA, KB) mm(swp_c, F[KA], F[KB]);      // one of the X2_PRODUCTS of a k-tile's four fragment sets F
+  constexpr bool RING = NS > 2 || (EPI == EPI_H_QKV_NORM && !X2);
+  if constexpr (!RING) {      // the two-stage loops: tile 0
+    HG_DMA(0, 0)
+    HG_SYNC
+  }
+  // EPI_H_QKV_NORM: the q / k column tiles run the swapped product (a lane owns a token row: the row norm is lane-local), as in the
+  // phase-split kernels; a compile-time property of the k-loop copy that runs.  Block-uniform: a 128-column tile is all q / k or all v.
+  const bool swp = EPI == EPI_H_QKV_NORM && (n0 + wn * 64) < 2 * p.heads * 64;
 
-  if constexpr (NS > 2 || (EPI == EPI_H_QKV_NORM && !X2)) {
+  if constexpr (RING) {
     // ---- ring of NS stages (NS = 2: the plain double buffer, for the non-X2 fused QKV tiles), swapped product on q / k column tiles
-    const bool swp = EPI == EPI_H_QKV_NORM && (n0 + wn * 64) < 2 * p.heads * 64;      // (block-uniform: a 128-column tile is all q / k or all v)
     auto ring = [&](auto swp_c) __attribute__((always_inline)) {
-      constexpr bool SWP = decltype(swp_c)::value;
-      auto mm = [&](const Frag& fa_, const Frag& fb_) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            if constexpr (SWP) acc[i][j] = H16<DT>::mfma(__builtin_bit_cast(T8, fb_.b[j]), __builtin_bit_cast(T8, fa_.a[i]), acc[i][j]);
-            else acc[i][j] = H16<DT>::mfma(__builtin_bit_cast(T8, fa_.a[i]), __builtin_bit_cast(T8, fb_.b[j]), acc[i][j]);
-          }
-      };
 #pragma unroll
       for (int s_ = 0; s_ < NS - 1; ++s_)
         if (s_ < nk) { HG_DMA(s_, s_) }
@@ -614,10 +170,9 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 ? 1 : 2)) void gemm_h16_kerne
         for (int g = 0; g < 4; ++g) read_frag(fa[g], 0, g);
         auto mul = [&](Frag (&fc)[4]) __attribute__((always_inline)) {
           if constexpr (X2) {
-            mm(fc[2], fc[0]); mm(fc[0], fc[2]); mm(fc[3], fc[1]); mm(fc[1], fc[3]);      // (tail, head), (head, tail) of both k-steps
-            mm(fc[0], fc[0]); mm(fc[1], fc[1]);                                          // (head, head)
+            X2_PRODUCTS(HG_X2_MM, fc)
           } else {
-            mm(fc[0], fc[0]); mm(fc[1], fc[1]); mm(fc[2], fc[2]); mm(fc[3], fc[3]);
+            mm(swp_c, fc[0], fc[0]); mm(swp_c, fc[1], fc[1]); mm(swp_c, fc[2], fc[2]); mm(swp_c, fc[3], fc[3]);
           }
         };
         // a step with a successor tile (the last tile is peeled off below: a step whose barrier is conditional makes the compiler's
@@ -645,28 +200,21 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 ? 1 : 2)) void gemm_h16_kerne
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // NS == 2: tile kt is the only one outstanding
         __syncthreads();                    // tile kt visible to every wave; every wave is done with tile kt - 1, whose buffer the next DMA takes
         if (kt + NS - 1 < nk) { HG_DMA(kt + NS - 1, (kt + NS - 1) & (NS - 1)) }
-        if constexpr (X2) {
-          Frag f[4];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) read_frag(f[g], cur, g);
-          mm(f[2], f[0]); mm(f[0], f[2]); mm(f[3], f[1]); mm(f[1], f[3]);      // (tail, head), (head, tail) of both k-steps
-          mm(f[0], f[0]); mm(f[1], f[1]);                                      // (head, head)
-        } else {
-          read_frag(f0, cur, 0);
-          read_frag(f1, cur, 1);
-          HG_FENCE
-          mm(f0, f0);
-          HG_FENCE
-          read_frag(f0, cur, 2);
-          HG_FENCE
-          mm(f1, f1);
-          HG_FENCE
-          read_frag(f1, cur, 3);
-          HG_FENCE
-          mm(f0, f0);
-          HG_FENCE
-          mm(f1, f1);
-        }
+        static_assert(NS > 2 || !X2, "split precision on two stages runs the k_loop below");
+        read_frag(f0, cur, 0);
+        read_frag(f1, cur, 1);
+        HG_FENCE
+        mm(swp_c, f0, f0);
+        HG_FENCE
+        read_frag(f0, cur, 2);
+        HG_FENCE
+        mm(swp_c, f1, f1);
+        HG_FENCE
+        read_frag(f1, cur, 3);
+        HG_FENCE
+        mm(swp_c, f0, f0);
+        HG_FENCE
+        mm(swp_c, f1, f1);
       }
     };
     if constexpr (EPI == EPI_H_QKV_NORM) {
@@ -675,52 +223,15 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 ? 1 : 2)) void gemm_h16_kerne
       ring(std::false_type{});
     }
     __syncthreads();                        // the operand buffers become the epilogue slabs
-    unsigned char* slab = smem + wave * H16_STG_BYTES;
-    const int mw = m0 + wm * TM * 32, nw = n0 + wn * 64;
-    GemmParamsH q = p;
-    if constexpr (EPI == EPI_H_BIAS_RESID_F32) {
-      if (gridDim.y > 1) q.C = reinterpret_cast<float*>(p.C) + (size_t)blockIdx.y * p.M * p.ldc;      // split-K: plane blockIdx.y of the partial buffer
-    }
-    if constexpr (X2) {
-      if constexpr (EPI == EPI_H_QKV_NORM) {
-        if (swp) gemm_x2_qknorm_epilogue<TM>(q, acc, mw, nw, lane);
-        else gemm_x2_epilogue<EPI_H_QKV, TM>(q, acc, slab, mw, nw, lane);
-      } else {
-        gemm_x2_epilogue<EPI, TM>(q, acc, slab, mw, nw, lane);
-      }
-    } else if constexpr (EPI == EPI_H_QKV_NORM) {
-      if (swp) gemm_h16_qknorm_epilogue<DT, TM>(q, acc, mw, nw, lane);
-      else gemm_h16_epilogue<EPI_H_QKV, DT, TM>(q, acc, slab, mw, nw, lane);
-    } else {
-      gemm_h16_epilogue<EPI, DT, TM>(q, acc, slab, mw, nw, lane);
-    }
-    return;
-  }
-  HG_DMA(0, 0)
-  HG_SYNC
-  if constexpr (X2) {
-    // EPI_H_QKV_NORM: the q / k column tiles run the swapped product (a lane owns a token row: the row norm is lane-local), as in the
-    // phase-split kernels; a compile-time property of the k-loop copy that runs
-    const bool swp = EPI == EPI_H_QKV_NORM && (n0 + wn * 64) < 2 * p.heads * 64;
+  } else if constexpr (X2) {
     auto k_loop = [&](auto swp_c) __attribute__((always_inline)) {
-      constexpr bool SWP = decltype(swp_c)::value;
       Frag f[4];
-      auto mma2 = [&](const Frag& fa_, const Frag& fb_) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            if constexpr (SWP) acc[i][j] = H16<DT>::mfma(__builtin_bit_cast(T8, fb_.b[j]), __builtin_bit_cast(T8, fa_.a[i]), acc[i][j]);
-            else acc[i][j] = H16<DT>::mfma(__builtin_bit_cast(T8, fa_.a[i]), __builtin_bit_cast(T8, fb_.b[j]), acc[i][j]);
-          }
-      };
       for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         if (kt + 1 < nk) { HG_DMA(kt + 1, cur ^ 1) }     // spare buffer: every wave finished reading it before the last barrier
 #pragma unroll
         for (int g = 0; g < 4; ++g) read_frag(f[g], cur, g);
-        mma2(f[2], f[0]); mma2(f[0], f[2]); mma2(f[3], f[1]); mma2(f[1], f[3]);      // (tail, head), (head, tail) of both k-steps
-        mma2(f[0], f[0]); mma2(f[1], f[1]);                                          // (head, head)
+        X2_PRODUCTS(HG_X2_MM, f)
         HG_SYNC
       }
     };
@@ -729,79 +240,83 @@ __global__ __launch_bounds__(64 * WM * WN, (NS > 2 ? 1 : 2)) void gemm_h16_kerne
     } else {
       k_loop(std::false_type{});
     }
-    static_assert(!X2 || EPI == EPI_H_BIAS_RESID_F32 || EPI == EPI_H_GEGLU || EPI == EPI_H_QKV_NORM, "split precision: the three epilogues of the model path");
-    unsigned char* slab = smem + wave * H16_STG_BYTES;
-    const int mw = m0 + wm * TM * 32, nw = n0 + wn * 64;
-    if constexpr (EPI == EPI_H_QKV_NORM) {
-      if (swp) gemm_x2_qknorm_epilogue<TM>(p, acc, mw, nw, lane);
-      else gemm_x2_epilogue<EPI_H_QKV, TM>(p, acc, slab, mw, nw, lane);
-    } else if constexpr (EPI == EPI_H_BIAS_RESID_F32) {
-      if (gridDim.y > 1) {      // split-K: this block's share of the k-tiles, scaled, into plane blockIdx.y of the partial buffer
-        GemmParamsH q = p;
-        q.C = reinterpret_cast<float*>(p.C) + (size_t)blockIdx.y * p.M * p.ldc;
-        gemm_x2_epilogue<EPI, TM>(q, acc, slab, mw, nw, lane);
-      } else {
-        gemm_x2_epilogue<EPI, TM>(p, acc, slab, mw, nw, lane);
-      }
-    } else {
-      gemm_x2_epilogue<EPI, TM>(p, acc, slab, mw, nw, lane);
+  } else {
+    read_frag(f0, 0, 0);
+
+    int kt = 0;
+    for (; kt + 1 < nk; ++kt) {
+      const int cur = kt & 1;
+      HG_DMA(kt + 1, cur ^ 1)                 // spare buffer: every wave finished reading it before the last barrier
+      read_frag(f1, cur, 1);
+      HG_FENCE
+      mma(f0);
+      HG_FENCE
+      read_frag(f0, cur, 2);
+      HG_FENCE
+      mma(f1);
+      HG_FENCE
+      read_frag(f1, cur, 3);
+      HG_FENCE
+      mma(f0);
+      HG_FENCE
+      HG_SYNC                                 // tile kt+1 landed (vmcnt(0)) and visible; reads of tile kt complete
+      read_frag(f0, cur ^ 1, 0);
+      HG_FENCE
+      mma(f1);
+      HG_FENCE
     }
-    return;
-  }
-  read_frag(f0, 0, 0);
-
-  int kt = 0;
-  for (; kt + 1 < nk; ++kt) {
-    const int cur = kt & 1;
-    HG_DMA(kt + 1, cur ^ 1)                 // spare buffer: every wave finished reading it before the last barrier
-    read_frag(f1, cur, 1);
-    HG_FENCE
-    mma(f0);
-    HG_FENCE
-    read_frag(f0, cur, 2);
-    HG_FENCE
-    mma(f1);
-    HG_FENCE
-    read_frag(f1, cur, 3);
-    HG_FENCE
-    mma(f0);
-    HG_FENCE
-    HG_SYNC                                 // tile kt+1 landed (vmcnt(0)) and visible; reads of tile kt complete
-    read_frag(f0, cur ^ 1, 0);
-    HG_FENCE
-    mma(f1);
-    HG_FENCE
-  }
-  {
-    const int cur = kt & 1;
-    read_frag(f1, cur, 1);
-    HG_FENCE
-    mma(f0);
-    HG_FENCE
-    read_frag(f0, cur, 2);
-    HG_FENCE
-    mma(f1);
-    HG_FENCE
-    read_frag(f1, cur, 3);
-    HG_FENCE
-    mma(f0);
-    HG_FENCE
-    mma(f1);
+    {
+      const int cur = kt & 1;
+      read_frag(f1, cur, 1);
+      HG_FENCE
+      mma(f0);
+      HG_FENCE
+      read_frag(f0, cur, 2);
+      HG_FENCE
+      mma(f1);
+      HG_FENCE
+      read_frag(f1, cur, 3);
+      HG_FENCE
+      mma(f0);
+      HG_FENCE
+      mma(f1);
+    }
+    __syncthreads();
   }
 
-  // ---------------- epilogue ----------------
+  // ---------------- epilogue (the block is synchronised: the operand buffers become the per-wave slabs) ----------------
   static_assert(TN == 2, "wave tiles are 64 columns wide: one head / one GEGLU value+gate group");
   static_assert(WM * WN * H16_STG_BYTES + 1024 <= NS * (BM + BN) * 128, "staging slabs (+ the LN statistics) must fit the operand buffers");
-  __syncthreads();
-  if constexpr (EPI == EPI_H_BIAS_RESID_F32) {
-    if (gridDim.y > 1) {
-      GemmParamsH q = p;
-      q.C = reinterpret_cast<float*>(p.C) + (size_t)blockIdx.y * p.M * p.ldc;
-      gemm_h16_epilogue<EPI, DT, TM>(q, acc, smem + wave * H16_STG_BYTES, m0 + wm * TM * 32, n0 + wn * 64, lane);
-      return;
-    }
+  // Split-K: plane blockIdx.y of the partial buffer takes the place of C.  The rule and the choice stand once; the shapes they are applied
+  // in are the ones the compiler has seen so far, because the code it emits follows them: the ring kernels hold ONE copy of their epilogue,
+  // on copied parameters whatever EPI is; the two-stage kernels one on p and a second for the planes; and the plain two-stage loop forms
+  // the wave tile's slab and origin inside each case, not ahead of the choice (EPI_H_BIAS_RESID_F32, 2 134 lines of assembly: 1 633 move).
+#define HG_SPLITK_PLANE (reinterpret_cast<float*>(p.C) + (size_t)blockIdx.y * p.M * p.ldc)
+#define HG_EPILOGUE(SLAB, MW, NW)                                                                             \
+  if constexpr (RING) {                                                                                       \
+    GemmParamsH q = p;                                                                                        \
+    if constexpr (EPI == EPI_H_BIAS_RESID_F32) {                                                              \
+      if (gridDim.y > 1) q.C = HG_SPLITK_PLANE;                                                               \
+    }                                                                                                         \
+    H16_EPILOGUE(q, SLAB, MW, NW)                                                                             \
+  } else {                                                                                                    \
+    if constexpr (EPI == EPI_H_BIAS_RESID_F32) {                                                              \
+      if (gridDim.y > 1) {                                                                                    \
+        GemmParamsH q = p;                                                                                    \
+        q.C = HG_SPLITK_PLANE;                                                                                \
+        H16_EPILOGUE(q, SLAB, MW, NW)                                                                         \
+        return;                                                                                               \
+      }                                                                                                       \
+    }                                                                                                         \
+    H16_EPILOGUE(p, SLAB, MW, NW)                                                                             \
   }
-  gemm_h16_epilogue<EPI, DT, TM>(p, acc, smem + wave * H16_STG_BYTES, m0 + wm * TM * 32, n0 + wn * 64, lane);
+  if constexpr (RING || X2) {
+    unsigned char* slab = smem + wave * H16_STG_BYTES;
+    const int mw = m0 + wm * TM * 32, nw = n0 + wn * 64;
+    HG_EPILOGUE(slab, mw, nw)
+  } else {
+    HG_EPILOGUE(smem + wave * H16_STG_BYTES, m0 + wm * TM * 32, n0 + wn * 64)
+  }
 }
 
 #ifdef RAP_ABLATION_BUILD
@@ -829,8 +344,31 @@ extern "C" int rap_debug_gemm_ts(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(
 // LDS image of a stage: A as [h][wave row][2 x 32 rows] x 128 B and W as [g][wave column][32 rows] x 128 B (the halves are
 // contiguous 16 KB blocks = 2 DMA pieces per thread); the permutation lives in the per-lane GLOBAL source address.
 // ---------------------------------------------------------------------------------------------
-// split-precision phase: (head, tail) fragment pairs (ka, kb) of the three kept products, the two row tiles alternating
-#define X2_MMA1(SWP, H, G, FB, KA, KB)                                                                        \
+// What the one-tile kernel and its persistent form below share, as macros over the kernels' own names (tid, smem, STAGE, ABYTES, wr, wc,
+// hi, l31, sw, acc, PRIO, X2): as a function with parameters even the piece mapping moved ~40 instructions of every instantiation.
+// piece j (0..7) of a stage: LDS chunk id = j * 512 + tid -> LDS row s = id >> 3 (0..255 A, 256..511 W), 16-byte slot id & 7.  Declares
+// `row`, the row of the A (j < 4, counted from ROW0_A) or W (j >= 4, from ROW0_W) panel that LDS row holds, and `lslot`, the logical
+// (swizzled) slot of the physical one.
+#define PH_PIECE_ROW(J, ROW0_A, ROW0_W)                                                                       \
+  const int id = (J) * 512 + tid;                                                                             \
+  const int s = (id >> 3) & 255;                                                                              \
+  const int lslot = (id & 7) ^ ((s >> 1) & 7);                                                                \
+  const int row = (J) < 4 ? ROW0_A + ((s >> 6) & 1) * 128 + (s >> 7) * 64 + (s & 63)  /* [h][wr][64 rows] -> wr*128 + h*64 + row */ \
+                          : ROW0_W + ((s >> 5) & 3) * 64 + (s >> 7) * 32 + (s & 31);  /* [g][wc][32 rows] -> wc*64 + g*32 + row */
+// operand fragments of a phase: the A rows of half h (two row tiles), the W rows of half g; four k-steps each
+#define PH_FRAGMENTS                                                                                          \
+  uint4 fa[2][4], fb0[4], fb1[4];                                                                             \
+  auto read_a = [&](int buf, int h) {                                                                         \
+    _Pragma("unroll") for (int ii = 0; ii < 2; ++ii)                                                          \
+      _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                                        \
+        fa[ii][ks] = *reinterpret_cast<const uint4*>(smem + buf * STAGE + (h * 128 + wr * 64 + ii * 32 + l31) * 128 + (((2 * ks + hi) ^ sw) * 16)); \
+  };                                                                                                          \
+  auto read_b = [&](uint4 (&fb)[4], int buf, int g) {                                                         \
+    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                                          \
+      fb[ks] = *reinterpret_cast<const uint4*>(smem + buf * STAGE + ABYTES + (g * 128 + wc * 32 + l31) * 128 + (((2 * ks + hi) ^ sw) * 16)); \
+  };
+// fragment pair (ka of A, kb of W) into quadrant (H, G), the two row tiles alternating; SWP: the swapped product C^T = W A^T
+#define PH_MMA1(SWP, H, G, FB, KA, KB)                                                                        \
   if constexpr (SWP) {                                                                                        \
     acc[2 * (H)][G] = H16<DT>::mfma(__builtin_bit_cast(T8, FB[KB]), __builtin_bit_cast(T8, fa[0][KA]), acc[2 * (H)][G]);           \
     acc[2 * (H) + 1][G] = H16<DT>::mfma(__builtin_bit_cast(T8, FB[KB]), __builtin_bit_cast(T8, fa[1][KA]), acc[2 * (H) + 1][G]);   \
@@ -838,9 +376,19 @@ extern "C" int rap_debug_gemm_ts(void* p) { return hipMemcpyToSymbol(HIP_SYMBOL(
     acc[2 * (H)][G] = H16<DT>::mfma(__builtin_bit_cast(T8, fa[0][KA]), __builtin_bit_cast(T8, FB[KB]), acc[2 * (H)][G]);           \
     acc[2 * (H) + 1][G] = H16<DT>::mfma(__builtin_bit_cast(T8, fa[1][KA]), __builtin_bit_cast(T8, FB[KB]), acc[2 * (H) + 1][G]);   \
   }
-#define X2_MMA(SWP, H, G, FB)                                                                                 \
-  X2_MMA1(SWP, H, G, FB, 2, 0) X2_MMA1(SWP, H, G, FB, 0, 2) X2_MMA1(SWP, H, G, FB, 3, 1) X2_MMA1(SWP, H, G, FB, 1, 3)               \
-  X2_MMA1(SWP, H, G, FB, 0, 0) X2_MMA1(SWP, H, G, FB, 1, 1)
+// the M part of a phase: 8 MFMAs (the four k-steps), 12 in split precision, under s_setprio where PRIO is set
+#define PH_MMA(SWP, H, G, FB)                                                                                 \
+  __builtin_amdgcn_sched_barrier(0);                                                                          \
+  if (PRIO) __builtin_amdgcn_s_setprio(1);                                                                    \
+  if constexpr (X2) {                                                                                         \
+    X2_PRODUCTS(PH_MMA1, SWP, H, G, FB)                                                                       \
+  } else {                                                                                                    \
+    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) { PH_MMA1(SWP, H, G, FB, ks, ks) }                       \
+  }                                                                                                           \
+  if (PRIO) __builtin_amdgcn_s_setprio(0);                                                                    \
+  __builtin_amdgcn_sched_barrier(0);
+#define PH_BAR __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0);
+#define PH_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory");
 // X2 (round 5): the split-precision product on paired operands (half.h RAP_DT_F32X2; DT = fp16).  A 128-byte line of a stage is 32 heads
 // followed by 32 tails of one 32-column chunk, so the fragments of "k-steps" 0, 1 are head fragments and those of 2, 3 the tail
 // fragments of the same 32 logical columns; a phase multiplies head x head, head x tail and tail x head into the one accumulator:
@@ -866,21 +414,12 @@ __global__ __launch_bounds__(512, 2) void gemm_h16_ph_kernel(GemmParamsH p) {
   const int m0 = (logical / nt) * 256;
   const int n0 = (logical % nt) * 256;
 
-  // piece j (0..7) of a stage: LDS chunk id = j * 512 + tid -> LDS row s = id >> 3 (0..255 A, 256..511 W), 16-byte slot id & 7
-  const u16* src[8];
+  const u16* src[8];      // the pieces' sources at k = 0, rows clamped to M
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int id = j * 512 + tid;
-    const int s = (id >> 3) & 255;
-    const int lslot = (id & 7) ^ ((s >> 1) & 7);
-    if (j < 4) {
-      int r = m0 + ((s >> 6) & 1) * 128 + (s >> 7) * 64 + (s & 63);       // [h][wr][64 rows] -> wr*128 + h*64 + row
-      r = r < p.M ? r : p.M - 1;
-      src[j] = p.A + (size_t)r * p.lda + 8 * lslot;
-    } else {
-      const int r = n0 + ((s >> 5) & 3) * 64 + (s >> 7) * 32 + (s & 31);   // [g][wc][32 rows] -> wc*64 + g*32 + row
-      src[j] = p.W + (size_t)r * p.ldw + 8 * lslot;
-    }
+    PH_PIECE_ROW(j, m0, n0)
+    if (j < 4) src[j] = p.A + (size_t)(row < p.M ? row : p.M - 1) * p.lda + 8 * lslot;
+    else src[j] = p.W + (size_t)row * p.ldw + 8 * lslot;
   }
 
   f32x16 acc[TM][2];
@@ -895,23 +434,8 @@ __global__ __launch_bounds__(512, 2) void gemm_h16_ph_kernel(GemmParamsH p) {
   const int sw = (l31 >> 1) & 7;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
-#define PH_PIECE(J, KT, BUF) HG_DMA1(src[J] + (size_t)(KT) * 64, lds_wave + (unsigned)((BUF) * STAGE + (J) * 8192))
-#define PH_BAR __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0);
-#define PH_VM(N) asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory");
-
-  uint4 fa[2][4], fb0[4], fb1[4];
-  auto read_a = [&](int buf, int h) {
-#pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-        fa[ii][ks] = *reinterpret_cast<const uint4*>(smem + buf * STAGE + (h * 128 + wr * 64 + ii * 32 + l31) * 128 + (((2 * ks + hi) ^ sw) * 16));
-  };
-  auto read_b = [&](uint4 (&fb)[4], int buf, int g) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      fb[ks] = *reinterpret_cast<const uint4*>(smem + buf * STAGE + ABYTES + (g * 128 + wc * 32 + l31) * 128 + (((2 * ks + hi) ^ sw) * 16));
-  };
+#define PH_PIECE(J, KT, BUF) LDS_DMA_X4(src[J] + (size_t)(KT) * 64, lds_wave + (unsigned)((BUF) * STAGE + (J) * 8192))
+  PH_FRAGMENTS
   // EPI_H_QKV_NORM: the q and k column tiles run the SWAPPED product C^T = W A^T (the MFMA's A operand is the weight fragment): a lane
   // then owns one token row and 16 of every 32 columns, so the row norm of a head is lane-local up to one lane^32 exchange and the
   // 16-bit results leave as 16-byte row pieces without an LDS transpose.  The v tiles keep the normal order (the V^T image wants a
@@ -920,24 +444,6 @@ __global__ __launch_bounds__(512, 2) void gemm_h16_ph_kernel(GemmParamsH p) {
   // SWP is a compile-time property of the k-loop COPY that runs (round 4, as in the persistent kernel below): as a run-time flag inside
   // the phases the accumulators of the two alternatives are reconciled with register copies at every phase and the kernel spilled
   // (44 bytes of scratch in the <EPI_H_QKV_NORM> instantiations).
-#define PH_MMA(SWP, H, G, FB)                                                                                 \
-  __builtin_amdgcn_sched_barrier(0);                                                                          \
-  if (PRIO) __builtin_amdgcn_s_setprio(1);                                                                    \
-  if constexpr (X2) {                                                                                         \
-    X2_MMA(SWP, H, G, FB)                                                                                     \
-  } else if constexpr (SWP) {                                                                                 \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                        \
-      acc[2 * (H)][G] = H16<DT>::mfma(__builtin_bit_cast(T8, FB[ks]), __builtin_bit_cast(T8, fa[0][ks]), acc[2 * (H)][G]);         \
-      acc[2 * (H) + 1][G] = H16<DT>::mfma(__builtin_bit_cast(T8, FB[ks]), __builtin_bit_cast(T8, fa[1][ks]), acc[2 * (H) + 1][G]); \
-    }                                                                                                         \
-  } else {                                                                                                    \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                        \
-      acc[2 * (H)][G] = H16<DT>::mfma(__builtin_bit_cast(T8, fa[0][ks]), __builtin_bit_cast(T8, FB[ks]), acc[2 * (H)][G]);         \
-      acc[2 * (H) + 1][G] = H16<DT>::mfma(__builtin_bit_cast(T8, fa[1][ks]), __builtin_bit_cast(T8, FB[ks]), acc[2 * (H) + 1][G]); \
-    }                                                                                                         \
-  }                                                                                                           \
-  if (PRIO) __builtin_amdgcn_s_setprio(0);                                                                    \
-  __builtin_amdgcn_sched_barrier(0);
 
   // prologue: tile 0 completely, plus the A half h0 of tile 1 (what phase q3 of "tile -1" would have issued)
 #pragma unroll
@@ -993,34 +499,13 @@ __global__ __launch_bounds__(512, 2) void gemm_h16_ph_kernel(GemmParamsH p) {
   static_assert(8 * H16_STG_BYTES <= 2 * STAGE, "staging slabs must fit the operand buffers");
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if constexpr (X2) {
-    if constexpr (EPI == EPI_H_QKV_NORM) {
-      if (swp) gemm_x2_qknorm_epilogue<TM>(p, acc, m0 + wr * 128, n0 + wc * 64, lane);
-      else gemm_x2_epilogue<EPI_H_QKV, TM>(p, acc, smem + wave * H16_STG_BYTES, m0 + wr * 128, n0 + wc * 64, lane);
-    } else {
-      gemm_x2_epilogue<EPI, TM>(p, acc, smem + wave * H16_STG_BYTES, m0 + wr * 128, n0 + wc * 64, lane);
-    }
-  } else if constexpr (EPI == EPI_H_QKV_NORM) {
-    if (swp) gemm_h16_qknorm_epilogue<DT, TM>(p, acc, m0 + wr * 128, n0 + wc * 64, lane);
-    else gemm_h16_epilogue<EPI_H_QKV, DT, TM>(p, acc, smem + wave * H16_STG_BYTES, m0 + wr * 128, n0 + wc * 64, lane);
-  } else {
-    gemm_h16_epilogue<EPI, DT, TM>(p, acc, smem + wave * H16_STG_BYTES, m0 + wr * 128, n0 + wc * 64, lane);
-  }
+  H16_EPILOGUE(p, smem + wave * H16_STG_BYTES, m0 + wr * 128, n0 + wc * 64)
   GEMM_TS(4)
 }
 
 template <int EPI, int DT, int PRIO, int STAG, bool X2 = false>
 static int launch_ph(hipStream_t stream, const GemmParamsH& p) {
-  constexpr int LDS = 4 * 256 * 128;
-  auto kern = gemm_h16_ph_kernel<EPI, DT, PRIO, STAG, X2>;
-  // per device and cheap: set unconditionally (a process may drive several GPUs)
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-    rap_set_last_hip_error((int)hipGetLastError());
-    return RAP_ERR_HIP;
-  }
-  hipLaunchKernelGGL(kern, dim3(((p.M + 255) / 256) * (p.N / 256)), dim3(512), LDS, stream, p);
-  RAP_LAUNCH_CHECK();
-  return RAP_OK;
+  return rap_launch_dyn_lds(gemm_h16_ph_kernel<EPI, DT, PRIO, STAG, X2>, dim3(((p.M + 255) / 256) * (p.N / 256)), dim3(512), 4 * 256 * 128, stream, p);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1051,6 +536,7 @@ template <int EPI, int DT, bool X2 = false>
 __global__ __launch_bounds__(512, 2) void gemm_h16_php_kernel(GemmParamsH p) {
   typedef typename H16<DT>::T8 T8;
   constexpr int TM = 4;
+  constexpr int PRIO = 0;      // (PH_MMA: no s_setprio in the M parts here)
   constexpr int ABYTES = 256 * 128, STAGE = 2 * ABYTES;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];   // [stage 0: A B][stage 1: A B][32 KB of epilogue slabs]
 
@@ -1065,21 +551,13 @@ __global__ __launch_bounds__(512, 2) void gemm_h16_php_kernel(GemmParamsH p) {
   const int total = (p.M / 256) * nt;
   const int nk = p.K / 64;
 
-  // piece j (0..7) of a stage: LDS chunk id = j * 512 + tid -> LDS row s = id >> 3 (0..255 A, 256..511 W), 16-byte slot id & 7;
-  // voff[j] = byte offset of the piece's source inside the tile's A (j < 4) or W (j >= 4) panel at k = 0
+  // voff[j] = byte offset of piece j's source inside the tile's A (j < 4) or W (j >= 4) panel at k = 0
   unsigned voff[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const int id = j * 512 + tid;
-    const int s = (id >> 3) & 255;
-    const int lslot = (id & 7) ^ ((s >> 1) & 7);
-    if (j < 4) {
-      const int r = ((s >> 6) & 1) * 128 + (s >> 7) * 64 + (s & 63);       // [h][wr][64 rows] -> wr*128 + h*64 + row
-      voff[j] = (unsigned)(r * p.lda + 8 * lslot) * 2u;
-    } else {
-      const int r = ((s >> 5) & 3) * 64 + (s >> 7) * 32 + (s & 31);         // [g][wc][32 rows] -> wc*64 + g*32 + row
-      voff[j] = (unsigned)(r * p.ldw + 8 * lslot) * 2u;
-    }
+    PH_PIECE_ROW(j, 0, 0)
+    if (j < 4) voff[j] = (unsigned)(row * p.lda + 8 * lslot) * 2u;
+    else voff[j] = (unsigned)(row * p.ldw + 8 * lslot) * 2u;
   }
 
   f32x16 acc[TM][2];
@@ -1087,46 +565,11 @@ __global__ __launch_bounds__(512, 2) void gemm_h16_php_kernel(GemmParamsH p) {
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
   // one LDS-DMA piece: scalar base (64-bit, SGPRs) + per-thread 32-bit offset; m0 carries the wave-uniform LDS byte address
-#define PHP_DMA1(VOFF, SBASE, LDSB)                                                                           \
-  {                                                                                                           \
-    unsigned keep_;                                                                                           \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %3\n\ts_mov_b32 m0, %0" \
-                 : "=&s"(keep_) : "v"(VOFF), "s"(LDSB), "s"(SBASE) : "memory");                                \
-  }
-#define PHP_PIECE(J, SBASE, BUF) PHP_DMA1(voff[J], SBASE, lds_wave + (unsigned)((BUF) * STAGE + (J) * 8192))
-
-  uint4 fa[2][4], fb0[4], fb1[4];
-  auto read_a = [&](int buf, int h) {
-#pragma unroll
-    for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-        fa[ii][ks] = *reinterpret_cast<const uint4*>(smem + buf * STAGE + (h * 128 + wr * 64 + ii * 32 + l31) * 128 + (((2 * ks + hi) ^ sw) * 16));
-  };
-  auto read_b = [&](uint4 (&fb)[4], int buf, int g) {
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      fb[ks] = *reinterpret_cast<const uint4*>(smem + buf * STAGE + ABYTES + (g * 128 + wc * 32 + l31) * 128 + (((2 * ks + hi) ^ sw) * 16));
-  };
+#define PHP_PIECE(J, SBASE, BUF) LDS_DMA_X4_SADDR(voff[J], SBASE, lds_wave + (unsigned)((BUF) * STAGE + (J) * 8192))
+  PH_FRAGMENTS
   // SWP (EPI_H_QKV_NORM, q and k column tiles): the swapped product C^T = W A^T, see the kernel above.  A compile-time property of the
   // k-loop COPY that runs (chosen per output tile): as a run-time flag inside the phases it cost 2x (r03 call 10: the accumulators of
   // the two alternatives are reconciled with register copies at every phase).
-#define PHP_MMA(SWP, H, G, FB)                                                                                \
-  __builtin_amdgcn_sched_barrier(0);                                                                          \
-  if constexpr (X2) {                                                                                         \
-    X2_MMA(SWP, H, G, FB)                                                                                     \
-  } else if constexpr (SWP) {                                                                                 \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                        \
-      acc[2 * (H)][G] = H16<DT>::mfma(__builtin_bit_cast(T8, FB[ks]), __builtin_bit_cast(T8, fa[0][ks]), acc[2 * (H)][G]);         \
-      acc[2 * (H) + 1][G] = H16<DT>::mfma(__builtin_bit_cast(T8, FB[ks]), __builtin_bit_cast(T8, fa[1][ks]), acc[2 * (H) + 1][G]); \
-    }                                                                                                         \
-  } else {                                                                                                    \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                        \
-      acc[2 * (H)][G] = H16<DT>::mfma(__builtin_bit_cast(T8, fa[0][ks]), __builtin_bit_cast(T8, FB[ks]), acc[2 * (H)][G]);         \
-      acc[2 * (H) + 1][G] = H16<DT>::mfma(__builtin_bit_cast(T8, fa[1][ks]), __builtin_bit_cast(T8, FB[ks]), acc[2 * (H) + 1][G]); \
-    }                                                                                                         \
-  }                                                                                                           \
-  __builtin_amdgcn_sched_barrier(0);
 
   // scalar source bases of an output tile (virtual block id v): A panel rows m0.., W panel rows n0.., at k = 0
   auto tile_bases = [&](int v, const unsigned char*& ab, const unsigned char*& wb, int& m0, int& n0) {
@@ -1191,28 +634,28 @@ __global__ __launch_bounds__(512, 2) void gemm_h16_php_kernel(GemmParamsH p) {
         __builtin_amdgcn_sched_barrier(0);
         if (ok1) { PHP_PIECE(4, w1, buf ^ 1) PHP_PIECE(5, w1, buf ^ 1) if (!nowait) { PH_VM(6) } } else { PH_VM(2) }
         PH_BAR
-        PHP_MMA(SWP, 0, 0, fb0)
+        PH_MMA(SWP, 0, 0, fb0)
         PH_BAR
         // ---- q1: quadrant (h0, g1)
         read_b(fb1, buf, 1);
         __builtin_amdgcn_sched_barrier(0);
         if (ok1) { PHP_PIECE(6, w1, buf ^ 1) PHP_PIECE(7, w1, buf ^ 1) if (!nowait) { PH_VM(6) } } else { PH_VM(0) }
         PH_BAR
-        PHP_MMA(SWP, 0, 1, fb1)
+        PH_MMA(SWP, 0, 1, fb1)
         PH_BAR
         // ---- q2: quadrant (h1, g1)
         read_a(buf, 1);
         __builtin_amdgcn_sched_barrier(0);
         if (ok1) { PHP_PIECE(2, a1, buf ^ 1) PHP_PIECE(3, a1, buf ^ 1) if (!nowait) { PH_VM(6) } }
         PH_BAR
-        PHP_MMA(SWP, 1, 1, fb1)
+        PH_MMA(SWP, 1, 1, fb1)
         PH_BAR
         // ---- q3: quadrant (h1, g0)
         read_b(fb0, buf, 0);
         __builtin_amdgcn_sched_barrier(0);
         if (ok2) { PHP_PIECE(0, a2, buf) PHP_PIECE(1, a2, buf) PH_VM(6) } else if (ok1) { PH_VM(4) }
         PH_BAR
-        PHP_MMA(SWP, 1, 0, fb0)
+        PH_MMA(SWP, 1, 0, fb0)
         PH_BAR
         par ^= 1;
       }
@@ -1232,19 +675,7 @@ __global__ __launch_bounds__(512, 2) void gemm_h16_php_kernel(GemmParamsH p) {
       const int last = par ^ 1;                  // the stage the last k-tile was read from: its bytes [16 KB, 64 KB) are idle
       unsigned char* slab = wave < 5 ? smem + last * STAGE + 16384 + wave * H16_STG_BYTES : smem + 2 * STAGE + (wave - 5) * H16_STG_BYTES;
       static_assert(5 * H16_STG_BYTES <= STAGE - 16384 && 3 * H16_STG_BYTES <= 32768, "epilogue slabs must fit the idle regions");
-      if constexpr (X2) {
-        if constexpr (EPI == EPI_H_QKV_NORM) {
-          if (swp) gemm_x2_qknorm_epilogue<TM>(p, acc, m0 + wr * 128, n0 + wc * 64, lane);
-          else gemm_x2_epilogue<EPI_H_QKV, TM>(p, acc, slab, m0 + wr * 128, n0 + wc * 64, lane);
-        } else {
-          gemm_x2_epilogue<EPI, TM>(p, acc, slab, m0 + wr * 128, n0 + wc * 64, lane);
-        }
-      } else if constexpr (EPI == EPI_H_QKV_NORM) {
-        if (swp) gemm_h16_qknorm_epilogue<DT, TM>(p, acc, m0 + wr * 128, n0 + wc * 64, lane);
-        else gemm_h16_epilogue<EPI_H_QKV, DT, TM>(p, acc, slab, m0 + wr * 128, n0 + wc * 64, lane);
-      } else {
-        gemm_h16_epilogue<EPI, DT, TM>(p, acc, slab, m0 + wr * 128, n0 + wc * 64, lane);
-      }
+      H16_EPILOGUE(p, slab, m0 + wr * 128, n0 + wc * 64)
     }
     PHP_TS(2)
 #ifdef RAP_ABLATION_BUILD
@@ -1261,25 +692,9 @@ __global__ __launch_bounds__(512, 2) void gemm_h16_php_kernel(GemmParamsH p) {
 
 template <int EPI, int DT, bool X2 = false>
 static int launch_php(hipStream_t stream, const GemmParamsH& p) {
-  constexpr int LDS = 4 * 256 * 128 + 32768;
-  auto kern = gemm_h16_php_kernel<EPI, DT, X2>;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-    rap_set_last_hip_error((int)hipGetLastError());
-    return RAP_ERR_HIP;
-  }
-  static std::atomic<int> n_cu_cache[16] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return RAP_ERR_HIP;
-  int n_cu = (dev >= 0 && dev < 16) ? n_cu_cache[dev].load() : 0;
-  if (n_cu == 0) {
-    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu <= 0) return RAP_ERR_HIP;
-    n_cu = n_cu >= 8 ? (n_cu / 8) * 8 : n_cu;     // a multiple of the XCD count: a block's virtual ids stay on its XCD
-    if (dev >= 0 && dev < 16) n_cu_cache[dev] = n_cu;
-  }
-  const int total = (p.M / 256) * (p.N / 256);
-  hipLaunchKernelGGL(kern, dim3(total < n_cu ? total : n_cu), dim3(512), LDS, stream, p);
-  RAP_LAUNCH_CHECK();
-  return RAP_OK;
+  const int blocks = rap_persistent_blocks((p.M / 256) * (p.N / 256));
+  if (blocks <= 0) return RAP_ERR_HIP;
+  return rap_launch_dyn_lds(gemm_h16_php_kernel<EPI, DT, X2>, dim3(blocks), dim3(512), 4 * 256 * 128 + 32768, stream, p);
 }
 
 // Kernel choice (round 3: the fifteen other main loops of rounds 1-2 -- rings, pipelined rings, interleaved issue, persistent,
@@ -1294,17 +709,9 @@ rap_tuning_t g_rap_gemm_h16_persistent = 1;     // tuning key 11: the persistent
 template <int EPI, int DT, int WM, int WN, int TM, int TN, bool X2 = false, int NS = 2>
 static int launch_cfg(hipStream_t stream, const GemmParamsH& p, int splits = 1) {
   constexpr int BM = 32 * TM * WM, BN = 32 * TN * WN;
-  constexpr int LDS = NS * (BM + BN) * 128;
-  auto kern = gemm_h16_kernel<EPI, DT, WM, WN, TM, TN, X2, NS>;
-  // per device and cheap: set unconditionally (a process may drive several GPUs)
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-    rap_set_last_hip_error((int)hipGetLastError());
-    return RAP_ERR_HIP;
-  }
   const int mt = (EPI == EPI_H_QKV_NORM || EPI == EPI_H_QKV) ? ((p.M + 255) / 256) * (256 / BM) : (p.M + BM - 1) / BM;
-  hipLaunchKernelGGL(kern, dim3(mt * (p.N / BN), splits), dim3(64 * WM * WN), LDS, stream, p);
-  RAP_LAUNCH_CHECK();
-  return RAP_OK;
+  return rap_launch_dyn_lds(gemm_h16_kernel<EPI, DT, WM, WN, TM, TN, X2, NS>, dim3(mt * (p.N / BN), splits), dim3(64 * WM * WN), NS * (BM + BN) * 128,
+                            stream, p);
 }
 
 // The 128 x 128 kernel for few-token calls (round 6): a launch with at most g_rap_ring_blocks blocks (tuning key 18; 0 = never) takes the
@@ -1374,11 +781,11 @@ int gemm_h16_splits_by_shape(int M, int N, int K) {
 }
 int gemm_h16_splits(int M, int N, int K) { return g_rap_gemm_splitk ? gemm_h16_splits_by_shape(M, N, K) : 1; }
 
-template <int DT>
+template <int DT, bool X2 = false>
 static int launch_splitk(hipStream_t stream, int epilogue, const GemmParamsH& p, int stages, int splits) {
-  GemmParamsH q = p;
+  GemmParamsH q = p;      // (acc_scale stays: the split-precision partials are in true units)
   q.C = p.splitk_ws; q.ldc = p.N; q.bias = nullptr; q.resid = nullptr; q.resid_h = nullptr; q.splitk_ws = nullptr;
-  if (int rc = launch_small<EPI_H_BIAS_RESID_F32, DT>(stream, q, stages, splits)) return rc;
+  if (int rc = launch_small<EPI_H_BIAS_RESID_F32, DT, X2>(stream, q, stages, splits)) return rc;
   if (p.defer_combine) return RAP_OK;      // the caller's combine + LayerNorm pass consumes the planes (launch_resid_combine_ln_h16)
   const long n8 = (long)p.M * (p.N / 8);
   const dim3 grid((unsigned)((n8 + 255) / 256));
@@ -1463,10 +870,10 @@ int gemm_h16_form(int dtype, int epilogue, const GemmParamsH& p, bool* planes_to
 
 template <int EPI, int DT, bool X2 = false>
 static int launch_form(hipStream_t stream, const GemmParamsH& p, int form) {
-  switch (form / 100) {
+  switch (rap_form_kernel(form)) {
     case RAP_FORM_256P: return launch_php<EPI, DT, X2>(stream, p);
     case RAP_FORM_256: return launch_ph<EPI, DT, 0, 1, X2>(stream, p);
-    case RAP_FORM_128: return launch_small<EPI, DT, X2>(stream, p, (form / 10) % 10);
+    case RAP_FORM_128: return launch_small<EPI, DT, X2>(stream, p, rap_form_stages(form));
 #ifdef RAP_ABLATION_BUILD
     case RAP_FORM_256_2S:
       if constexpr (!X2 && EPI != EPI_H_QKV_NORM) return launch_cfg<EPI, DT, 2, 4, 4, 2>(stream, p);
@@ -1476,11 +883,17 @@ static int launch_form(hipStream_t stream, const GemmParamsH& p, int form) {
   }
 }
 
+// The fused QKV projections: N is three model widths and the V^T image is given and covers align_up(M, 256) token rows.  The q / k gains
+// are the caller's rule: 16-bit EPI_H_QKV_NORM needs both, split precision both or neither (none = no qk-norm), EPI_H_QKV reads none.
+static bool qkv_args_ok(const GemmParamsH& p, bool gammas_ok) {
+  return p.N == 3 * p.heads * 64 && p.vt && p.vt_nblk * 64 >= (p.M + 255) / 256 * 256 && gammas_ok;
+}
+
 template <int DT>
 static int launch_dt(hipStream_t stream, int epilogue, const GemmParamsH& p, int form, bool planes_to_ws) {
   if (planes_to_ws) {
     if ((p.ldc & 7) || (p.ldr & 7) || (epilogue == EPI_H_BIAS_RESID_H16 && !p.resid_h)) return RAP_ERR_INVALID;
-    return launch_splitk<DT>(stream, epilogue, p, (form / 10) % 10, form % 10);
+    return launch_splitk<DT>(stream, epilogue, p, rap_form_stages(form), rap_form_splits(form));
   }
   switch (epilogue) {
     case EPI_H_BIAS: return launch_form<EPI_H_BIAS, DT>(stream, p, form);
@@ -1490,39 +903,26 @@ static int launch_dt(hipStream_t stream, int epilogue, const GemmParamsH& p, int
       return launch_form<EPI_H_BIAS_RESID_H16, DT>(stream, p, form);
     case EPI_H_GEGLU: return launch_form<EPI_H_GEGLU, DT>(stream, p, form);
     case EPI_H_QKV_NORM:
-      if (p.N != 3 * p.heads * 64 || !p.vt || p.vt_nblk * 64 < (p.M + 255) / 256 * 256 || !p.gamma_q || !p.gamma_k) return RAP_ERR_INVALID;
+      if (!qkv_args_ok(p, p.gamma_q && p.gamma_k)) return RAP_ERR_INVALID;
       return launch_form<EPI_H_QKV_NORM, DT>(stream, p, form);
     case EPI_H_QKV:
-      if (p.N != 3 * p.heads * 64 || !p.vt || p.vt_nblk * 64 < (p.M + 255) / 256 * 256) return RAP_ERR_INVALID;
+      if (!qkv_args_ok(p, true)) return RAP_ERR_INVALID;
       return launch_form<EPI_H_QKV, DT>(stream, p, form);
     default: return RAP_ERR_INVALID;
   }
 }
 
-static int launch_x2_splitk(hipStream_t stream, const GemmParamsH& p, int stages, int splits) {
-  GemmParamsH q = p;
-  q.C = p.splitk_ws; q.ldc = p.N; q.bias = nullptr; q.resid = nullptr; q.splitk_ws = nullptr;      // (acc_scale stays: the partials are in true units)
-  if (int rc = launch_small<EPI_H_BIAS_RESID_F32, RAP_DT_F16, true>(stream, q, stages, splits)) return rc;
-  if (p.defer_combine) return RAP_OK;
-  const long n8 = (long)p.M * (p.N / 8);
-  hipLaunchKernelGGL(gemm_h16_splitk_combine_kernel<false>, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, stream, p.splitk_ws, splits, p.M, p.N,
-                     p.bias, (const void*)p.resid, p.ldr, p.C, p.ldc);
-  RAP_LAUNCH_CHECK();
-  return RAP_OK;
-}
 static int launch_x2(hipStream_t stream, int epilogue, const GemmParamsH& p, int form, bool planes_to_ws) {
   switch (epilogue) {
     case EPI_H_BIAS_RESID_F32:
       if (planes_to_ws) {
         if ((p.ldc & 7) || (p.ldr & 7)) return RAP_ERR_INVALID;
-        return launch_x2_splitk(stream, p, (form / 10) % 10, form % 10);
+        return launch_splitk<RAP_DT_F16, true>(stream, epilogue, p, rap_form_stages(form), rap_form_splits(form));
       }
       return launch_form<EPI_H_BIAS_RESID_F32, RAP_DT_F16, true>(stream, p, form);
-    case EPI_H_GEGLU:
-      if (p.ldc & 7) return RAP_ERR_INVALID;
-      return launch_form<EPI_H_GEGLU, RAP_DT_F16, true>(stream, p, form);
+    case EPI_H_GEGLU: return launch_form<EPI_H_GEGLU, RAP_DT_F16, true>(stream, p, form);      // (ldc: checked by launch_gemm_h16)
     case EPI_H_QKV_NORM:
-      if (p.N != 3 * p.heads * 64 || !p.vt || p.vt_nblk * 64 < (p.M + 255) / 256 * 256 || ((p.gamma_q == nullptr) != (p.gamma_k == nullptr))) return RAP_ERR_INVALID;
+      if (!qkv_args_ok(p, (p.gamma_q == nullptr) == (p.gamma_k == nullptr))) return RAP_ERR_INVALID;
       return launch_form<EPI_H_QKV_NORM, RAP_DT_F16, true>(stream, p, form);
     default: return RAP_ERR_INVALID;
   }

@@ -49,6 +49,13 @@ enum GemmFormKernel {
   RAP_FORM_256_2S = 4, // RAP_ABLATION_BUILD only: the two-stage 256 x 256 kernel of the 16-bit path
 };
 static inline int rap_gemm_form(int kernel, int stages, int splits) { return 100 * kernel + 10 * stages + splits; }
+static inline int rap_form_kernel(int form) { return form / 100; }
+static inline int rap_form_stages(int form) { return (form / 10) % 10; }
+static inline int rap_form_splits(int form) { return form % 10; }
+// Grid of a persistent 256 x 256 GEMM kernel (gemm_f32.hip): one block per CU of the current device, the CU count rounded down to a multiple
+// of the XCD count (8: a block's virtual ids v = blockIdx.x + i * gridDim.x stay on its XCD) and cached per device, at most `tiles`.
+// <= 0: the device query failed.
+int rap_persistent_blocks(int tiles);
 int gemm_f32_form(int epilogue, const GemmParams& p);       // reads M, N, K, lda, ldw, ldc, ldr, splitk_ws (given or not), splitk_planes
 // the K splits of the fp32 few-row rule from the shape alone (tuning key 6 and the strides gate the launch, not a reservation): 4 for bias +
 // residual, `planes` (2 or 4) for bias + SiLU, 1 = no split

@@ -19,6 +19,7 @@
 //  3. spin_pool_kernel (one wave per keypoint): the 1x1 attention pool 32->16->1 with folded BatchNorm + ReLU, weighted mean over
 //     the 7x20 map, L2 normalisation (patch_embedder.py:81-83).
 #include "kernels.h"
+#include "lds_dma.h"
 #include "kabsch.h"
 
 #define SP_PATCH 512
@@ -285,12 +286,6 @@ __global__ __launch_bounds__(256, 2) void spin_conv3x3_kernel(SpinConvParams p) 
   const int b_row = 2 * AF + (wn * 32 * TN + l31) * 32;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float*)smem_c;
   const unsigned lds_wave = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)wave * 1024u);
-#define SC_DMA1(GSRC, LDSB)                                                                                   \
-  {                                                                                                           \
-    unsigned keep_;                                                                                           \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
-                 : "=&s"(keep_) : "v"(GSRC), "s"(LDSB) : "memory");                                           \
-  }
   auto dma = [&](int kt, int buf) {
     const int tap = kt / tiles_per_tap, c0 = (kt - tap * tiles_per_tap) * 32;
     const int dy = tap / 3 - 1, dx = tap % 3 - 1;
@@ -309,12 +304,12 @@ __global__ __launch_bounds__(256, 2) void spin_conv3x3_kernel(SpinConvParams p) 
         int ww = a_w[i] + dx; ww = ww < 0 ? ww + SP_AZI : (ww >= SP_AZI ? ww - SP_AZI : ww);
         src = (hh >= 0 && hh < SP_ELE) ? p.y + (size_t)(a_pix[i] + hh * SP_AZI + ww) * p.ldy + c0 + a_ls[i] : p.zeros + a_ls[i];
       }
-      SC_DMA1(src, lds_wave + (unsigned)((buf * AF + i * 1024) * 4))
+      LDS_DMA_X4(src, lds_wave + (unsigned)((buf * AF + i * 1024) * 4))
     }
 #pragma unroll
     for (int i = 0; i < CB; ++i)
       if (CB * 256 <= BN * 8 || i * 256 + tid < BN * 8)            // BN = 32: only the first 256 chunks exist
-        SC_DMA1(w_src[i] + (size_t)kt * 32, lds_wave + (unsigned)((2 * AF + buf * BF + i * 1024) * 4))
+        LDS_DMA_X4(w_src[i] + (size_t)kt * 32, lds_wave + (unsigned)((2 * AF + buf * BF + i * 1024) * 4))
   };
 #define SC_SYNC asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads();
 #define SC_RD(OFF) (*reinterpret_cast<const float4*>(&smem_c[OFF]))
