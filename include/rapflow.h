@@ -35,7 +35,9 @@ extern "C" {
  * rap_nearest_neighbors (the same search over a uniform-grid index); rap_attention_split_workspace_bytes, rap_attention_f32_split and
  * rap_x2_attention_split (kernel-level access to the split-KV attention of few-token calls); rap_gemm_f32_form and rap_gemm_h16_form (the
  * GEMM dispatch decision as host arithmetic), rap_call_plan (every shape-dependent decision of a model call, likewise), rap_gemm_f32_splitk_workspace_bytes and rap_gemm_f32_splitk (kernel-level access to the
- * split-K form of the fp32 residual and SiLU GEMMs of few-token calls). */
+ * split-K form of the fp32 residual and SiLU GEMMs of few-token calls); rap_normals_workspace_bytes, rap_estimate_normals,
+ * rap_icp_plane_workspace_bytes, rap_icp_plane, rap_icp_plane_grid_workspace_bytes and rap_icp_plane_grid (point-to-plane ICP and the
+ * normals it needs). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -317,6 +319,50 @@ size_t rap_nn_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32
 int rap_nearest_neighbors(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t n_x_points,
                           int64_t n_y_points, const float* R, const float* T, float max_distance, int32_t* idx_out, float* d2_out, void* ws,
                           size_t ws_bytes, void* stream);
+
+/* Surface normals of packed clouds: the plane fit of every point's neighbourhood, Open3D's estimate_normals with a hybrid search as the
+ * reference calls it (dataset_process/utils/dataset_utils.py:325-358: radius 0.5, max_nn 20).  P (n_points,3) fp32; seg (K,2) int32
+ * (start, len) rows, clamped to the array on the device, which must not overlap (the work list holds n_points / 256 + K + 1 items; a
+ * segment that no longer fits is left out); a segment that repeats an earlier one exactly is worked once, with the earlier one's
+ * viewpoint.  For row i of segment k the neighbourhood is the rows j of the SAME segment with
+ * sqrtf(d2(p_i, p_j)) <= radius (fp32 direct differences, the distance of rap_icp; radius <= 0: no limit, pure k-NN), of those the
+ * max_nn (3 .. 32) with the smallest (d2, j), the row itself included; rows with a non-finite coordinate are never neighbours.  Mean
+ * and centred covariance (divided by the count) in fp64 from the fp32 coordinates; the normal is the unit eigenvector of the smallest
+ * eigenvalue (fp64 Jacobi), rounded to fp32.  Orientation: with viewpoint (K,3), n . (viewpoint[k] - p_i) >= 0; with NULL, the
+ * component of largest magnitude is positive (the lowest index among equals).  Fewer than three neighbours, or a non-finite p_i:
+ * normal (0,0,0) and eigenvalues 0 -- a stated departure from Open3D's (0,0,1): rap_icp_plane skips a zero normal, it cannot skip a
+ * made-up one.  normals (n_points,3); eigenvalues (n_points,3) ascending, or NULL; rows outside every segment are not written.
+ * Brute-force search, O(len^2) per segment: meant for voxel-downsampled clouds.  Two launches, no host read, no atomics,
+ * deterministic, a row's bits depend on its own segment only; can be captured into a graph.
+ * ws >= rap_normals_workspace_bytes(n_points, K) (host arithmetic; 0 for non-positive arguments). */
+size_t rap_normals_workspace_bytes(int64_t n_points, int32_t K);
+int rap_estimate_normals(const float* P, const int32_t* seg, int32_t K, int64_t n_points, int32_t max_nn, float radius,
+                         const float* viewpoint, float* normals, float* eigenvalues, void* ws, size_t ws_bytes, void* stream);
+
+/* Batched point-to-plane ICP: rap_icp's argument list plus Y_normals (n_y_points,3) fp32, and rap_icp's rules for segments, the gate,
+ * empty problems (xn == 0 or yn == 0), Xt and the execution properties.  Per problem, from R, T = init or identity:
+ *   for it in 0 .. max_iterations-1:
+ *     p_i = x_i R + T (fp32);  nn(i) = first arg-min as in rap_icp;  S = the gated i whose normal n = Y_normals[nn(i)] is finite and not 0;
+ *     in double: r_i = (p_i - y_nn(i)) . n,  J_i = [p_i x n, n],  A = sum_S J J^T,  b = sum_S J r,  e = sum_S r^2;
+ *     S empty: rmse = inf, converged = 0, stop with the R, T it had;
+ *     rmse = sqrt(e / |S|): the residual of the transform that ENTERED this iteration;
+ *     (omega, tau) = -A^+ b, A^+ without the eigenvalues <= 1e-12 lambda_max (the minimum-norm step: no motion along what a planar
+ *     target does not observe);  dR = exp([omega]x);  R <- R dR^T,  T <- T dR^T + tau  (kept in fp64 between iterations; the outputs are
+ *     its fp32 rounding);  iterations = it + 1;  rel = 1 in the first iteration, else (prev - rmse) / prev;
+ *     prev == 0 or rel <= relative_rmse_thr: converged = 1, stop.
+ * The update of the last iteration is applied before the stop, so the reported rmse is one update BEHIND the returned R, T.
+ * rap_icp_plane_grid: the same on the uniform-grid index of rap_icp_grid, bit for bit (K <= 65535).
+ * ws >= rap_icp_plane_workspace_bytes(n_x_points, K) / rap_icp_plane_grid_workspace_bytes(n_x_points, n_y_points, K). */
+size_t rap_icp_plane_workspace_bytes(int64_t n_x_points, int32_t K);
+int rap_icp_plane(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals, int32_t K,
+                  int64_t n_x_points, int64_t n_y_points, const float* init_R, const float* init_T, int32_t max_iterations,
+                  float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations,
+                  uint8_t* converged, float* Xt, void* ws, size_t ws_bytes, void* stream);
+size_t rap_icp_plane_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K);
+int rap_icp_plane_grid(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals, int32_t K,
+                       int64_t n_x_points, int64_t n_y_points, const float* init_R, const float* init_T, int32_t max_iterations,
+                       float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations,
+                       uint8_t* converged, float* Xt, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- MiniSpinNet local feature extractor (the step before the path) ----
  * Replaces MiniSpinNet.forward (reference dataset_process/utils/spinnet/patch_embedder.py:49-183 with patchnet.py:16-84 and

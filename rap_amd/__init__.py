@@ -7,6 +7,7 @@ One hot path of PRBonn/RAP, rebuilt as hand-written HIP kernels behind the refer
 from .data import transform_and_collate
 from .evaluator import Evaluator
 from .flow_model import PointCloudDiT
+from .normals import estimate_normals_packed, estimate_point_normals
 from .icp import ICPSolution, align_anchor, compute_transform_errors_icp, icp_packed, iterative_closest_point, nearest_neighbors_packed
 from .modeling import RectifiedPointFlow
 from .procrustes import fit_transformations, rigidify_prediction_with_procrustes, solve_procrustes
@@ -18,4 +19,5 @@ __all__ = ["PointCloudDiT", "RectifiedPointFlow", "fit_transformations", "rigidi
            "solve_procrustes", "euler_step", "flow_sampler", "get_sampler", "compute_rigidity_rmse",
            "average_trajectory_rigidity_rmse", "select_generations_by_rigidity", "compute_overlap_ratio",
            "select_generations_by_overlap", "transform_and_collate", "Evaluator", "iterative_closest_point", "icp_packed", "ICPSolution",
-           "align_anchor", "compute_transform_errors_icp", "nearest_neighbors_packed"]
+           "align_anchor", "compute_transform_errors_icp", "nearest_neighbors_packed",
+           "estimate_normals_packed", "estimate_point_normals"]

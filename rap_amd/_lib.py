@@ -80,6 +80,14 @@ SIGNATURES = {
                                c_size_t, _P]),
     "rap_nn_grid_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
     "rap_nearest_neighbors": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, c_float, _P, _P, _P, c_size_t, _P]),
+    "rap_normals_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "rap_estimate_normals": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_float, _P, _P, _P, _P, c_size_t, _P]),
+    "rap_icp_plane_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "rap_icp_plane": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, c_int32, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
+                                c_size_t, _P]),
+    "rap_icp_plane_grid_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "rap_icp_plane_grid": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, c_int32, c_float, c_float, _P, _P, _P, _P, _P, _P,
+                                     _P, c_size_t, _P]),
     "rap_voxel_bounds": (c_int32, [_P, c_int64, c_float, _P, _P, _P]),
     "rap_voxel_table_slots": (c_int64, [_P]),
     "rap_voxel_workspace_bytes": (c_size_t, [_P]),

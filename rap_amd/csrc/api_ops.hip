@@ -787,6 +787,76 @@ extern "C" int rap_nearest_neighbors(const float* X, const int32_t* x_seg, const
                                   idx_out, d2_out, items, g);
 }
 
+// batched point-to-plane ICP (icp_plane.hip; nn_grid.hip) and the normals it needs (normals.hip)
+struct IcpPlaneWs { NnWork* items; void* partials; void* ranges; double* prev; int32_t* done; double* state; size_t total; };
+static IcpPlaneWs carve_icp_plane(int64_t n, int K, char* basep) {
+  IcpPlaneWs w; Carver c(basep);
+  const size_t max_items = nn_max_items((long)n, K);
+  w.items = (NnWork*)c.take(max_items * sizeof(NnWork));
+  w.partials = c.take(max_items * icp_plane_partial_bytes());
+  w.ranges = c.take((size_t)K * 16);
+  w.prev = (double*)c.take((size_t)K * 8);
+  w.done = (int32_t*)c.take((size_t)K * 4);
+  w.state = (double*)c.take((size_t)K * 12 * 8);
+  w.total = c.total();
+  return w;
+}
+extern "C" size_t rap_icp_plane_workspace_bytes(int64_t n_x_points, int32_t K) {
+  return (n_x_points <= 0 || K <= 0) ? 0 : carve_icp_plane(n_x_points, K, nullptr).total;
+}
+extern "C" int rap_icp_plane(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals, int32_t K,
+                             int64_t NX, int64_t NY, const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
+                             float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged,
+                             float* Xt, void* ws, size_t ws_bytes, void* stream) {
+  if (!X || !x_seg || !Y || !y_seg || !Y_normals || !R || !T || !rmse || !iterations || !converged || K <= 0 || max_iterations <= 0 ||
+      NX <= 0 || NY <= 0 || NX > 0x7fffffffLL / 8 || NY > 0x7fffffffLL / 8 || relative_rmse_thr != relative_rmse_thr ||
+      max_correspondence_distance != max_correspondence_distance)
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  IcpPlaneWs w = carve_icp_plane(NX, K, (char*)ws);
+  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_icp_plane((hipStream_t)stream, X, x_seg, Y, y_seg, Y_normals, K, (long)NX, (long)NY, init_R, init_T, max_iterations,
+                          relative_rmse_thr, max_correspondence_distance > 0.f ? max_correspondence_distance : 0.f, R, T, rmse, iterations,
+                          converged, Xt, w.items, w.partials, w.ranges, w.prev, w.done, w.state);
+}
+extern "C" size_t rap_icp_plane_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
+  if (n_x_points <= 0 || n_y_points <= 0 || K <= 0) return 0;
+  Carver c(nullptr);
+  nn_grid_carve(c, (long)n_y_points, K);
+  return carve_icp_plane(n_x_points, K, nullptr).total + c.total();
+}
+extern "C" int rap_icp_plane_grid(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals,
+                                  int32_t K, int64_t NX, int64_t NY, const float* init_R, const float* init_T, int32_t max_iterations,
+                                  float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse,
+                                  int32_t* iterations, uint8_t* converged, float* Xt, void* ws, size_t ws_bytes, void* stream) {
+  if (!X || !x_seg || !Y || !y_seg || !Y_normals || !R || !T || !rmse || !iterations || !converged || K <= 0 || K > RAP_GRID_MAX_K ||
+      max_iterations <= 0 || NX <= 0 || NY <= 0 || NX > 0x7fffffffLL / 8 || NY > 0x7fffffffLL / 8 ||
+      relative_rmse_thr != relative_rmse_thr || max_correspondence_distance != max_correspondence_distance)
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  IcpPlaneWs w = carve_icp_plane(NX, K, (char*)ws);
+  Carver c((char*)ws + w.total);
+  const NnGridWs g = nn_grid_carve(c, (long)NY, K);
+  if (w.total + c.total() > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_icp_plane_grid((hipStream_t)stream, X, x_seg, Y, y_seg, Y_normals, K, (long)NX, (long)NY, init_R, init_T, max_iterations,
+                               relative_rmse_thr, max_correspondence_distance > 0.f ? max_correspondence_distance : 0.f, R, T, rmse,
+                               iterations, converged, Xt, w.items, w.partials, w.ranges, w.prev, w.done, w.state, g);
+}
+extern "C" size_t rap_normals_workspace_bytes(int64_t n_points, int32_t K) {
+  return (n_points <= 0 || K <= 0) ? 0 : align_up(nn_max_items((long)n_points, K) * sizeof(NnWork), 256) + align_up((size_t)K * 4, 256);
+}
+extern "C" int rap_estimate_normals(const float* P, const int32_t* seg, int32_t K, int64_t n_points, int32_t max_nn, float radius,
+                                    const float* viewpoint, float* normals, float* eigenvalues, void* ws, size_t ws_bytes, void* stream) {
+  if (!P || !seg || !normals || K <= 0 || n_points <= 0 || n_points > 0x7fffffffLL / 8 || max_nn < 3 || max_nn > 32 || radius != radius)
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  if (rap_normals_workspace_bytes(n_points, K) > ws_bytes) return RAP_ERR_WORKSPACE;
+  Carver c(ws);
+  NnWork* items = (NnWork*)c.take(nn_max_items((long)n_points, K) * sizeof(NnWork));
+  int32_t* repeat = (int32_t*)c.take((size_t)K * 4);
+  return launch_estimate_normals((hipStream_t)stream, P, seg, K, (long)n_points, max_nn, radius, viewpoint, normals, eigenvalues, items, repeat);
+}
+
 extern "C" int rap_farthest_point_sampling(const float* points, const int32_t* cloud_start, const int32_t* cloud_len,
                                            const int32_t* k_per_cloud, const int32_t* start_idx, int32_t n_clouds, int32_t k_max,
                                            int32_t* indices_out, float* dist_ws, void* stream) {

@@ -72,3 +72,63 @@ __device__ __forceinline__ void icp_moments(bool active, int besti, float best, 
   if (threadIdx.x < ICP_NMOM) out->m[threadIdx.x] = (red_m[0][threadIdx.x] + red_m[1][threadIdx.x]) + (red_m[2][threadIdx.x] + red_m[3][threadIdx.x]);
   if (threadIdx.x == ICP_NMOM) out->count = (long long)(red_n[0] + red_n[1] + red_n[2] + red_n[3]);
 }
+
+// ---- point-to-plane (icp_plane.hip; the grid path in nn_grid.hip) ----
+#define ICP_PLANE_NMOM 28      // upper triangle of A = sum J J^T, row by row (21), b = sum J r (6), e = sum r^2
+struct IcpPlanePartial { double m[ICP_PLANE_NMOM]; long long count; };
+
+// the neighbour's normal counts when every component is finite and it is not the zero vector ("no estimate", normals.hip)
+__device__ __forceinline__ bool icp_normal_ok(float nx, float ny, float nz) {
+  const float inf = __builtin_inff();
+  return fabsf(nx) < inf && fabsf(ny) < inf && fabsf(nz) < inf && (nx != 0.f || ny != 0.f || nz != 0.f);
+}
+
+// wave sum of one moment into the wave's row of red_m; the sums of a block are taken one at a time, so that no more than the seven
+// doubles of J and r stay live across them, not 28 accumulators (the query kernels stay at 50 / 68 VGPRs)
+__device__ __forceinline__ void icp_plane_put(double v, double* __restrict__ row, int i) {
+  v = wave_sum_d(v);
+  if ((threadIdx.x & 63) == 0) row[i] = v;
+}
+
+// Epilogue of a block of ICP_TILE queries for the point-to-plane step, built as icp_moments is: (px, py, pz) is the MOVED query (what
+// the search saw, fp32), y = Y[y_start + besti] its neighbour, n = Yn[y_start + besti] the neighbour's normal.  In double:
+// r = (p - y) . n, J = [p x n, n]; the gated pairs with a usable normal are summed per wave, then over the four waves in a fixed order.
+// Every thread of the block calls it.  Both search paths end here, so they return the same bits.
+__device__ __forceinline__ void icp_plane_moments(bool active, int besti, float best, float gate, float px, float py, float pz,
+                                                  const float* __restrict__ Y, const float* __restrict__ Yn, int y_start,
+                                                  double (*red_m)[ICP_PLANE_NMOM], int* red_n, IcpPlanePartial* __restrict__ out) {
+  double J[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, r = 0.0;
+  int n = 0;
+  if (active && besti >= 0 && (!(gate > 0.f) || sqrtf(best) <= gate)) {
+    const size_t ti = (size_t)y_start + besti;
+    const float n0 = Yn[ti * 3 + 0], n1 = Yn[ti * 3 + 1], n2 = Yn[ti * 3 + 2];
+    if (icp_normal_ok(n0, n1, n2)) {
+      const double p[3] = {(double)px, (double)py, (double)pz};
+      const double nv[3] = {(double)n0, (double)n1, (double)n2};
+      const double d[3] = {p[0] - (double)Y[ti * 3 + 0], p[1] - (double)Y[ti * 3 + 1], p[2] - (double)Y[ti * 3 + 2]};
+      r = d[0] * nv[0] + d[1] * nv[1] + d[2] * nv[2];
+      J[0] = p[1] * nv[2] - p[2] * nv[1];
+      J[1] = p[2] * nv[0] - p[0] * nv[2];
+      J[2] = p[0] * nv[1] - p[1] * nv[0];
+      J[3] = nv[0]; J[4] = nv[1]; J[5] = nv[2];
+      n = 1;
+    }
+  }
+  double* row = red_m[threadIdx.x >> 6];
+  int at = 0;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+#pragma unroll
+    for (int j = i; j < 6; ++j) icp_plane_put(J[i] * J[j], row, at++);
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) icp_plane_put(J[i] * r, row, 21 + i);
+  icp_plane_put(r * r, row, 27);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if ((threadIdx.x & 63) == 0) red_n[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x < ICP_PLANE_NMOM)
+    out->m[threadIdx.x] = (red_m[0][threadIdx.x] + red_m[1][threadIdx.x]) + (red_m[2][threadIdx.x] + red_m[3][threadIdx.x]);
+  if (threadIdx.x == ICP_PLANE_NMOM) out->count = (long long)(red_n[0] + red_n[1] + red_n[2] + red_n[3]);
+}

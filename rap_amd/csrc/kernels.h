@@ -319,6 +319,26 @@ int launch_nearest_neighbors(hipStream_t stream, const float* X, const int32_t* 
                              long NY, const float* R, const float* T, float gate, int32_t* idx_out, float* d2_out, NnWork* items,
                              const NnGridWs& g);
 
+// batched point-to-plane ICP (icp_plane.hip; the grid path in nn_grid.hip): launch_icp's / launch_icp_grid's arguments plus the normals
+// of Y.  partials: icp_plane_partial_bytes() per item; state: 12 doubles per problem (the fp64 pose); the rest as launch_icp
+size_t icp_plane_partial_bytes();
+int launch_icp_plane_state(hipStream_t stream, const float* R, const float* T, int K, double* state);
+int launch_icp_plane_finish(hipStream_t stream, const void* partials, const void* ranges, int K, int it, float relative_rmse_thr, double* state,
+                            float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, double* prev, int32_t* done);
+int launch_icp_plane(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals,
+                     int K, long NX, long NY, const float* init_R, const float* init_T, int max_iterations, float relative_rmse_thr, float gate,
+                     float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, NnWork* items, void* partials,
+                     void* ranges, double* prev, int32_t* done, double* state);
+int launch_icp_plane_grid(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg,
+                          const float* Y_normals, int K, long NX, long NY, const float* init_R, const float* init_T, int max_iterations,
+                          float relative_rmse_thr, float gate, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt,
+                          NnWork* items, void* partials, void* ranges, double* prev, int32_t* done, double* state, const NnGridWs& g);
+
+// surface normals from the plane fit of every point's neighbourhood (normals.hip; Open3D's estimate_normals as reference
+// dataset_process/utils/dataset_utils.py:325-358 calls it).  items: nn_max_items(N, K) NnWork; repeat: 4 bytes per segment
+int launch_estimate_normals(hipStream_t stream, const float* P, const int32_t* seg, int K, long N, int max_nn, float radius,
+                            const float* viewpoint, float* normals, float* eigenvalues, NnWork* items, int32_t* repeat);
+
 // farthest point sampling (fps.hip; reference dataset_process/utils/point_sampling_utils.py:263-305)
 int launch_fps(hipStream_t stream, const float* pts, const int32_t* cloud_start, const int32_t* cloud_len, const int32_t* Ks,
                const int32_t* starts, int C, int Kmax,

@@ -389,6 +389,30 @@ __global__ __launch_bounds__(ICP_TILE) void icp_grid_query_kernel(const float* _
   icp_moments(active, besti, best, gate, x0, x1, x2, Y, w.y_start, red_m, red_n, partials + blockIdx.x);
 }
 
+// icp_plane_query_kernel (icp_plane.hip) with the grid search: same items, same query transform, same epilogue
+__global__ __launch_bounds__(ICP_TILE) void icp_plane_grid_query_kernel(const float* __restrict__ X, const float* __restrict__ Y,
+                                                                        const float* __restrict__ Yn, const NnWork* __restrict__ items,
+                                                                        const float* __restrict__ R, const float* __restrict__ T,
+                                                                        const int32_t* __restrict__ done, float gate,
+                                                                        const NnGrid* __restrict__ grids, const unsigned* __restrict__ cell_start,
+                                                                        const float4* __restrict__ sorted, IcpPlanePartial* __restrict__ partials) {
+  __shared__ double red_m[ICP_TILE / 64][ICP_PLANE_NMOM];
+  __shared__ int red_n[ICP_TILE / 64];
+  const NnWork w = items[blockIdx.x];
+  if (w.x_len <= 0) return;
+  const int prob = w.pad0;
+  if (done[prob]) return;
+  const int q = w.q0 + threadIdx.x;
+  const bool active = q < w.x_len;
+  const size_t qi = (size_t)w.x_start + (active ? q : w.x_len - 1);
+  float qx, qy, qz;
+  icp_apply(R + (size_t)prob * 9, T + (size_t)prob * 3, X[qi * 3 + 0], X[qi * 3 + 1], X[qi * 3 + 2], qx, qy, qz);
+  float best;
+  int besti;
+  grid_search(grids[prob], Y, cell_start, sorted, qx, qy, qz, grid_gate2(gate), best, besti);
+  icp_plane_moments(active, besti, best, gate, qx, qy, qz, Y, Yn, w.y_start, red_m, red_n, partials + blockIdx.x);
+}
+
 // items of 256 queries of one problem, as icp_setup_kernel lays them out
 __global__ void nn_grid_items_kernel(const int32_t* __restrict__ x_seg, const int32_t* __restrict__ y_seg, int K, long NX, long NY,
                                      NnWork* __restrict__ items, int max_items) {
@@ -466,6 +490,27 @@ int launch_icp_grid(hipStream_t stream, const float* X, const int32_t* x_seg, co
                        (const float4*)g.sorted, (IcpPartial*)partials);
     RAP_LAUNCH_CHECK();
     if ((rc = launch_icp_finish(stream, partials, ranges, K, it, relative_rmse_thr, R, T, rmse, iterations, converged, prev, done))) return rc;
+  }
+  if (Xt) return launch_icp_apply(stream, X, items, max_items, R, T, Xt);
+  return RAP_OK;
+}
+
+int launch_icp_plane_grid(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg,
+                          const float* Y_normals, int K, long NX, long NY, const float* init_R, const float* init_T, int max_iterations,
+                          float relative_rmse_thr, float gate, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt,
+                          NnWork* items, void* partials, void* ranges, double* prev, int32_t* done, double* state, const NnGridWs& g) {
+  const int max_items = (int)nn_max_items(NX, K);
+  int rc = launch_icp_setup(stream, x_seg, y_seg, K, NX, NY, init_R, init_T, items, ranges, R, T, rmse, iterations, converged, prev, done);
+  if (rc) return rc;
+  if ((rc = launch_icp_plane_state(stream, R, T, K, state))) return rc;
+  if ((rc = launch_nn_grid_build(stream, Y, y_seg, K, NY, g))) return rc;
+  for (int it = 0; it < max_iterations; ++it) {
+    hipLaunchKernelGGL(icp_plane_grid_query_kernel, dim3(max_items), dim3(ICP_TILE), 0, stream, X, Y, Y_normals, (const NnWork*)items,
+                       (const float*)R, (const float*)T, (const int32_t*)done, gate, (const NnGrid*)g.grids, (const unsigned*)g.cell_start,
+                       (const float4*)g.sorted, (IcpPlanePartial*)partials);
+    RAP_LAUNCH_CHECK();
+    if ((rc = launch_icp_plane_finish(stream, partials, ranges, K, it, relative_rmse_thr, state, R, T, rmse, iterations, converged, prev, done)))
+      return rc;
   }
   if (Xt) return launch_icp_apply(stream, X, items, max_items, R, T, Xt);
   return RAP_OK;

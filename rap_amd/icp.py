@@ -1,4 +1,5 @@
-"""Batched point-to-point ICP on the device (``icp.hip``) and the two reference metrics that rest on it.
+"""Batched ICP on the device (point-to-point: ``icp.hip``; point-to-plane: ``icp_plane.hip``) and the two reference metrics that rest
+on it.
 
 The reference takes ICP from pytorch3d (``iterative_closest_point``; ``rectified_point_flow/eval/metrics.py:79`` and ``:261``) and runs
 it one problem at a time, with a KNN launch, an SVD launch and a host read of the convergence test per iteration.  Here one ``rap_icp``
@@ -23,6 +24,7 @@ layout X was given in), R (K,3,3) and T (K,3) with ``Xt = X @ R + T`` (row vecto
 
 
 SEARCHES = ("brute", "grid")
+ESTIMATIONS = ("point_to_point", "point_to_plane")
 
 
 def _check_search(search):
@@ -30,15 +32,33 @@ def _check_search(search):
         raise ValueError(f"search must be one of {SEARCHES}, got {search!r}")
 
 
+def _check_estimation(estimation):
+    if estimation not in ESTIMATIONS:
+        raise ValueError(f"estimation must be one of {ESTIMATIONS}, got {estimation!r}")
+
+
 def icp_packed(X, x_seg, Y, y_seg, init_R=None, init_T=None, max_iterations: int = 100, relative_rmse_thr: float = 1e-6,
-               max_correspondence_distance: float | None = None, return_Xt: bool = True, search: str = "brute") -> ICPSolution:
+               max_correspondence_distance: float | None = None, return_Xt: bool = True, search: str = "brute",
+               estimation: str = "point_to_point", y_normals=None) -> ICPSolution:
     """K problems on packed clouds: problem k aligns ``X[xs:xs+xn]`` to ``Y[ys:ys+yn]`` with ``(xs, xn) = x_seg[k]``,
     ``(ys, yn) = y_seg[k]``.  X (NX,3), Y (NY,3) fp32; x_seg, y_seg (K,2) int32 device tensors whose rows need not be contiguous or
     ordered (the x segments must not overlap); init_R (K,3,3) / init_T (K,3) or None.  Semantics, stopping rules and the treatment of
     empty problems: ``rap_icp`` in include/rapflow.h.  No host synchronisation; ``Xt`` (NX,3) starts as a copy of X, so rows outside
     every segment pass through unchanged.  ``search``: ``"brute"`` (every x against every y, ``rap_icp``) or ``"grid"`` (a uniform-grid
-    index over Y built once per call, ``rap_icp_grid``); both give the same bits."""
+    index over Y built once per call, ``rap_icp_grid``); both give the same bits.
+
+    ``estimation="point_to_plane"`` minimises the distance to the tangent plane of the neighbour instead (``rap_icp_plane`` /
+    ``rap_icp_plane_grid``: a Gauss-Newton step per iteration; on scan surfaces a few iterations instead of dozens, because points may
+    slide along the surface).  ``y_normals`` (NY,3): the normals of Y, rows with a zero or non-finite normal are left out of the fit;
+    None: estimated in the same call from Y's own segments (``estimate_normals_packed`` with 20 neighbours, no radius, no viewpoint --
+    the sign of a normal does not enter the residual; y segments may repeat, but segments that overlap without being equal can leave
+    rows without a normal: pass ``y_normals`` then).  The reported rmse is then the point-to-plane residual of the transform that
+    ENTERED the last iteration, one update behind the returned R, T."""
     _check_search(search)
+    _check_estimation(estimation)
+    plane = estimation == "point_to_plane"
+    if y_normals is not None and not plane:
+        raise ValueError("y_normals is only used by estimation='point_to_plane'")
     _require_cuda(X, "X")
     _require_cuda(Y, "Y")
     device = X.device
@@ -55,9 +75,18 @@ def icp_packed(X, x_seg, Y, y_seg, init_R=None, init_T=None, max_iterations: int
         X = torch.zeros((1, 3), dtype=torch.float32, device=device)
         xs = torch.zeros_like(xs)
         return_Xt = False
+    Yn = None
+    if plane and y_normals is not None:
+        Yn = _f32c(y_normals.to(device).reshape(-1, 3))
+        if Yn.shape[0] != Y.shape[0]:
+            raise ValueError(f"y_normals must have one row per row of Y, got {Yn.shape[0]} for {Y.shape[0]}")
     if Y.shape[0] == 0:
         Y = torch.zeros((1, 3), dtype=torch.float32, device=device)
         ys = torch.zeros_like(ys)
+        Yn = None
+    if plane and Yn is None:
+        from .normals import estimate_normals_packed
+        Yn = estimate_normals_packed(Y, ys, max_nn=20, radius=0.0)
     NX, NY = X.shape[0], Y.shape[0]
     iR = None if init_R is None else _f32c(init_R.to(device).reshape(K, 3, 3))
     iT = None if init_T is None else _f32c(init_T.to(device).reshape(K, 3))
@@ -72,10 +101,12 @@ def icp_packed(X, x_seg, Y, y_seg, init_R=None, init_T=None, max_iterations: int
         raise ValueError("max_correspondence_distance must be positive (None: no gate)")
     lib = _lib.load()
     grid = search == "grid"
-    fn, name = (lib.rap_icp_grid, "rap_icp_grid") if grid else (lib.rap_icp, "rap_icp")
-    ws = workspace(device, lib.rap_icp_grid_workspace_bytes(NX, NY, K) if grid else lib.rap_icp_workspace_bytes(NX, K))
+    name = ("rap_icp_plane" if plane else "rap_icp") + ("_grid" if grid else "")
+    fn, query = getattr(lib, name), getattr(lib, name + "_workspace_bytes")
+    ws = workspace(device, query(NX, NY, K) if grid else query(NX, K))
+    clouds = (_lib.ptr(X), _lib.ptr(xs), _lib.ptr(Y), _lib.ptr(ys)) + ((_lib.ptr(Yn),) if plane else ())
     with torch.cuda.device(device):
-        rc = fn(_lib.ptr(X), _lib.ptr(xs), _lib.ptr(Y), _lib.ptr(ys), K, NX, NY, _lib.ptr(iR), _lib.ptr(iT), int(max_iterations),
+        rc = fn(*clouds, K, NX, NY, _lib.ptr(iR), _lib.ptr(iT), int(max_iterations),
                 float(relative_rmse_thr), gate, _lib.ptr(R), _lib.ptr(T), _lib.ptr(rmse), _lib.ptr(iters), _lib.ptr(conv),
                 _lib.ptr(Xt), _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
     _lib.check(rc, name)
@@ -130,15 +161,20 @@ def _lengths(lengths, K, N, device):
 
 def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100, relative_rmse_thr: float = 1e-6,
                             max_correspondence_distance: float | None = None, x_lengths=None, y_lengths=None,
-                            search: str = "brute") -> ICPSolution:
-    """Point-to-point ICP of X onto Y: padded batches ``X (K,N,3)``, ``Y (K,M,3)`` with optional ``x_lengths`` / ``y_lengths`` (K,), or
+                            search: str = "brute", estimation: str = "point_to_point", Y_normals=None) -> ICPSolution:
+    """ICP of X onto Y (point-to-point by default): padded batches ``X (K,N,3)``, ``Y (K,M,3)`` with optional ``x_lengths`` /
+    ``y_lengths`` (K,), or
     ``(N,3)`` / ``(M,3)`` for one problem.  ``init_transform = (R, T)`` with R (K,3,3) or (3,3), T (K,3) or (3,) in the row-vector
     convention ``Xt = X @ R + T``.  pytorch3d's algorithm and defaults (rigid, no scale estimate), except that every problem of the batch
     stops on its own and that a problem whose rmse reaches exactly 0 counts as converged.  ``max_correspondence_distance`` keeps only
     the points whose neighbour lies within that distance in each fit.  Returns an ``ICPSolution``; ``Xt`` has X's shape (padding rows
     unchanged).  One ``rap_icp`` call, no host synchronisation.  ``search="grid"`` finds the same neighbours through a uniform-grid
-    index over Y (``rap_icp_grid``): the same bits, and far less work on large clouds."""
+    index over Y (``rap_icp_grid``): the same bits, and far less work on large clouds.  ``estimation="point_to_plane"``: the
+    point-to-plane estimator of ``icp_packed`` with ``Y_normals`` (K,M,3) or (M,3), estimated from Y where None."""
     _check_search(search)
+    _check_estimation(estimation)
+    if Y_normals is not None and estimation != "point_to_plane":
+        raise ValueError("Y_normals is only used by estimation='point_to_plane'")
     _require_cuda(X, "X")
     single = X.dim() == 2
     Xb = X.unsqueeze(0) if single else X
@@ -155,7 +191,10 @@ def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100
         iR, iT = init_transform[0], init_transform[1]
         iR = iR.to(device).reshape(-1, 3, 3).expand(K, 3, 3)
         iT = iT.to(device).reshape(-1, 3).expand(K, 3)
-    sol = icp_packed(Xb, x_seg, Yb, y_seg, iR, iT, max_iterations, relative_rmse_thr, max_correspondence_distance, search=search)
+    if Y_normals is not None and tuple(Y_normals.shape) != tuple(Y.shape):
+        raise ValueError(f"Y_normals must have Y's shape {tuple(Y.shape)}, got {tuple(Y_normals.shape)}")
+    sol = icp_packed(Xb, x_seg, Yb, y_seg, iR, iT, max_iterations, relative_rmse_thr, max_correspondence_distance, search=search,
+                     estimation=estimation, y_normals=Y_normals)
     return sol._replace(Xt=sol.Xt.reshape(X.shape))
 
 

@@ -7,6 +7,10 @@ section 7, row 4).  Prints one JSON line per workload; --out FILE also writes th
 
 --search grid times the same calls on the uniform-grid neighbour index (rap_icp_grid: the same results, bit for bit); its
 "pair_distances_per_s" is then the rate a brute-force search would need to keep up, not work that was done.
+
+--estimation point_to_plane times rap_icp_plane / rap_icp_plane_grid on the same clouds with the analytic normals of the surface (the
+iterations after the fourth or so run at the fixed point: the same work, which is what a per-iteration time needs).  --normals-points N
+adds a line for the normal estimation (rap_estimate_normals, 20 neighbours within 0.5) of one cloud of N points of the same surface.
 """
 from __future__ import annotations
 
@@ -29,7 +33,26 @@ def make_problems(torch, K, n, seed=2024):
         return torch.stack([x, y, 0.15 * torch.sin(5 * x) * torch.cos(4 * y) + 0.1 * x * x], dim=-1)
     th = torch.tensor(4.0 * 3.14159265 / 180.0)
     Rz = torch.tensor([[torch.cos(th), -torch.sin(th), 0.0], [torch.sin(th), torch.cos(th), 0.0], [0.0, 0.0, 1.0]])
-    return surf().cuda(), (surf() @ Rz + torch.tensor([0.03, -0.02, 0.01])).cuda()
+    X, Yl = surf(), surf()
+    x, y = Yl[..., 0], Yl[..., 1]                                     # the surface's normal (-f_x, -f_y, 1), moved with the cloud
+    nrm = torch.stack([-(0.75 * torch.cos(5 * x) * torch.cos(4 * y) + 0.2 * x), 0.6 * torch.sin(5 * x) * torch.sin(4 * y), torch.ones_like(x)], dim=-1)
+    nrm = nrm / nrm.norm(dim=-1, keepdim=True)
+    return X.cuda(), (Yl @ Rz + torch.tensor([0.03, -0.02, 0.01])).cuda(), (nrm @ Rz).cuda()
+
+
+def time_calls(torch, call, warmup, calls):
+    for _ in range(warmup):
+        out = call()
+    torch.cuda.synchronize()
+    gpu = []
+    for _ in range(calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = call()
+        e1.record()
+        torch.cuda.synchronize()
+        gpu.append(e0.elapsed_time(e1))
+    return out, gpu
 
 
 def main():
@@ -39,34 +62,35 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--search", choices=["brute", "grid"], default="brute")
+    ap.add_argument("--estimation", choices=["point_to_point", "point_to_plane"], default="point_to_point")
+    ap.add_argument("--normals-points", type=int, default=0, help="also time the normal estimation of one cloud of this many points")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
     import rap_amd
     lines = []
+    pct = lambda v, p: sorted(v)[min(len(v) - 1, int(round(p * (len(v) - 1))))]
     for name in (sorted(WORKLOADS) if a.workload == "all" else [a.workload]):
         K, n = WORKLOADS[name]
-        X, Y = make_problems(torch, K, n)
-        call = lambda: rap_amd.iterative_closest_point(X, Y, max_iterations=a.iterations, relative_rmse_thr=float("-inf"), search=a.search)
-        for _ in range(a.warmup):
-            sol = call()
-        torch.cuda.synchronize()
-        gpu = []
-        for _ in range(a.calls):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            sol = call()
-            e1.record()
-            torch.cuda.synchronize()
-            gpu.append(e0.elapsed_time(e1))
+        X, Y, Yn = make_problems(torch, K, n)
+        extra = dict(estimation=a.estimation, Y_normals=Yn) if a.estimation == "point_to_plane" else {}
+        call = lambda: rap_amd.iterative_closest_point(X, Y, max_iterations=a.iterations, relative_rmse_thr=float("-inf"), search=a.search, **extra)
+        sol, gpu = time_calls(torch, call, a.warmup, a.calls)
         assert int(sol.iterations.min()) == a.iterations and not bool(sol.converged.any()), "a problem stopped early"
-        pct = lambda v, p: sorted(v)[min(len(v) - 1, int(round(p * (len(v) - 1))))]
         med = statistics.median(gpu)
         pairs = a.iterations * K * n * n
-        lines.append(json.dumps({"workload": name, "search": a.search, "problems": K, "points": n, "iterations": a.iterations, "calls": len(gpu), "warmup": a.warmup,
+        lines.append(json.dumps({"workload": name, "search": a.search, "estimation": a.estimation, "problems": K, "points": n, "iterations": a.iterations, "calls": len(gpu), "warmup": a.warmup,
                                  "gpu_ms": {"median": med, "p10": pct(gpu, 0.1), "p90": pct(gpu, 0.9)}, "ms_per_iteration": med / a.iterations,
                                  "pair_distances_per_s": pairs / (med * 1e-3), "mean_rmse": float(sol.rmse.mean())}))
+        print(lines[-1], flush=True)
+    if a.normals_points > 0:
+        P = make_problems(torch, 1, a.normals_points)[1][0]
+        nrm, gpu = time_calls(torch, lambda: rap_amd.estimate_point_normals(P, k_neighbors=20, radius=0.5), a.warmup, a.calls)
+        assert bool(torch.isfinite(nrm).all()) and bool((nrm.norm(dim=1) > 0.5).all()), "a point without a normal"
+        lines.append(json.dumps({"workload": "normals", "points": a.normals_points, "max_nn": 20, "radius": 0.5, "calls": len(gpu), "warmup": a.warmup,
+                                 "gpu_ms": {"median": statistics.median(gpu), "p10": pct(gpu, 0.1), "p90": pct(gpu, 0.9)},
+                                 "pair_distances_per_s": a.normals_points ** 2 / (statistics.median(gpu) * 1e-3)}))
         print(lines[-1], flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
