@@ -37,7 +37,8 @@ extern "C" {
  * GEMM dispatch decision as host arithmetic), rap_call_plan (every shape-dependent decision of a model call, likewise), rap_gemm_f32_splitk_workspace_bytes and rap_gemm_f32_splitk (kernel-level access to the
  * split-K form of the fp32 residual and SiLU GEMMs of few-token calls); rap_normals_workspace_bytes, rap_estimate_normals,
  * rap_icp_plane_workspace_bytes, rap_icp_plane, rap_icp_plane_grid_workspace_bytes and rap_icp_plane_grid (point-to-plane ICP and the
- * normals it needs). */
+ * normals it needs); rap_deskew, rap_fuse_frames, rap_submap_overlap with their *_workspace_bytes queries and
+ * rap_submap_groups_connected (sweeps and poses -> submaps, their overlap matrix and the connectivity of candidate groups). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -338,6 +339,68 @@ int rap_nearest_neighbors(const float* X, const int32_t* x_seg, const float* Y, 
 size_t rap_normals_workspace_bytes(int64_t n_points, int32_t K);
 int rap_estimate_normals(const float* P, const int32_t* seg, int32_t K, int64_t n_points, int32_t max_nn, float radius,
                          const float* viewpoint, float* normals, float* eigenvalues, void* ws, size_t ws_bytes, void* stream);
+
+/* Submaps (submaps.hip): the stage of the reference's data preparation before the "views" exist
+ * (dataset_process/utils/processing_utils.py:1927-2090).  Common to the four calls below:
+ *   - F frames (sweeps) are ONE packed (n_points,3) fp32 array and cu_frames (F+1) int32 on the device, frame f = rows
+ *     [cu_frames[f], cu_frames[f+1]); it must start at 0, not decrease and end at n_points.  S submaps are contiguous runs of frames:
+ *     submap_frames (S+1) int32, submap s = frames [submap_frames[s], submap_frames[s+1]), entries in [0, F], not decreasing.  Every
+ *     table is replaced by the running maximum of its clamped entries before it indexes anything; empty frames and submaps are valid.
+ *   - poses are (F,4,4) float64, row-major, column vectors (x' = R x + t), as the reference's numpy arrays.
+ *   - the DEFERRED error: a malformed input is not known to the host when the call returns.  The call then writes NaN (n_voxels: -1,
+ *     connected: 0) to every output and ORs a bit into *status (device int32, or NULL; never cleared by a call): 1 a table had to be
+ *     changed, 2 the voxel grid of rap_submap_overlap spans 2^21 voxels or more on an axis, 4 a group of
+ *     rap_submap_groups_connected has a length outside [1, n_max] or a member outside [0, S).
+ *   - limits: n_points < 2^31, F <= 2^24, S <= 4096.  n_points == 0 is valid (the point arrays may then be NULL); F == 0 is valid
+ *     with n_points == 0 for rap_deskew and rap_fuse_frames and does nothing.
+ *   - the caller's stream, no host read or wait, no floating-point atomics (integer atomics only: results are bit-identical from call
+ *     to call), can be captured into a graph; ws >= the *_workspace_bytes query (host arithmetic, 0 for arguments the call refuses),
+ *     and nothing outside it or the outputs is written.
+ *
+ * rap_deskew: per-point motion compensation (deskewing, dataset_utils.py:682-747).  ts (n_points,) fp32 time stamps; rel_pose[f] =
+ * inv(pose[f-1]) pose[f], R a rotation by theta in [0, pi) (at theta = pi the axis is not defined: NaN).  Per frame, in fp32:
+ * tmin, tmax over the frame (NaN stamps aside); s_i = (ts_i - tmin) / (tmax - tmin) - ts_mid, and s_i = 0.5 - ts_mid where
+ * tmax - tmin <= 1e-8.  out_i = R(s_i) p_i + s_i T with R(s) = exp(s log R), the rotation about R's axis by s theta for ANY real s
+ * (what roma.rotmat_slerp(I, R, s) evaluates): axis and angle once per frame in double, Rodrigues' formula per point in fp32 with a
+ * series below 1e-3 rad.  Bit-for-bit the input where s_i == 0 and where rel_pose[f] is exactly the identity (how a caller says
+ * "frame 0 is not deskewed"; such a frame is copied whatever its stamps are, NaN included); elsewhere NaN where ts_i is NaN.
+ * Three launches. */
+size_t rap_deskew_workspace_bytes(int64_t n_points, int32_t F);
+int rap_deskew(const float* points, const float* ts, const int32_t* cu_frames, int32_t F, int64_t n_points, const double* rel_pose,
+               float ts_mid, float* out, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* rap_fuse_frames: frames -> world (create_submap_from_frames, submap_utils.py:26-50, for every submap at once: rows keep their order,
+ * so submap s is world[cu_frames[submap_frames[s]] .. cu_frames[submap_frames[s+1]])).  world_i = fp32(R p_i + t - origin) with the
+ * arithmetic in double and ONE rounding (origin (3,) float64 or NULL = 0: a 10 km offset does not cost fp32 digits);
+ * world_normals_i = fp32(R n_i / |R n_i|), divided by 1 where the norm is below 1e-8 (dataset_utils.py:402-405): a zero normal stays
+ * zero.  normals and world_normals: both or neither.  Two launches. */
+size_t rap_fuse_frames_workspace_bytes(int64_t n_points, int32_t F);
+int rap_fuse_frames(const float* points, const float* normals, const int32_t* cu_frames, int32_t F, int64_t n_points, const double* pose,
+                    const double* origin, float* world, float* world_normals, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
+/* rap_submap_overlap: the S x S matrix of calculate_point_cloud_overlap_ratio_fast (dataset_utils.py:603-650, without its random
+ * subsampling).  V_s = the set of voxels floor((R p + t) / voxel_size) (double; pose NULL: floor(p / voxel_size), points already in a
+ * common frame) of the rows of submap s, rows with a non-finite coordinate (of R p + t; of p without poses) dropped; a finite coordinate whose
+ * quotient reaches +-2^62 is not dropped: it fails the extent limit below (status bit 2).  ratio (S,S) float64, ratio[i][j] =
+ * |V_i n V_j| / |V_i u V_j| (integers divided in double: exact wherever the voxel of every point is), 0.0 where V_i or V_j is empty
+ * (i == j included), symmetric; n_voxels (S,) int64 = |V_s|.  F >= 1, 1 <= S <= 4096, voxel_size > 0 and finite.  The grid of the
+ * whole call may span at most 2^21 - 1 voxel steps per axis (status bit 2 otherwise).  Voxel keys are sorted per submap with two
+ * rocPRIM radix sorts; the intersections are binary searches of the smaller set's keys in the larger set.  The workspace query
+ * reserves rocPRIM's scratch by a rule (8 bytes per row + 64 KiB) that holds for rocPRIM with caller-owned double buffers as shipped
+ * with ROCm 7; the call asks rocPRIM for its actual need, and should a later rocPRIM want more than was reserved, the call returns
+ * RAP_ERR_WORKSPACE although ws_bytes equals the query -- then AFTER its first launches, with ratio and n_voxels not written. */
+size_t rap_submap_overlap_workspace_bytes(int64_t n_points, int32_t F, int32_t S);
+int rap_submap_overlap(const float* points, const int32_t* cu_frames, int32_t F, int64_t n_points, const double* pose,
+                       const int32_t* submap_frames, int32_t S, double voxel_size, double* ratio, int64_t* n_voxels, int32_t* status,
+                       void* ws, size_t ws_bytes, void* stream);
+
+/* rap_submap_groups_connected: the union-find of check_submap_validity (submap_utils.py:102-164) for G candidate groups at once.
+ * ratio (S,S) float64 as above; groups (G,n_max) int32, group g = its first group_len[g] entries (submap numbers), 1 <= n_max <= 64.
+ * Members a (earlier in the group) and b are joined where lo <= ratio[a][b] <= hi, both ends inclusive, NaN never; connected[g] = 1
+ * where every member is reachable from the first (a group of one: 1).  connected (G,) uint8.  G == 0 does nothing.  One launch, one
+ * wave per group, no workspace. */
+int rap_submap_groups_connected(const double* ratio, int32_t S, const int32_t* groups, const int32_t* group_len, int32_t G, int32_t n_max,
+                                double lo, double hi, uint8_t* connected, int32_t* status, void* stream);
 
 /* Batched point-to-plane ICP: rap_icp's argument list plus Y_normals (n_y_points,3) fp32, and rap_icp's rules for segments, the gate,
  * empty problems (xn == 0 or yn == 0), Xt and the execution properties.  Per problem, from R, T = init or identity:

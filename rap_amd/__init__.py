@@ -12,6 +12,8 @@ from .icp import ICPSolution, align_anchor, compute_transform_errors_icp, icp_pa
 from .modeling import RectifiedPointFlow
 from .procrustes import fit_transformations, rigidify_prediction_with_procrustes, solve_procrustes
 from .sampler import euler_step, flow_sampler, get_sampler
+from .submaps import (calculate_point_cloud_overlap_ratio_fast, check_submap_validity, create_submap_from_frames, deskew_packed, deskewing,
+                      fuse_frames_packed, groups_connected, submap_overlap_matrix)
 from .selection import (average_trajectory_rigidity_rmse, compute_overlap_ratio, compute_rigidity_rmse,
                         select_generations_by_overlap, select_generations_by_rigidity)
 
@@ -20,4 +22,6 @@ __all__ = ["PointCloudDiT", "RectifiedPointFlow", "fit_transformations", "rigidi
            "average_trajectory_rigidity_rmse", "select_generations_by_rigidity", "compute_overlap_ratio",
            "select_generations_by_overlap", "transform_and_collate", "Evaluator", "iterative_closest_point", "icp_packed", "ICPSolution",
            "align_anchor", "compute_transform_errors_icp", "nearest_neighbors_packed",
-           "estimate_normals_packed", "estimate_point_normals"]
+           "estimate_normals_packed", "estimate_point_normals", "deskew_packed", "fuse_frames_packed", "submap_overlap_matrix",
+           "groups_connected", "deskewing", "create_submap_from_frames", "calculate_point_cloud_overlap_ratio_fast",
+           "check_submap_validity"]

@@ -82,6 +82,13 @@ SIGNATURES = {
     "rap_nearest_neighbors": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, c_float, _P, _P, _P, c_size_t, _P]),
     "rap_normals_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_estimate_normals": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_float, _P, _P, _P, _P, c_size_t, _P]),
+    "rap_deskew_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "rap_deskew": (c_int32, [_P, _P, _P, c_int32, c_int64, _P, c_float, _P, _P, _P, c_size_t, _P]),
+    "rap_fuse_frames_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "rap_fuse_frames": (c_int32, [_P, _P, _P, c_int32, c_int64, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "rap_submap_overlap_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "rap_submap_overlap": (c_int32, [_P, _P, c_int32, c_int64, _P, _P, c_int32, ctypes.c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "rap_submap_groups_connected": (c_int32, [_P, c_int32, _P, _P, c_int32, c_int32, ctypes.c_double, ctypes.c_double, _P, _P, _P]),
     "rap_icp_plane_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_icp_plane": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, c_int32, c_float, c_float, _P, _P, _P, _P, _P, _P, _P,
                                 c_size_t, _P]),
