@@ -352,6 +352,36 @@ def pair_batch():
     return data, cloud, 0.25
 
 
+LARGE_PAIRS = [(16_700, 300), (300, 257)]      # 66 items of 256 sources: a second round of pair_finish_kernel's lane-strided sum; then
+#                                                an ordinary pair, whose first item is therefore not item 0
+
+
+@functools.lru_cache(maxsize=None)
+def large_pair_batch():
+    """LARGE_PAIRS as one packed batch for compute_pair_metrics in direct mode (the layout of pair_batch).  Every source lies either
+    0.005 .. 0.02 or 0.04 .. 0.05 from a target point and the threshold sits in the widest gap of the nearest distances around 0.03.
+    -> (data, cloud, thr, pairs): pairs as correspondence_pairs() gives them, for the float64 oracle"""
+    g = torch.Generator().manual_seed(3131)
+    pairs = []
+    for ns, nt in LARGE_PAIRS:
+        tg = torch.rand(nt, 3, generator=g)
+        pick = torch.randint(0, nt, (ns,), generator=g)
+        r = torch.where(torch.rand(ns, generator=g) < 0.5, 0.005 + 0.015 * torch.rand(ns, generator=g), 0.04 + 0.01 * torch.rand(ns, generator=g))
+        sg = tg[pick] + r[:, None] * torch.nn.functional.normalize(torch.randn(ns, 3, generator=g), dim=1)
+        sp = sg + 0.03 * torch.randn(ns, 3, generator=g)
+        tp = tg + 0.03 * torch.randn(nt, 3, generator=g)
+        d = torch.cdist(sg.double(), tg.double()).min(dim=1).values.numpy()
+        pairs.append({"sg": sg, "tg": tg, "sp": sp, "tp": tp, "thr": gap_threshold(d, 0.03)})
+    ppp = torch.tensor(LARGE_PAIRS, dtype=torch.int64)
+    off, cu = offsets_of(ppp)
+    B = len(pairs)
+    data = {"pointclouds_gt": torch.cat([x for p in pairs for x in (p["sg"], p["tg"])]), "points_per_part": ppp,
+            "cu_seqlens_batch": cu.to(torch.int32), "scales": torch.tensor([0.25 / p["thr"] for p in pairs], dtype=torch.float32),
+            "rotations": torch.eye(3).repeat(B, 2, 1, 1), "translations": torch.zeros(B, 2, 3)}
+    cloud = torch.cat([x for p in pairs for x in (p["sp"], p["tp"])])
+    return data, cloud, 0.25, pairs
+
+
 # ---------------------------------------------------------------------------------------------
 # voxel down-sampling and coverage
 # ---------------------------------------------------------------------------------------------

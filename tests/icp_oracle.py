@@ -226,3 +226,144 @@ def metrics_batch(seed=7):
     return dict(gt=f(gt), cond=f(cond), pred=f(pred), ppp=ppp, anchor=anchor, cu=cu, R_gt=R_gt.astype(np.float32),
                 t_gt=t_gt.astype(np.float32), R_pred=R_pred.astype(np.float32), t_pred=t_pred.astype(np.float32),
                 scale=np.array([0.8, 1.0, 1.3], np.float32))
+
+
+# ---------------------------------------------------------------------------------------------
+# table scale: K = 300 problems in one call, and one problem of more than 64 items (tests/test_table_scale_gpu.py)
+# ---------------------------------------------------------------------------------------------
+BATCH_K = 300
+BATCH_MARGIN = 5e-5            # the smallest nearest / second-nearest gap (a distance) of every compared problem, over all its iterations:
+#                                five times the 1e-5 of the normals tests, fifty times what fp32 moves a distance by
+# the small surface pairs of the batch: problem number -> (seed, nx, ny), seeds chosen so that both estimators keep BATCH_MARGIN
+BATCH_SURFACES = {5: (117, 48, 96), 13: (126, 48, 96), 21: (136, 64, 128), 29: (138, 48, 96), 37: (139, 64, 128), 45: (146, 80, 160),
+                  53: (148, 64, 128), 61: (153, 48, 96), 69: (154, 64, 128), 77: (156, 48, 96), 85: (161, 80, 160), 93: (174, 48, 96),
+                  101: (178, 64, 128), 109: (187, 64, 128), 117: (201, 48, 96), 125: (210, 48, 96), 133: (216, 48, 96), 141: (231, 48, 96),
+                  149: (240, 48, 96), 157: (247, 64, 128), 165: (253, 64, 128), 173: (265, 64, 128), 181: (270, 48, 96), 189: (273, 48, 96),
+                  197: (277, 64, 128), 205: (282, 48, 96), 213: (295, 64, 128), 221: (300, 48, 96), 229: (306, 48, 96), 237: (316, 64, 128),
+                  245: (336, 48, 96), 253: (339, 48, 96), 261: (343, 64, 128), 269: (349, 64, 128), 277: (357, 48, 96)}
+BATCH_EMPTY_X, BATCH_EMPTY_Y, BATCH_ONE_POINT = (259, 281), (263, 285), (267, 289)
+# problem number -> the earlier problem (below 256) whose y segment it searches: its grid's owner sits in another round of the plan loop
+BATCH_SHARED_Y = {271: 3, 275: 129, 279: 254, 293: 3, 297: 40}
+
+
+# THE POINT-TO-PLANE VARIANT of the batch.  An exact fit ends at a point-to-plane rmse of 1e-8 that is made of input roundings alone, and
+# whether that still decreases by a millionth is no property of the algorithm: the iteration count of such a problem cannot be compared.
+# So in this variant every lattice problem carries a residual (residual_lattice_pair: the x points moved by up to a tenth of the spacing,
+# as big_pair does), and the seeds -- BATCH_PLANE_STEPS[k] steps of 300 past 1000 + k for a lattice, BATCH_PLANE_SURFACES for a surface
+# pair -- are the first of their sequence at which no stopping decision of the yardstick is a matter of rounding
+# (icp_plane_oracle.BATCH_THR; tests/test_icp_plane_host.py proves it for every problem).
+BATCH_PLANE_SURFACES = {5: (126, 48, 96), 13: (129, 48, 96), 21: (141, 48, 96), 29: (148, 64, 128), 37: (161, 80, 160), 45: (162, 48, 96),
+                        53: (168, 48, 96), 61: (184, 64, 128), 69: (187, 64, 128), 77: (195, 48, 96), 85: (201, 48, 96), 93: (209, 80, 160),
+                        101: (213, 48, 96), 109: (216, 48, 96), 117: (227, 80, 160), 125: (228, 48, 96), 133: (231, 48, 96), 141: (235, 64, 128),
+                        149: (247, 64, 128), 157: (261, 48, 96), 165: (268, 64, 128), 173: (273, 48, 96), 181: (276, 48, 96), 189: (282, 48, 96),
+                        197: (288, 48, 96), 205: (295, 64, 128), 213: (297, 48, 96), 221: (300, 48, 96), 229: (313, 64, 128), 237: (316, 64, 128),
+                        245: (329, 80, 160), 253: (336, 48, 96), 261: (339, 48, 96), 269: (343, 64, 128), 277: (348, 48, 96)}
+BATCH_PLANE_STEPS = "0" * 39 + "1" + "0" * 260      # one digit per problem
+
+
+def batch_lattice_args(k, plane=False):
+    return dict(seed=1000 + k + 300 * (int(BATCH_PLANE_STEPS[k], 36) if plane else 0), side=4 + k % 3, degrees=0.5 + (k % 11) / 10.0)
+
+
+def residual_lattice_pair(seed, side, degrees, spacing=0.05):
+    """make_lattice_pair with every x point moved by up to a tenth of the spacing per axis: the same correspondences, a residual near 3e-3"""
+    X, Y, R, T = make_lattice_pair(seed, side, spacing, degrees)
+    X = X.astype(np.float64) + np.random.default_rng(seed + 7).uniform(-0.1, 0.1, X.shape) * spacing
+    return X.astype(np.float32), Y, R, T
+
+
+@functools.lru_cache(maxsize=None)
+def batch300(plane=False):
+    """(plane: the variant for the point-to-plane estimator, see BATCH_PLANE_STEPS)
+    -> dict(X, Y, x_seg (K,2), y_seg (K,2), parts, init_R (K,3,3), init_T (K,3), kinds): K = 300 problems whose segments lie in
+    a shuffled order with 0 to 3 junk rows between them.  Lattice pairs with a known truth (make_lattice_pair: side 4..6, 0.5..1.5
+    degrees), the surface pairs of BATCH_SURFACES (which take different numbers of iterations), empty-X, empty-Y and one-point problems
+    at numbers >= 256, and the problems of BATCH_SHARED_Y: the x of an earlier lattice problem without its last 5 points, against that
+    problem's own y segment.  parts[k] = (X_k, Y_k) as the yardstick takes them (None for a problem that is not compared); init_R, init_T:
+    a start of up to 0.2 degrees and 5e-4 per problem, for the variant with init_transform."""
+    rng = np.random.default_rng(300)
+    K = BATCH_K
+    xs, ys, kinds, y_of = [None] * K, [None] * K, ["lattice"] * K, list(range(K))
+    surfaces = BATCH_PLANE_SURFACES if plane else BATCH_SURFACES
+    for k in range(K):
+        if k in BATCH_SURFACES:
+            xs[k], ys[k] = pair(*surfaces[k])
+            kinds[k] = "surface"
+        else:
+            xs[k], ys[k] = (residual_lattice_pair if plane else make_lattice_pair)(**batch_lattice_args(k, plane))[:2]
+    for k, j in BATCH_SHARED_Y.items():
+        assert kinds[j] == "lattice" and j < 256 <= k
+        xs[k], ys[k], y_of[k], kinds[k] = xs[j][:-5], ys[j], j, "shared_y"
+    for k in BATCH_EMPTY_X:
+        xs[k], kinds[k] = xs[k][:0], "empty_x"
+    for k in BATCH_EMPTY_Y:
+        ys[k], kinds[k] = ys[k][:0], "empty_y"
+    for k in BATCH_ONE_POINT:
+        xs[k], kinds[k] = xs[k][:1], "one_point"
+    junk = lambda: rng.uniform(-1, 1, (int(rng.integers(0, 4)), 3)).astype(np.float32)
+
+    def pack(clouds, own):
+        rows, seg, at = [junk()], np.zeros((K, 2), np.int32), 0
+        at = rows[0].shape[0]
+        for k in rng.permutation(K):
+            if own[k] != k:
+                continue
+            seg[k] = (at, clouds[k].shape[0])
+            rows += [clouds[k], junk()]
+            at += clouds[k].shape[0] + rows[-1].shape[0]
+        for k in range(K):
+            if own[k] != k:
+                seg[k] = seg[own[k]]
+        return np.concatenate(rows), seg
+    X, x_seg = pack(xs, list(range(K)))
+    Y, y_seg = pack(ys, y_of)
+    for k in BATCH_EMPTY_X:
+        x_seg[k] = (17, 0)
+    for k in BATCH_EMPTY_Y:
+        y_seg[k] = (40, 0)
+    init_R = np.stack([rotation(rng.normal(size=3), rng.uniform(0.0, 0.2)).T for _ in range(K)]).astype(np.float32)
+    init_T = rng.uniform(-5e-4, 5e-4, (K, 3)).astype(np.float32)
+    parts = [(xs[k], ys[k]) if kinds[k] in ("lattice", "surface", "shared_y") else None for k in range(K)]
+    return dict(X=X, Y=Y, x_seg=x_seg, y_seg=y_seg, parts=parts, init_R=init_R, init_T=init_T, kinds=kinds)
+
+
+@functools.lru_cache(maxsize=None)
+def batch300_solved(init=False, f32=False):
+    """the yardstick of every compared problem of batch300(), None for the others (f32: the same statements in fp32, without margins)"""
+    b = batch300()
+    return [None if p is None else icp(p[0], p[1], init=(b["init_R"][k].astype(np.float64), b["init_T"][k].astype(np.float64)) if init else None,
+                                       dtype=np.float32 if f32 else np.float64, margins=not f32)
+            for k, p in enumerate(b["parts"])]
+
+
+BIG_PLANE_SEEDS = (11, 12)
+BIG_NX = (16_700, 33_000)      # 66 and 129 items of 256 queries: a second and a third round of the finish kernels' lane-strided sum
+
+
+@functools.lru_cache(maxsize=None)
+def big_pair(nx, seed=0, side=6, spacing=0.05):
+    """-> X (nx,3), Y (side^3,3) fp32: the points of a lattice pair's X drawn nx times with replacement, each moved by up to a tenth of
+    the spacing per axis; Y as make_lattice_pair leaves it (moved by one degree, permuted).  Not an exact fit: the rmse stays near 3e-3."""
+    X0, Y, _, _ = make_lattice_pair(seed, side, spacing)
+    rng = np.random.default_rng(seed + 1)
+    X = X0[rng.integers(0, X0.shape[0], nx)].astype(np.float64) + rng.uniform(-0.1, 0.1, (nx, 3)) * spacing
+    return X.astype(np.float32), Y
+
+
+@functools.lru_cache(maxsize=None)
+def big_batch(nx, plane=False):
+    """the big problem as problem 1 of 3, between two small lattice problems: its first item is not item 0.  plane: the two neighbours
+    carry a residual (BIG_PLANE_SEEDS, chosen as BATCH_PLANE_STEPS is).  -> X, Y, x_seg, y_seg, parts"""
+    small = (lambda seed, side: residual_lattice_pair(seed, side, 1.0)[:2]) if plane else (lambda seed, side: make_lattice_pair(seed, side)[:2])
+    sa, sc = BIG_PLANE_SEEDS if plane else (11, 12)
+    a, b, c = small(sa, 4), big_pair(nx), small(sc, 5)
+    X, Y = np.concatenate([a[0], b[0], c[0]]), np.concatenate([c[1], a[1], b[1]])
+    na, nb, nc = a[0].shape[0], b[0].shape[0], c[0].shape[0]
+    x_seg = np.array([[0, na], [na, nb], [na + nb, nc]], np.int32)
+    y_seg = np.array([[nc, na], [nc + na, b[1].shape[0]], [0, nc]], np.int32)
+    return X, Y, x_seg, y_seg, [a, b, c]
+
+
+@functools.lru_cache(maxsize=None)
+def big_solved(nx):
+    return [icp(x, y) for x, y in big_batch(nx)[4]]

@@ -19,6 +19,8 @@ every ratio are demanded exactly.  The rule guards against ROUNDING; where the q
 that q is the fp32 coordinate itself -- it is not needed, and the two cases at the 21-bit limit of the key (|q| about 1e6, where no
 coordinate can be 1.0 away from an integer) are of that kind (``exact_quotient``).
 """
+import functools
+
 import numpy as np
 
 # worst |fp32 formula - fp64 formula| / max(1, |p|_inf + |T|_inf) over deskew_case() and deskew_short_case(), every ts_mid: measured by
@@ -168,6 +170,76 @@ def ulps(got, want64):
     return np.abs(got.view(np.int32).astype(np.int64) - want.view(np.int32).astype(np.int64)).max() if got.size else 0
 
 
+SCALE_F = (255, 256, 257, 4099)              # frame counts on either side of one round of the 256-thread table walk, and sixteen rounds
+SCALE_LONG = 1100                            # rows of the one long frame of scale_frames_case: more than a chunk of 1024
+
+
+def scale_frames_case(F):
+    """F sweeps whose lengths cycle through 0..7 rows (every eighth frame is empty, and a 1024-row chunk lies in about 290 frames), except
+    frame F // 2 with SCALE_LONG rows (so that some chunks lie in ONE frame) and an angle of 0.3.  The other angles cycle through DESKEW_THETAS; every 37th frame has
+    an exactly-identity rel_pose.  Stamps as in deskew_case: the largest first, the smallest last.  Poses and unit normals for the fuse
+    of the same frames.  -> dict(points, ts, cu, rel_pose, pose, normals, identity (frame numbers), long (frame number))"""
+    rng = np.random.default_rng(9000 + F)
+    lengths = [k % 8 for k in range(F)]
+    lengths[F // 2] = SCALE_LONG
+    identity = [k for k in range(5, F, 37) if k != F // 2]
+    pts, ts, rel, pose = [], [], [], []
+    for k, n in enumerate(lengths):
+        pts.append(frame_points(rng, n))
+        t = rng.uniform(0.0, 0.1, n).astype(np.float32)
+        if n >= 2:
+            t[0], t[-1] = np.float32(0.1), np.float32(0.0)
+        ts.append(t)
+        rel.append(np.eye(4) if k in identity else make_pose(rng, 0.3 if k == F // 2 else DESKEW_THETAS[k % len(DESKEW_THETAS)]))
+        pose.append(make_pose(rng, rng.uniform(0.1, 3.0), 30.0))
+    P = np.concatenate(pts)
+    v = rng.normal(size=(P.shape[0], 3))
+    cu = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    return dict(points=P, ts=np.concatenate(ts), cu=cu, rel_pose=np.stack(rel), pose=np.stack(pose),
+                normals=(v / np.linalg.norm(v, axis=1, keepdims=True)).astype(np.float32), identity=identity, long=F // 2)
+
+
+def table_per(n):
+    """entries of an n-entry table that one thread of the sanitising block walks (rap_amd/csrc/submaps.hip: ceil(n / 256))"""
+    return -(-n // 256)
+
+
+def malformed_tables(cu, at, limit, need_last=True):
+    """single-entry edits of a prefix table at entry `at` (which must not be a thread's first): one decreasing entry, one entry past
+    `limit`, and (where the last entry has to be `limit`) a last entry one short of it.  -> [(name, table)]"""
+    n, per = len(cu), table_per(len(cu))
+    assert per >= 2 and at % per != 0 and 10 < at < n - 1 and (not need_last or (n - 1) % per != 0)
+    out = []
+    dec = cu.copy()
+    dec[at] = cu[at - 10]
+    assert dec[at] < dec[at - 1]
+    out.append(("decreasing", dec))
+    past = cu.copy()
+    past[at] = limit + 5
+    out.append(("past the limit", past))
+    if need_last:
+        short = cu.copy()
+        short[-1] = limit - 1
+        assert short[-1] >= short[-2]                        # still non-decreasing: ONLY the end is wrong
+        out.append(("short of the end", short))
+    return out
+
+
+def boundary_repeats_case(F=4099):
+    """a VALID table of F one-row frames whose only repeated values sit where one thread's entries end and the next one's begin: frame
+    per * t - 1 is empty for every t >= 1, so cu[per * t] == cu[per * t - 1].  -> points, ts, cu, rel_pose"""
+    rng = np.random.default_rng(17)
+    per = table_per(F + 1)
+    lengths = np.ones(F, np.int64)
+    lengths[np.arange(per, F + 1, per) - 1] = 0
+    cu = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    rep = np.flatnonzero(np.diff(cu) == 0) + 1
+    assert rep.size >= 200 and (rep % per == 0).all()
+    n = int(cu[-1])
+    rel = np.stack([make_pose(rng, DESKEW_THETAS[k % len(DESKEW_THETAS)]) for k in range(F)])
+    return frame_points(rng, n), rng.uniform(0.0, 0.1, n).astype(np.float32), cu, rel
+
+
 # ---- fuse -----------------------------------------------------------------------------------------------------------------------------
 def transform_points(points, transform):
     homo = np.hstack([points, np.ones((points.shape[0], 1))])
@@ -288,7 +360,7 @@ def _build(rng, voxel_sets_, voxel_size, posed, dup=2, frames_per_submap=2, extr
         w = w[rng.permutation(w.shape[0])]
         if extra_rows and s in extra_rows:
             w = np.concatenate([w[:1], extra_rows[s], w[1:]]) if w.shape[0] else extra_rows[s]
-        for part in np.array_split(w, frames_per_submap):
+        for part in np.array_split(w, frames_per_submap if isinstance(frames_per_submap, int) else frames_per_submap[s]):
             M = make_pose(rng, rng.uniform(0.1, 3.0), 20.0) if posed else None
             local = (part - M[:3, 3]) @ M[:3, :3] if posed else part            # R^T (w - t), rows
             pts.append(local.astype(np.float32))
@@ -355,6 +427,88 @@ def extent_case(span):
     pts = np.array([[lo + 0.5, 0.5, -0.5], [lo + span + 0.5, 0.5, -0.5]], np.float32)
     assert (pts.astype(np.float64)[:, 0] == np.array([lo + 0.5, lo + span + 0.5])).all()
     return dict(points=pts, cu=np.array([0, 1, 2], np.int32), submap_frames=np.array([0, 1, 2], np.int32), pose=None, voxel_size=1.0)
+
+
+# ---- overlap at table scale -------------------------------------------------------------------------------------------------------------
+def overlap_matrix_incidence(world_list, voxel_size):
+    """overlap_matrix by an incidence matrix: M (S,V) says which of the V distinct voxels of the call each submap holds, M M^T in float64
+    holds every |A n B| (sums of at most V ones: exact), and the ratio is the same division of the same two integers -- the same doubles
+    as the set form (tests/test_submaps_host.py holds the two together), at a cost that allows S = 4096"""
+    vox, sid = [], []
+    for s, w in enumerate(world_list):
+        w = np.asarray(w, np.float64).reshape(-1, 3)
+        w = w[np.isfinite(w).all(axis=1)]
+        vox.append(np.floor(w / voxel_size).astype(np.int64))
+        sid.append(np.full(w.shape[0], s, np.int64))
+    S = len(world_list)
+    vox, sid = np.concatenate(vox).reshape(-1, 3), np.concatenate(sid)
+    if vox.shape[0] == 0:
+        return np.zeros((S, S)), np.zeros(S, np.int64)
+    _, col = np.unique(vox, axis=0, return_inverse=True)
+    col = col.reshape(-1)
+    M = np.zeros((S, int(col.max()) + 1))
+    M[sid, col] = 1.0
+    inter = M @ M.T
+    n = np.diag(inter).copy()
+    union = n[:, None] + n[None, :] - inter
+    both = (n[:, None] > 0) & (n[None, :] > 0)
+    ratio = np.where(both, inter / np.where(both, union, 1.0), 0.0)
+    assert (inter == np.round(inter)).all()
+    return ratio, n.astype(np.int64)
+
+
+SCALE_S = (255, 256, 257, 1025, 4096)       # submap counts on either side of one round of 256, five rounds, and SUB_MAX_S itself
+SCALE_POOL = 1500                            # distinct voxels that every submap of a scale case draws from
+SCALE_COUNTS = (40, 64, 100)                 # the sizes that most submaps tie in ...
+SCALE_RARE = (0, 1, 256, 257)                # ... and the ones a few have: empty, one voxel, a full chunk of keys, a chunk and one
+
+
+@functools.lru_cache(maxsize=None)
+def overlap_scale_case(S):
+    """S submaps of 1 to 4 frames whose unique-voxel counts are SCALE_COUNTS (thirds of the submaps tie in size: the intersect kernel's
+    "smaller side, lower index on a tie" rule decides most pairs) with SCALE_RARE at about every 25th submap, all drawn from one pool of
+    SCALE_POOL voxels, one point per voxel.  Posed except at S = 4096, where instead an uncovered frame lies before and after the submaps
+    (rows of no submap on both sides of the sort by submap number, S + 1 = 4097 among them), each with a row far outside the grid."""
+    rng = np.random.default_rng(5000 + S)
+    posed = S != 4096
+    pool = _lattice(rng, SCALE_POOL)
+    counts = rng.choice(SCALE_COUNTS, S)
+    rare = rng.permutation(S)[:max(8, S // 25)]
+    counts[rare] = np.resize(SCALE_RARE, rare.shape[0])
+    sets = [pool[rng.permutation(SCALE_POOL)[:n]] for n in counts]
+    c = _build(rng, sets, 0.5 if posed else 2.0, posed, dup=1, frames_per_submap=[int(v) for v in rng.integers(1, 5, S)])
+    if not posed:
+        far = np.array([[1e7, -1e7, 1e7]], np.float32)
+        lead, tail = [np.concatenate([far, ((pool[:n] + 0.5) * 2.0).astype(np.float32)]) for n in (300, 200)]
+        c["points"] = np.concatenate([lead, c["points"], tail])
+        c["cu"] = np.concatenate([[0], c["cu"] + lead.shape[0], [c["cu"][-1] + lead.shape[0] + tail.shape[0]]]).astype(np.int32)
+        c["submap_frames"] = (c["submap_frames"] + 1).astype(np.int32)
+    c["counts"] = counts
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def overlap_scale_oracle(S):
+    c = overlap_scale_case(S)
+    return overlap_matrix_incidence(case_world(c), c["voxel_size"])
+
+
+CONN_S, CONN_G = 1025, 1027                  # the real matrix of overlap_scale_case(1025); a group count that is no multiple of 4
+CONN_LO, CONN_HI = 0.02, 1.0
+CONN_BAD = (5, 514, 1026)                    # malformed groups: lengths 0, a member equal to S, length 0 -- the last group among them
+
+
+def connectivity_scale_case():
+    """-> ratio (the oracle's matrix of overlap_scale_case(CONN_S)), groups (CONN_G lists of 1 to 64 members drawn from all of [0, S), the
+    lengths cycling), lo, hi, bad (the malformed groups' numbers).  The thresholds are such that both verdicts occur in at least a
+    quarter of the well-formed groups (tests/test_submaps_host.py)."""
+    ratio, _ = overlap_scale_oracle(CONN_S)
+    rng = np.random.default_rng(31)
+    groups = [[int(v) for v in rng.integers(0, CONN_S, 1 + (7 * g) % 64)] for g in range(CONN_G)]
+    groups[CONN_BAD[0]] = []
+    groups[CONN_BAD[1]] = groups[CONN_BAD[1]][:3] + [CONN_S]
+    groups[CONN_BAD[2]] = []
+    return ratio, groups, CONN_LO, CONN_HI, CONN_BAD
 
 
 # ---- connectivity -----------------------------------------------------------------------------------------------------------------------

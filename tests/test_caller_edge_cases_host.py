@@ -187,6 +187,20 @@ def test_correspondence_margins_and_ties():
     assert int(data["cu_seqlens_batch"][-1]) == cloud.shape[0] and thr == 0.25
 
 
+def test_large_pair_has_more_than_64_items_and_keeps_the_threshold_margin():
+    data, cloud, thr, pairs = C.large_pair_batch()
+    assert data["points_per_part"].tolist() == [list(x) for x in C.LARGE_PAIRS] and cloud.shape == data["pointclouds_gt"].shape
+    assert -(-C.LARGE_PAIRS[0][0] // C.NN_TILE) > 64 and int(data["cu_seqlens_batch"][-1]) == cloud.shape[0] and thr == 0.25
+    for p in pairs:
+        d = torch.cdist(p["sg"].double(), p["tg"].double()).min(dim=1).values
+        m = float((d - p["thr"]).abs().min())
+        n = O.compute_correspondence_rmse(p["sg"], p["tg"], p["sp"], p["tp"], p["thr"])[1]
+        print(f"{tuple(p['sg'].shape)} x {tuple(p['tg'].shape)}: thr {p['thr']:.6f}, margin {m:.2e}, {n} correspondences")
+        assert m > C.MARGIN and 0.2 < n / p["sg"].shape[0] < 0.8
+        counted = (d <= p["thr"]).numpy()                                  # sources of both kinds in the first AND in the last item
+        assert 0 < counted[:C.NN_TILE].sum() < C.NN_TILE and 0 < counted[-(len(d) % C.NN_TILE or C.NN_TILE):].sum()
+
+
 def test_chamfer_batch_is_the_size_sweep():
     c = C.chamfer_batch()
     assert (c["cu"][1:] - c["cu"][:-1]).tolist() == C.NN_SIZES == [1, 2, 255, 256, 257, 511, 512, 513, 769]

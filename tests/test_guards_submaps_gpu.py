@@ -36,6 +36,15 @@ def t(a, dtype=None):
 
 def test_deskew_writes_only_its_rows_and_its_exact_workspace(lib, dev):
     P, ts, cu, rel, _ = O.deskew_case()                      # the last frame ends exactly at the end of the arrays
+    deskew_guard(lib, dev, P, ts, cu, rel)
+
+
+def test_deskew_with_thousands_of_frames_writes_only_its_rows_and_its_exact_workspace(lib, dev):
+    c = O.scale_frames_case(4099)                            # table copies of 16 KiB and 32 KiB: far larger than the carver's alignment
+    deskew_guard(lib, dev, c["points"], c["ts"], c["cu"], c["rel_pose"])
+
+
+def deskew_guard(lib, dev, P, ts, cu, rel):
     N, F = P.shape[0], len(cu) - 1
     want = O.deskew_packed(P, ts, cu, rel, 0.0)
     scale = O.deskew_scale(P, cu, rel)
@@ -88,9 +97,9 @@ def test_fuse_frames_writes_only_its_rows_and_its_exact_workspace(lib, dev, with
     refused_call_wrote_nothing(dev, call)
 
 
-@pytest.mark.parametrize("name", ["counts_posed", "edge", "three"])
+@pytest.mark.parametrize("name", ["counts_posed", "edge", "three", "scale_257"])
 def test_submap_overlap_writes_only_its_matrix_and_its_exact_workspace(lib, dev, name):
-    c0 = O.overlap_case(name)
+    c0 = O.overlap_scale_case(257) if name == "scale_257" else O.overlap_case(name)      # S = 257: tables of more than 256 entries
     N, F, S = c0["points"].shape[0], len(c0["cu"]) - 1, len(c0["submap_frames"]) - 1
     want, want_n = O.overlap_matrix(O.case_world(c0), c0["voxel_size"])
     need = lib.rap_submap_overlap_workspace_bytes(N, F, S)

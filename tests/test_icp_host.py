@@ -103,3 +103,69 @@ def test_yardstick_rules_for_empty_and_tiny_problems():
     assert one.converged and one.iterations == 2 and one.rmse < 1e-12
     lim = O.icp(X, Y, max_iterations=1)
     assert lim.iterations == 1 and not lim.converged
+
+
+# ---- the inputs at table scale (tests/test_table_scale_gpu.py) ---------------------------------------------------------------------------
+def test_batch_of_300_problems_is_what_the_gpu_test_takes_it_for():
+    b = O.batch300()
+    K, kinds, xs, ys = O.BATCH_K, b["kinds"], b["x_seg"], b["y_seg"]
+    assert K == 300 and xs.shape == ys.shape == (K, 2) and b["init_R"].shape == (K, 3, 3) and b["init_T"].shape == (K, 3)
+    count = {name: kinds.count(name) for name in set(kinds)}
+    print(f"X {b['X'].shape[0]} rows, Y {b['Y'].shape[0]} rows: {count}")
+    assert count["lattice"] >= 250 and count["surface"] >= 30
+    for special in (O.BATCH_EMPTY_X, O.BATCH_EMPTY_Y, O.BATCH_ONE_POINT, tuple(O.BATCH_SHARED_Y)):
+        assert len(special) >= 2 and min(special) >= 256
+    assert all(xs[k, 1] == 0 for k in O.BATCH_EMPTY_X) and all(ys[k, 1] == 0 for k in O.BATCH_EMPTY_Y) and all(xs[k, 1] == 1 for k in O.BATCH_ONE_POINT)
+    for k, j in O.BATCH_SHARED_Y.items():                             # the owner of the grid sits in the first round of the plan loop
+        assert j < 256 <= k and tuple(ys[k]) == tuple(ys[j]) and tuple(xs[k]) != tuple(xs[j])
+    assert len(set(O.BATCH_SHARED_Y.values())) < len(O.BATCH_SHARED_Y)      # one target shared by three problems
+    # shuffled, with junk between: the segments do not lie in problem order, do not overlap, and leave rows uncovered
+    for seg, rows, shared in ((xs, b["X"], {}), (ys, b["Y"], O.BATCH_SHARED_Y)):
+        own = [k for k in range(K) if seg[k, 1] > 0 and k not in shared]
+        order = sorted(own, key=lambda k: seg[k, 0])
+        assert order != own and sum(a > c for a, c in zip(order, order[1:])) > K // 3
+        ends = [(int(seg[k, 0]), int(seg[k, 0] + seg[k, 1])) for k in order]
+        assert all(e0 <= s1 for (_, e0), (s1, _) in zip(ends, ends[1:])) and ends[-1][1] <= rows.shape[0]
+        assert sum(int(seg[k, 1]) for k in own) < rows.shape[0] - K // 2
+    for k, p in enumerate(b["parts"]):
+        if p is not None:
+            assert np.array_equal(b["X"][xs[k, 0]:xs[k, 0] + xs[k, 1]], p[0]) and np.array_equal(b["Y"][ys[k, 0]:ys[k, 0] + ys[k, 1]], p[1])
+    assert sum(p is not None for p in b["parts"]) == K - 6            # every problem is compared but the empty and the one-point ones
+    ang = np.degrees(np.arccos(np.clip((np.trace(b["init_R"].astype(np.float64), axis1=1, axis2=2) - 1) / 2, -1, 1)))
+    assert 0.15 < ang.max() < 0.21 and len({tuple(r.ravel()) for r in b["init_R"]}) == K
+
+
+@pytest.mark.parametrize("init", [False, True], ids=["identity", "init_transform"])
+def test_batch_of_300_keeps_its_neighbour_margin_and_spreads_its_iteration_counts(init):
+    b, ref, f32 = O.batch300(), O.batch300_solved(init), O.batch300_solved(init, f32=True)
+    compared = [k for k in range(O.BATCH_K) if ref[k] is not None]
+    margin = min(ref[k].nn_margin for k in compared)
+    counts = sorted({ref[k].iterations for k in compared})
+    print(f"{len(compared)} problems: smallest nearest / second-nearest gap {margin:.2e} (required {O.BATCH_MARGIN:.0e}), iteration counts {counts}")
+    assert O.BATCH_MARGIN > 1e-5 and margin >= O.BATCH_MARGIN         # above the 1e-5 of the normals tests
+    assert all(ref[k].converged for k in compared)
+    assert len(counts) >= 3 and len({ref[k].iterations for k in compared if k >= 256}) >= 3      # neighbours in done[] finish at different iterations
+    assert all(f32[k].iterations == ref[k].iterations for k in compared)      # the stop is no rounding decision
+    worst = max(max(np.abs(f32[k].R - ref[k].R).max(), np.abs(f32[k].T - ref[k].T).max(), abs(f32[k].rmse - ref[k].rmse)) for k in compared)
+    print(f"fp32 statements vs fp64: worst deviation {worst:.2e}")
+    assert worst < 5e-7
+    if not init:                                                      # the truth of the lattice pairs is known
+        dev = [max(np.abs(ref[k].R - R).max(), np.abs(ref[k].T - T).max())
+               for k in compared if b["kinds"][k] == "lattice" for R, T in [O.make_lattice_pair(**O.batch_lattice_args(k))[2:]]]
+        print(f"{len(dev)} lattice pairs: the yardstick within {max(dev):.2e} of the truth")
+        assert max(dev) < 1e-7
+        for k, j in O.BATCH_SHARED_Y.items():                          # a subset of an exact fit is an exact fit
+            assert np.abs(ref[k].R - ref[j].R).max() < 1e-7
+    else:
+        assert max(np.abs(ref[k].R - O.batch300_solved(False)[k].R).max() for k in compared if b["kinds"][k] != "surface") < 1e-7
+
+
+@pytest.mark.parametrize("nx", O.BIG_NX)
+def test_big_problem_has_more_than_64_items_and_keeps_its_margin(nx):
+    X, Y, xs, ys, parts = O.big_batch(nx)
+    ref = O.big_solved(nx)
+    items = -(-nx // 256)
+    print(f"{nx} x {parts[1][1].shape[0]}: {items} items, gap {ref[1].nn_margin:.2e}, {ref[1].iterations} iterations, rmse {ref[1].rmse:.2e}")
+    assert items > (64 if nx < 20_000 else 128) and xs[1, 0] > 0 and 216 <= parts[1][1].shape[0] <= 1000
+    assert all(r.converged and r.nn_margin >= O.BATCH_MARGIN for r in ref) and ref[1].rmse > 1e-3
+    assert O.icp(*parts[1], dtype=np.float32, margins=False).iterations == ref[1].iterations

@@ -136,3 +136,45 @@ def test_yardstick_rules_for_empty_unusable_and_coplanar_targets():
     assert abs(one.R[0, 1] - one.R[1, 0]) < 1e-12 and np.abs(one.T[:2]).max() < 1e-12 and abs(one.T[2]) > 1e-3
     lim = P.icp_plane(X, Y, Yn, max_iterations=1)
     assert lim.iterations == 1 and not lim.converged
+
+
+# ---- the inputs at table scale (tests/test_table_scale_gpu.py) ---------------------------------------------------------------------------
+@pytest.mark.parametrize("init", [False, True], ids=["identity", "init_transform"])
+def test_batch_of_300_with_normals_keeps_its_margins_and_every_count_is_decided(init):
+    b, p2p, (Yn, per) = O.batch300(True), O.batch300(), P.batch300_normals()
+    ref, f32 = P.batch300_solved(init), P.batch300_solved(init, f32=True)
+    compared = [k for k in range(O.BATCH_K) if ref[k] is not None]
+    assert Yn.shape == b["Y"].shape and len(compared) == O.BATCH_K - 6
+    # the variant differs from the point-to-point batch in the points alone: the same kinds, the same starts, lattices of the same sizes
+    assert b["kinds"] == p2p["kinds"] and np.array_equal(b["init_R"], p2p["init_R"]) and np.array_equal(b["init_T"], p2p["init_T"])
+    assert all(b["x_seg"][k, 1] == p2p["x_seg"][k, 1] for k in compared if b["kinds"][k] != "surface")
+    assert set(O.BATCH_PLANE_SURFACES) == set(O.BATCH_SURFACES) and len(O.BATCH_PLANE_STEPS) == O.BATCH_K
+    for k in compared:
+        a, n = b["y_seg"][k]
+        assert np.array_equal(Yn[a:a + n], per[k]) and np.abs(np.linalg.norm(per[k], axis=1) - 1.0).max() < 1e-6
+    margin, cond = min(ref[k].nn_margin for k in compared), min(ref[k].cond for k in compared)
+    counts = sorted({ref[k].iterations for k in compared})
+    print(f"{len(compared)} problems: smallest neighbour gap {margin:.2e} (required {O.BATCH_MARGIN:.0e}), smallest lambda_min / lambda_max {cond:.2e}, "
+          f"iteration counts {counts}, smallest final rmse {min(ref[k].rmse for k in compared):.1e}")
+    assert margin >= O.BATCH_MARGIN and cond > 1e-6 and all(ref[k].converged and f32[k].converged for k in compared)
+    worst = max(max(np.abs(f32[k].R - ref[k].R).max(), np.abs(f32[k].T - ref[k].T).max(), abs(f32[k].rmse - ref[k].rmse)) for k in compared)
+    print(f"fp32 moved points vs fp64: worst deviation {worst:.2e}")
+    assert worst < 1e-7
+    # the iteration count of a problem is compared where no rounding decides it (icp_plane_oracle.BATCH_THR): that has to be (all but) all
+    decided = P.batch300_decided(init)
+    moved = max(abs(x - y) for k in decided for x, y in zip(ref[k].rels, f32[k].rels))      # what the fp32 moved points make of a relative decrease
+    print(f"{len(decided)} of {len(compared)} problems have a decided count, iterations {sorted({ref[k].iterations for k in decided})}, "
+          f"{sum(k >= 256 for k in decided)} of them at numbers >= 256; fp32 moved points move a relative decrease by up to "
+          f"{moved:.1e} (threshold {P.BATCH_THR:.0e})")
+    assert len(decided) >= 0.98 * len(compared) and sum(k >= 256 for k in decided) >= 30
+    assert len({ref[k].iterations for k in decided}) >= 3 and len({ref[k].iterations for k in decided if k >= 256}) >= 2
+    assert moved < P.BATCH_THR / 100                                  # a factor of 10 from the threshold is far out of its reach
+
+
+@pytest.mark.parametrize("nx", O.BIG_NX)
+def test_big_problem_with_normals_keeps_its_margin_and_decided_counts(nx):
+    ref, f32 = P.big_solved(nx), P.big_solved(nx, f32=True)
+    print(f"{nx}: gap {ref[1].nn_margin:.2e}, iterations {[r.iterations for r in ref]}, rmse {ref[1].rmse:.2e}, lambda_min / lambda_max {ref[1].cond:.2e}")
+    assert all(r.converged and r.nn_margin >= O.BATCH_MARGIN and r.cond > 1e-6 for r in ref)
+    assert all(P.decided(r, f) for r, f in zip(ref, f32)) and ref[1].rmse > 1e-3      # the two small neighbours too: they carry a residual
+    assert max(np.abs(f32[1].R - ref[1].R).max(), np.abs(f32[1].T - ref[1].T).max(), abs(f32[1].rmse - ref[1].rmse)) < 1e-7

@@ -110,3 +110,22 @@ def test_batched_pairs_agree_with_the_single_pair_function_at_tile_edges(dev):
         assert pm[b, 1] == np.float32(ratio)
         assert abs(float(pm[b, 0]) - float(rmse)) <= 2e-6 * float(rmse), (b, pm[b, 0], float(rmse))
         assert np.isinf(pm[b, 2])                                         # no transform error without predicted poses
+
+
+def test_a_pair_of_more_than_64_items_matches_the_float64_oracle(dev):
+    """16 700 sources are 66 items of 256: pair_finish_kernel's lane-strided sum of item partials takes a second round, which no other
+    pair of the suite reaches (the largest has 4096 sources).  The ordinary pair after it starts at item 66.  Against the float64
+    oracle on the scaled parts, under test_correspondence_rmse_at_tile_edges' bounds: the count exactly, the rmse to 2e-6 relative + 1e-7."""
+    data, cloud, thr, pairs = C.large_pair_batch()
+    pm = metrics.compute_pair_metrics({k: v.to(dev) for k, v in data.items()}, cloud.to(dev), distance_threshold=thr).double().cpu().numpy()
+    again = metrics.compute_pair_metrics({k: v.to(dev) for k, v in data.items()}, cloud.to(dev), distance_threshold=thr).double().cpu().numpy()
+    assert np.array_equal(pm, again)
+    for b, p in enumerate(pairs):
+        s = data["scales"][b].double()
+        o_rmse, o_n, o_ratio, _ = O.compute_correspondence_rmse(p["sg"].double() * s, p["tg"].double() * s, p["sp"].double() * s, p["tp"].double() * s, thr)
+        print(f"{tuple(p['sg'].shape)} x {tuple(p['tg'].shape)}: count {int(pm[b, 3])} (oracle {o_n}), rmse {pm[b, 0]:.6f} (oracle {float(o_rmse):.6f}, "
+              f"relative deviation {abs(pm[b, 0] - float(o_rmse)) / float(o_rmse):.2e})")
+        assert int(pm[b, 3]) == o_n and o_n >= 1
+        assert pm[b, 1] == np.float32(o_n / p["sg"].shape[0])
+        assert abs(pm[b, 0] - float(o_rmse)) < 2e-6 * float(o_rmse) + 1e-7
+        assert np.isinf(pm[b, 2])                                         # no transform error without predicted poses

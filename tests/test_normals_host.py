@@ -181,3 +181,38 @@ def test_edge_sweep_lattices_keep_their_neighbour_sets_apart(n):
     assert gap.min() >= P.SWEEP_GAP, (n, gap.min())
     if n >= 255:
         assert counts.min() < 3 <= counts.max() and counts.max() <= 12      # the radius leaves some rows without an estimate, and binds
+
+
+# ---- the 300-segment batch (tests/test_table_scale_gpu.py) ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("max_nn", P.NORMALS_MAX_NN)
+def test_batch_of_300_segments_keeps_its_neighbour_sets_apart(max_nn):
+    b = P.normals_batch300()
+    seg, K = b["seg"], P.NORMALS_K
+    lengths = seg[:, 1]
+    assert K == 300 and set(lengths) == set(P.NORMALS_LENGTHS) | {0, 1, 2}
+    assert {int(n) for n in lengths[256:]} >= {0, 1, 2, 255, 257}                     # every kind also past the first round of the item kernel
+    for k, j in P.NORMALS_REPEATS.items():
+        assert k >= 256 > 0 <= j < k and tuple(seg[k]) == tuple(seg[j]) and lengths[k] >= 12
+    assert min(P.NORMALS_REPEATS.values()) < 256 <= max(P.NORMALS_REPEATS.values())
+    own = [k for k in range(K) if lengths[k] > 0 and k not in P.NORMALS_REPEATS]
+    order = sorted(own, key=lambda k: seg[k, 0])
+    ends = [(int(seg[k, 0]), int(seg[k, 0] + seg[k, 1])) for k in order]
+    assert order != own and all(e0 <= s1 for (_, e0), (s1, _) in zip(ends, ends[1:])) and ends[-1][1] <= b["P"].shape[0]
+    assert 300 < (~b["covered"]).sum() and b["covered"].sum() == sum(int(lengths[k]) for k in own)
+    for k in own:
+        assert np.array_equal(b["P"][seg[k, 0]:seg[k, 0] + seg[k, 1]], b["clouds"][k])
+        assert np.array_equal(np.sort(b["clouds"][k], axis=0), np.sort(P.sweep_lattice(int(lengths[k])), axis=0))
+    same = [k for k in own if lengths[k] == 40]
+    assert len(same) > 10 and not np.array_equal(b["clouds"][same[0]], b["clouds"][same[1]])      # the same rows in another order
+    ref = P.normals_batch300_solved(max_nn, True)
+    gap = min(r[3].min() for r in ref if r is not None)
+    clear, rows = 0, 0
+    for k in own:
+        n, eig, counts, _ = ref[k]
+        assert (counts == min(max_nn, lengths[k])).all()
+        toward = b["viewpoint"][k].astype(np.float64) - b["clouds"][k].astype(np.float64)
+        clear += (np.abs((n * toward).sum(axis=1)) >= P.NORMALS_VIEW_CLEAR * np.linalg.norm(toward, axis=1))[counts >= 3].sum()
+        rows += (counts >= 3).sum()
+    print(f"max_nn {max_nn}: smallest neighbour gap {gap:.2e} (required {P.SWEEP_GAP:.0e}); {clear} of {rows} normals clear of the viewpoint's flip")
+    assert gap >= P.SWEEP_GAP and clear == rows > 7000                 # every row: the GPU test compares every sign
+    assert len({tuple(v) for v in b["viewpoint"]}) == K - len(P.NORMALS_REPEATS)

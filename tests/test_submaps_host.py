@@ -171,6 +171,104 @@ def test_connectivity_case_has_both_verdicts_and_exact_bounds():
     assert sum(verdicts) >= 5 and sum(not v for v in verdicts) >= 5
 
 
+# ---- the inputs at table scale (tests/test_table_scale_gpu.py) ------------------------------------------------------------------------------
+@pytest.mark.parametrize("F", O.SCALE_F)
+def test_scale_frames_case_spans_hundreds_of_frames_per_chunk_and_has_both_kinds_of_chunk(F):
+    c = O.scale_frames_case(F)
+    cu, n = c["cu"], np.diff(c["cu"])
+    assert len(cu) == F + 1 and set(n) == set(range(8)) | {O.SCALE_LONG} and n[c["long"]] == O.SCALE_LONG
+    frame_of = lambda r: int(np.searchsorted(cu, r, side="right") - 1)
+    frames_of = lambda a, b: frame_of(min(b, cu[-1]) - 1) - frame_of(a) + 1       # first to last frame of the rows, the empty ones between them included
+    per_chunk = [frames_of(a, a + 1024) for a in range(0, int(cu[-1]), 1024)]
+    print(f"F {F}: {cu[-1]} rows, frames per 1024-row chunk {min(per_chunk)} .. {max(per_chunk)}")
+    assert max(per_chunk) > 16 * (17 if F == 4099 else 5)                   # a chunk of rows in that many rounds of 16 cached frames
+    if F == 4099:
+        assert min(per_chunk) < max(per_chunk) // 4                         # and one that lies mostly in the long frame
+    assert len(c["identity"]) >= 6 and all(np.array_equal(c["rel_pose"][k], np.eye(4)) for k in c["identity"])
+    assert any(n[k] >= 2 for k in c["identity"]) and c["long"] not in c["identity"]
+    th = [np.linalg.norm(O.rotvec(M[:3, :3])) for M in c["rel_pose"][:40]]
+    assert all(any(abs(t - want) <= 1e-9 + 1e-6 * want for t in th) for want in O.DESKEW_THETAS)
+    assert np.abs(np.linalg.norm(c["normals"], axis=1) - 1.0).max() < 1e-6
+    four = np.arange(0, int(cu[-1]) - 768, 1)                                # a lane's four rows (256 apart) in four different frames
+    f_of = np.searchsorted(cu, np.stack([four + 256 * k for k in range(4)]), side="right") - 1
+    assert (np.diff(f_of, axis=0) > 0).any(axis=0).sum() > 500               # the frame switches inside a lane's four rows ...
+    assert F != 4099 or (np.diff(f_of, axis=0) > 0).all(axis=0).any()        # ... three times
+
+
+def test_malformed_scale_tables_are_single_edits_away_from_a_threads_first_entry():
+    c = O.scale_frames_case(4099)
+    cu, N = c["cu"], c["points"].shape[0]
+    per = O.table_per(len(cu))
+    assert per == 17
+    edits = O.malformed_tables(cu, 3001, N)
+    assert [name for name, _ in edits] == ["decreasing", "past the limit", "short of the end"]
+    for name, bad in edits:
+        at = np.flatnonzero(bad != cu)
+        assert at.size == 1 and at[0] % per != 0 and at[0] // per > 0, name      # one entry; not a thread's first; not thread 0's
+    sf = O.overlap_scale_case(1025)["submap_frames"]
+    per = O.table_per(len(sf))
+    assert per == 5
+    for name, bad in O.malformed_tables(sf, 1023, int(sf[-1]), need_last=False):
+        at = np.flatnonzero(bad != sf)
+        assert at.size == 1 and at[0] % per != 0 and at[0] // per > 0, name
+    o = O.overlap_scale_case(1025)
+    assert len(O.malformed_tables(o["cu"], 2001, o["points"].shape[0])) == 3 and 2001 % O.table_per(len(o["cu"])) != 0
+    P, ts, cu, rel = O.boundary_repeats_case()
+    assert (np.diff(cu) >= 0).all() and cu[0] == 0 and cu[-1] == P.shape[0] == ts.shape[0] and len(cu) == 4100
+
+
+def test_incidence_oracle_equals_the_set_oracle():
+    cases = [(name, O.overlap_case(name)) for name in O.OVERLAP_CASES] + [("scale 257", O.overlap_scale_case(257))]
+    for name, c in cases:
+        world = O.case_world(c)
+        a, an = O.overlap_matrix(world, c["voxel_size"])
+        b, bn = O.overlap_matrix_incidence(world, c["voxel_size"])
+        assert np.array_equal(a, b) and np.array_equal(an, bn) and b.dtype == np.float64, name      # as doubles
+    r, n = O.overlap_matrix_incidence([np.zeros((0, 3)), np.zeros((0, 3))], 1.0)
+    assert not r.any() and not n.any()
+
+
+@pytest.mark.parametrize("S", O.SCALE_S)
+def test_overlap_scale_inputs_keep_the_margin_rule_and_tie_in_size(S):
+    c = O.overlap_scale_case(S)
+    world = O.case_world(c)
+    margin = min(O.voxel_margin(w, c["voxel_size"]) for w in world)
+    ratio, nv = O.overlap_scale_oracle(S)
+    pairs = np.triu_indices(S, 1)
+    both = ((nv[:, None] > 0) & (nv[None, :] > 0))[pairs]
+    share = (ratio[pairs] > 0).sum() / both.sum()
+    print(f"S {S}: {c['points'].shape[0]} rows in {len(c['cu']) - 1} frames, smallest margin {margin:.2e}, {share:.0%} of the pairs intersect, "
+          f"sizes {dict(zip(*np.unique(nv, return_counts=True)))}")
+    assert margin >= 1e-6 and not O.exact_quotient(c)
+    assert (c["pose"] is not None) == (S != 4096)
+    assert len(world) == S and np.array_equal(nv, c["counts"])
+    assert set(np.diff(c["submap_frames"])) == {1, 2, 3, 4}
+    for rare in O.SCALE_RARE:
+        assert (nv == rare).sum() >= 2
+    for tie in O.SCALE_COUNTS:                                           # the ordering rule decides among many submaps of equal size
+        assert (nv == tie).sum() >= S // 5
+    assert share > 0.5 and np.array_equal(ratio, ratio.T) and (np.diag(ratio) == (nv > 0)).all()
+    assert min(w.min() for w in world if w.size) < 0
+    if S == 4096:                                                        # rows before the first and after the last submap, far outside the grid
+        sf, cu = c["submap_frames"], c["cu"]
+        assert sf[0] == 1 and sf[-1] == len(cu) - 2 and cu[1] > 256 and cu[-1] - cu[-2] > 0
+        assert np.abs(c["points"][0]).min() >= 1e7 and np.abs(c["points"][cu[-2]]).min() >= 1e7
+        assert np.abs(np.concatenate(world)).max() < 100
+
+
+def test_connectivity_scale_case_has_both_verdicts_in_a_quarter_of_the_groups_each():
+    ratio, groups, lo, hi, bad = O.connectivity_scale_case()
+    assert ratio.shape == (O.CONN_S, O.CONN_S) and len(groups) == O.CONN_G == 1027 and O.CONN_G % 4
+    good = [g for k, g in enumerate(groups) if k not in bad]
+    assert {len(g) for g in good} == set(range(1, 65))
+    assert min(min(g) for g in good) < 8 and max(max(g) for g in good) >= O.CONN_S - 8
+    verdicts = [O.groups_connected(ratio, g, lo, hi) for g in good]
+    print(f"{sum(verdicts)} of {len(verdicts)} groups connected at lo = {lo}")
+    assert sum(verdicts) >= len(groups) // 4 and len(verdicts) - sum(verdicts) >= len(groups) // 4
+    assert [len(groups[k]) for k in bad] == [0, 4, 0] and groups[bad[1]][-1] == O.CONN_S
+    assert len({k // 4 for k in bad}) == 3 and bad[-1] == O.CONN_G - 1      # three different blocks of four groups, the last one partial
+
+
 # ---- the C ABI without a GPU ----------------------------------------------------------------------------------------------------------------
 def test_workspace_queries_are_host_arithmetic():
     lib = _lib.load()
