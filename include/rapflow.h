@@ -38,7 +38,8 @@ extern "C" {
  * split-K form of the fp32 residual and SiLU GEMMs of few-token calls); rap_normals_workspace_bytes, rap_estimate_normals,
  * rap_icp_plane_workspace_bytes, rap_icp_plane, rap_icp_plane_grid_workspace_bytes and rap_icp_plane_grid (point-to-plane ICP and the
  * normals it needs); rap_deskew, rap_fuse_frames, rap_submap_overlap with their *_workspace_bytes queries and
- * rap_submap_groups_connected (sweeps and poses -> submaps, their overlap matrix and the connectivity of candidate groups). */
+ * rap_submap_groups_connected (sweeps and poses -> submaps, their overlap matrix and the connectivity of candidate groups);
+ * rap_part_acc_workspace_bytes and rap_part_acc (part accuracy and the part matching that matched_part_ids arguments take). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -247,6 +248,21 @@ int rap_chamfer_rmse(const float* pointclouds_gt, const float* pointclouds_pred,
 int rap_correspondence_rmse(const float* source_gt, const float* target_gt, const float* source_pred, const float* target_pred,
                             int32_t n_source, int32_t n_target, float distance_threshold, float* out3, void* ws, size_t ws_bytes,
                             void* stream);
+
+/* Replaces compute_part_acc (reference eval/metrics.py:92-163) for a whole packed batch, without a host round trip.
+ * gt, pred (TP,3) packed by cu_batch (B+1,) int32 and points_per_part (B,P) int64 -- rap_overlap_ratio's layout; P <= 256.
+ *   cd[b,i,j] = mean_{x in gt_i} min_{y in pred_j} |x-y|^2 + mean_{y in pred_j} min_{x in gt_i} |x-y|^2   (no root, no 1/2)
+ * cd_out (B,P,P) fp32 or NULL, indexed by part SLOT, NaN where either part is empty.
+ * cost = (cd >= threshold) over the non-empty parts of a sample (n of them) is assigned as scipy.optimize.linear_sum_assignment
+ * assigns it -- the same permutation, not only the same value.  part_acc_out (B,) = matched pairs with cd < threshold / n.
+ * matched_out (B,P) int64 in the reference's indexing: row i and value j count the NON-EMPTY parts in order, entries from n on are 0
+ * (equal to slot indices only when no empty part precedes a used one).  A sample without a non-empty part: NaN and zeros.
+ * Deterministic bit for bit.  ws >= rap_part_acc_workspace_bytes(TP, B, P) = two planes of TP * P floats, the work list and
+ * O(B * P) words (0 for P > 256).  B = 0: RAP_OK, nothing launched. */
+size_t rap_part_acc_workspace_bytes(int64_t TP, int32_t B, int32_t P);
+int rap_part_acc(const float* pointclouds_gt, const float* pointclouds_pred, const int64_t* points_per_part, const int32_t* cu_batch,
+                 int32_t B, int32_t P, int64_t TP, float threshold, float* part_acc_out, int64_t* matched_out, float* cd_out,
+                 void* ws, size_t ws_bytes, void* stream);
 
 /* Scan-pair metrics of a whole packed batch with P = 2, as Evaluator._compute_metrics forms them per pair in a Python loop (reference
  * eval/evaluator.py:124-248 with compute_correspondence_rmse, eval/metrics.py:386-469, and compute_approximate_transform_error, :487-508,

@@ -69,6 +69,8 @@ SIGNATURES = {
     "rap_nn_metrics_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_chamfer_rmse": (c_int32, [_P, _P, _P, c_int32, c_int64, _P, _P, c_size_t, _P]),
     "rap_correspondence_rmse": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_float, _P, _P, c_size_t, _P]),
+    "rap_part_acc_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "rap_part_acc": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int64, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "rap_pair_metrics_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_pair_metrics": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int64, c_float, _P, _P, c_size_t, _P]),
     "rap_transform_errors_direct": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P, _P, _P]),

@@ -670,6 +670,41 @@ extern "C" int rap_correspondence_rmse(const float* source_gt, const float* targ
                                     distance_threshold, out3, w.d2a, w.nn, w.items);
 }
 
+// part accuracy and the part matching behind matched_part_ids: see part_acc.hip
+#define RAP_PART_ACC_MAX_P 256
+struct PartAccWs { int32_t* seg; float* d2a; float* d2b; NnWork* items; int32_t* count; uint32_t* ge; uint32_t* lt; size_t total; };
+static PartAccWs carve_part_acc(int64_t TP, int B, int P, char* basep) {
+  PartAccWs w; Carver c(basep);
+  const size_t words = (size_t)B * P * ((P + 31) / 32);
+  w.seg = (int32_t*)c.take((size_t)B * P * 2 * 4);
+  w.d2a = (float*)c.take((size_t)TP * P * 4);
+  w.d2b = (float*)c.take((size_t)TP * P * 4);
+  w.items = (NnWork*)c.take(part_acc_max_items((long)TP, B, P) * sizeof(NnWork));
+  w.count = (int32_t*)c.take(4);
+  w.ge = (uint32_t*)c.take(words * 4);
+  w.lt = (uint32_t*)c.take(words * 4);
+  w.total = c.total();
+  return w;
+}
+extern "C" size_t rap_part_acc_workspace_bytes(int64_t TP, int32_t B, int32_t P) {
+  return (TP < 0 || B < 0 || P < 0 || P > RAP_PART_ACC_MAX_P) ? 0 : carve_part_acc(TP, B, P, nullptr).total;
+}
+extern "C" int rap_part_acc(const float* pointclouds_gt, const float* pointclouds_pred, const int64_t* points_per_part, const int32_t* cu_batch,
+                            int32_t B, int32_t P, int64_t TP, float threshold, float* part_acc_out, int64_t* matched_out, float* cd_out,
+                            void* ws, size_t ws_bytes, void* stream) {
+  if (!points_per_part || !cu_batch || !part_acc_out || !matched_out || B < 0 || P <= 0 || P > RAP_PART_ACC_MAX_P || TP < 0 ||
+      threshold != threshold)
+    return RAP_ERR_INVALID;
+  if (TP > 0 && (!pointclouds_gt || !pointclouds_pred)) return RAP_ERR_INVALID;
+  if ((int64_t)B * P > 65535 || TP > 0x7fffffffLL / 8) return RAP_ERR_INVALID;
+  if (B == 0) return RAP_OK;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  PartAccWs w = carve_part_acc(TP, B, P, (char*)ws);
+  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_part_acc((hipStream_t)stream, pointclouds_gt, pointclouds_pred, points_per_part, cu_batch, B, P, (long)TP, threshold,
+                         part_acc_out, matched_out, cd_out, w.seg, w.d2a, w.d2b, w.items, w.count, w.ge, w.lt);
+}
+
 // batched scan-pair metrics of the evaluator + compute_transform_errors_direct: see pair_metrics.hip
 struct PairWs { NnWork* items; void* partials; void* ranges; size_t total; };
 static PairWs carve_pair(int64_t n, int B, char* basep) {

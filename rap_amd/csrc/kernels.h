@@ -273,6 +273,13 @@ int launch_chamfer_rmse(hipStream_t stream, const float* gt, const float* pred, 
 int launch_correspondence_rmse(hipStream_t stream, const float* source_gt, const float* target_gt, const float* source_pred,
                                const float* target_pred, int Ns, int Nt, float thr, float* out3, float* d2, int32_t* nn, NnWork* items);
 
+// part accuracy (part_acc.hip; reference eval/metrics.py:92-163).  seg: 2 ints per part; d2a, d2b: P * TP floats each; items:
+// part_acc_max_items(TP, B, P) NnWork; count: one int; ge_bits, lt_bits: B * P * ceil(P / 32) words each.  P <= 256
+size_t part_acc_max_items(long TP, int B, int P);
+int launch_part_acc(hipStream_t stream, const float* gt, const float* pred, const int64_t* ppp, const int32_t* cu_batch, int B, int P, long TP,
+                    float thr, float* part_acc, int64_t* matched, float* cd_out, int32_t* seg, float* d2a, float* d2b, NnWork* items,
+                    int32_t* count, uint32_t* ge_bits, uint32_t* lt_bits);
+
 // batched scan-pair metrics of the evaluator and the anchor-free pose errors (pair_metrics.hip; reference eval/evaluator.py:124-248,
 // eval/metrics.py:305-383, 487-508).  items: nn_max_items(TP, B) NnWork; partials: 16 bytes per item; ranges: 16 bytes per sample
 int launch_pair_metrics(hipStream_t stream, const float* gt, const float* cloud, const int64_t* ppp, const int32_t* cu_batch,

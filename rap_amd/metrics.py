@@ -35,6 +35,56 @@ def compute_cd(pointclouds_gt, pointclouds_pred, cu_seqlens_batch, anchor_indice
     return out
 
 
+def compute_part_acc(pointclouds_gt, pointclouds_pred, points_per_part, threshold: float = 0.01, return_matched_part_ids: bool = True,
+                     cu_seqlens_batch=None, return_cd_matrix: bool = False):
+    """Reference signature and return structure (eval/metrics.py:92-163) -> ``part_acc (B,)`` fp32, or ``(part_acc, matched_part_ids
+    (B,P) int64)``: the share of parts whose chamfer distance to the ground-truth part they are matched with is below ``threshold``,
+    under the assignment ``scipy.optimize.linear_sum_assignment`` makes of the 0/1 matrix ``cd >= threshold`` -- the same permutation,
+    computed on the device (``part_acc.hip``, ``assign.h``).  ``cd[b,i,j]`` is pytorch3d's bidirectional squared chamfer distance with
+    mean reduction between ground-truth part i and predicted part j (no root, no factor 1/2).
+
+    ``matched_part_ids`` keeps the reference's OWN indexing: row ``i`` and value ``j`` count the NON-EMPTY parts of the sample in order,
+    not the part slots, and entries from ``n_parts`` on are 0.  ``compute_transform_errors*`` index slots with it, as the reference's do:
+    the two agree only when no empty slot precedes a used one.  A sample without any non-empty part gets ``part_acc = NaN`` and zeros
+    (the reference raises there).
+
+    Clouds are ``(B,N,3)`` as in the reference, or packed ``(TP,3)`` with ``cu_seqlens_batch`` (B+1,) (an extension);
+    ``return_cd_matrix`` (an extension) appends the ``(B,P,P)`` matrix, indexed by part slot, NaN where either part is empty.  One call
+    for the whole batch, no host synchronisation (the reference copies every sample's matrix to the host).  P <= 256."""
+    _require_cuda(pointclouds_pred, "pointclouds_pred")
+    device = pointclouds_pred.device
+    B, P = points_per_part.shape
+    if cu_seqlens_batch is None:
+        if pointclouds_pred.dim() != 3:
+            raise ValueError("cu_seqlens_batch is required when the point clouds are packed (TP, 3)")
+        if pointclouds_pred.shape[0] != B:
+            raise ValueError(f"point clouds have batch size {pointclouds_pred.shape[0]}, points_per_part has {B}")
+        N = pointclouds_pred.shape[1]
+        cu = torch.arange(B + 1, dtype=torch.int32, device=device) * N
+    else:
+        cu = cu_seqlens_batch.to(device=device, dtype=torch.int32).contiguous()
+        if cu.shape[0] != B + 1:
+            raise ValueError(f"cu_seqlens_batch must have B + 1 = {B + 1} entries, got {cu.shape[0]}")
+    gt, pred = _f32c(pointclouds_gt.to(device).reshape(-1, 3)), _f32c(pointclouds_pred.reshape(-1, 3))
+    TP = pred.shape[0]
+    if gt.shape[0] != TP:
+        raise ValueError(f"pointclouds_gt has {gt.shape[0]} points, pointclouds_pred has {TP}")
+    ppp = points_per_part.to(device=device, dtype=torch.int64).contiguous()
+    acc = torch.empty((B,), dtype=torch.float32, device=device)
+    matched = torch.empty((B, P), dtype=torch.int64, device=device)
+    cd = torch.empty((B, P, P), dtype=torch.float32, device=device) if return_cd_matrix else None
+    lib = _lib.load()
+    ws = workspace(device, lib.rap_part_acc_workspace_bytes(TP, B, P))
+    with torch.cuda.device(device):
+        rc = lib.rap_part_acc(_lib.ptr(gt), _lib.ptr(pred), _lib.ptr(ppp), _lib.ptr(cu), B, P, TP, float(threshold), _lib.ptr(acc),
+                              _lib.ptr(matched), _lib.ptr(cd), _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
+    _lib.check(rc, "rap_part_acc")
+    out = (acc, matched) if return_matched_part_ids else (acc,)
+    if return_cd_matrix:
+        out = out + (cd,)
+    return out if len(out) > 1 else out[0]
+
+
 def compute_correspondence_rmse(source_gt, target_gt, source_pred, target_pred, distance_threshold: float = 0.1):
     """-> (rmse tensor, num_correspondences int, correspondence_ratio float), as the reference (one scan pair).  The two Python
     numbers of the return value are the reference's API and cost the one host read-back this function makes."""
