@@ -743,63 +743,88 @@ extern "C" int rap_transform_errors_direct(const float* R_gt, const float* t_gt,
                                         rot_err_per_part, trans_err_per_part, rot_err_mean, trans_err_mean);
 }
 
-// batched point-to-point ICP: see icp.hip
-struct IcpWs { NnWork* items; void* partials; void* ranges; double* prev; int32_t* done; size_t total; };
-static IcpWs carve_icp(int64_t n, int K, char* basep) {
+// batched ICP: point-to-point or point-to-plane (icp.hip, icp_plane.hip), on the tiled search or on a uniform-grid neighbour index
+// (nn_grid.hip).  The four entry points are one call (IcpCall, kernels.h) with two flags: plane (Y_normals given) and grid.
+#define RAP_GRID_MAX_K 65535      // the build kernels take the problem from blockIdx.y
+struct IcpWs { NnWork* items; void* partials; void* ranges; double* prev; int32_t* done; double* state; size_t total; };
+// plane: the larger partials of the point-to-plane estimator, and its fp64 pose after everything else
+static IcpWs carve_icp(int64_t n, int K, bool plane, char* basep) {
   IcpWs w; Carver c(basep);
   const size_t max_items = nn_max_items((long)n, K);
   w.items = (NnWork*)c.take(max_items * sizeof(NnWork));
-  w.partials = c.take(max_items * icp_partial_bytes());
+  w.partials = c.take(max_items * (plane ? icp_plane_partial_bytes() : icp_partial_bytes()));
   w.ranges = c.take((size_t)K * 16);
   w.prev = (double*)c.take((size_t)K * 8);
   w.done = (int32_t*)c.take((size_t)K * 4);
+  w.state = plane ? (double*)c.take((size_t)K * 12 * 8) : nullptr;
   w.total = c.total();
   return w;
 }
-extern "C" size_t rap_icp_workspace_bytes(int64_t n_x_points, int32_t K) {
-  return (n_x_points <= 0 || K <= 0) ? 0 : carve_icp(n_x_points, K, nullptr).total;
+static size_t icp_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int K, bool plane, bool grid) {
+  if (n_x_points <= 0 || K <= 0 || (grid && n_y_points <= 0)) return 0;
+  Carver c(nullptr);
+  if (grid) nn_grid_carve(c, (long)n_y_points, K);
+  return carve_icp(n_x_points, K, plane, nullptr).total + c.total();
+}
+// c: the entry point's arguments, with the caller's max_correspondence_distance in gate; the workspace pointers are filled in here
+static int icp_entry(IcpCall c, bool plane, bool grid, void* ws, size_t ws_bytes, void* stream) {
+  if (!c.X || !c.x_seg || !c.Y || !c.y_seg || (plane && !c.Y_normals) || !c.R || !c.T || !c.rmse || !c.iterations || !c.converged ||
+      c.K <= 0 || (grid && c.K > RAP_GRID_MAX_K) || c.max_iterations <= 0 || c.NX <= 0 || c.NY <= 0 || c.NX > 0x7fffffffLL / 8 ||
+      c.NY > 0x7fffffffLL / 8 || c.relative_rmse_thr != c.relative_rmse_thr || c.gate != c.gate)
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  const IcpWs w = carve_icp(c.NX, c.K, plane, (char*)ws);
+  Carver gc((char*)ws + w.total);
+  NnGridWs g = {};
+  if (grid) g = nn_grid_carve(gc, c.NY, c.K);
+  if (w.total + gc.total() > ws_bytes) return RAP_ERR_WORKSPACE;
+  c.gate = c.gate > 0.f ? c.gate : 0.f;
+  c.items = w.items; c.partials = w.partials; c.ranges = w.ranges; c.prev = w.prev; c.done = w.done; c.state = w.state;
+  c.grid = grid ? &g : nullptr;
+  return launch_icp((hipStream_t)stream, c);
+}
+extern "C" size_t rap_icp_workspace_bytes(int64_t n_x_points, int32_t K) { return icp_workspace_bytes(n_x_points, 0, K, false, false); }
+extern "C" size_t rap_icp_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
+  return icp_workspace_bytes(n_x_points, n_y_points, K, false, true);
+}
+extern "C" size_t rap_icp_plane_workspace_bytes(int64_t n_x_points, int32_t K) { return icp_workspace_bytes(n_x_points, 0, K, true, false); }
+extern "C" size_t rap_icp_plane_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
+  return icp_workspace_bytes(n_x_points, n_y_points, K, true, true);
 }
 extern "C" int rap_icp(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t NX, int64_t NY,
                        const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
                        float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt,
                        void* ws, size_t ws_bytes, void* stream) {
-  if (!X || !x_seg || !Y || !y_seg || !R || !T || !rmse || !iterations || !converged || K <= 0 || max_iterations <= 0 || NX <= 0 || NY <= 0 ||
-      NX > 0x7fffffffLL / 8 || NY > 0x7fffffffLL / 8 || relative_rmse_thr != relative_rmse_thr ||
-      max_correspondence_distance != max_correspondence_distance)
-    return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  IcpWs w = carve_icp(NX, K, (char*)ws);
-  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
-  return launch_icp((hipStream_t)stream, X, x_seg, Y, y_seg, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
-                    max_correspondence_distance > 0.f ? max_correspondence_distance : 0.f, R, T, rmse, iterations, converged, Xt, w.items,
-                    w.partials, w.ranges, w.prev, w.done);
-}
-
-// the same on a uniform-grid neighbour index, and the index as an entry point of its own: see nn_grid.hip
-#define RAP_GRID_MAX_K 65535      // the build kernels take the problem from blockIdx.y
-extern "C" size_t rap_icp_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
-  if (n_x_points <= 0 || n_y_points <= 0 || K <= 0) return 0;
-  Carver c(nullptr);
-  nn_grid_carve(c, (long)n_y_points, K);
-  return carve_icp(n_x_points, K, nullptr).total + c.total();
+  const IcpCall c = {X, x_seg, Y, y_seg, nullptr, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
+                     max_correspondence_distance, R, T, rmse, iterations, converged, Xt};
+  return icp_entry(c, false, false, ws, ws_bytes, stream);
 }
 extern "C" int rap_icp_grid(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t NX, int64_t NY,
                             const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
                             float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged,
                             float* Xt, void* ws, size_t ws_bytes, void* stream) {
-  if (!X || !x_seg || !Y || !y_seg || !R || !T || !rmse || !iterations || !converged || K <= 0 || K > RAP_GRID_MAX_K || max_iterations <= 0 ||
-      NX <= 0 || NY <= 0 || NX > 0x7fffffffLL / 8 || NY > 0x7fffffffLL / 8 || relative_rmse_thr != relative_rmse_thr ||
-      max_correspondence_distance != max_correspondence_distance)
-    return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  IcpWs w = carve_icp(NX, K, (char*)ws);
-  Carver c((char*)ws + w.total);
-  const NnGridWs g = nn_grid_carve(c, (long)NY, K);
-  if (w.total + c.total() > ws_bytes) return RAP_ERR_WORKSPACE;
-  return launch_icp_grid((hipStream_t)stream, X, x_seg, Y, y_seg, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
-                         max_correspondence_distance > 0.f ? max_correspondence_distance : 0.f, R, T, rmse, iterations, converged, Xt, w.items,
-                         w.partials, w.ranges, w.prev, w.done, g);
+  const IcpCall c = {X, x_seg, Y, y_seg, nullptr, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
+                     max_correspondence_distance, R, T, rmse, iterations, converged, Xt};
+  return icp_entry(c, false, true, ws, ws_bytes, stream);
 }
+extern "C" int rap_icp_plane(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals, int32_t K,
+                             int64_t NX, int64_t NY, const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
+                             float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged,
+                             float* Xt, void* ws, size_t ws_bytes, void* stream) {
+  const IcpCall c = {X, x_seg, Y, y_seg, Y_normals, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
+                     max_correspondence_distance, R, T, rmse, iterations, converged, Xt};
+  return icp_entry(c, true, false, ws, ws_bytes, stream);
+}
+extern "C" int rap_icp_plane_grid(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals,
+                                  int32_t K, int64_t NX, int64_t NY, const float* init_R, const float* init_T, int32_t max_iterations,
+                                  float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse,
+                                  int32_t* iterations, uint8_t* converged, float* Xt, void* ws, size_t ws_bytes, void* stream) {
+  const IcpCall c = {X, x_seg, Y, y_seg, Y_normals, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
+                     max_correspondence_distance, R, T, rmse, iterations, converged, Xt};
+  return icp_entry(c, true, true, ws, ws_bytes, stream);
+}
+
+// the neighbour index as an entry point of its own (nn_grid.hip), and the normals point-to-plane ICP needs (normals.hip)
 extern "C" size_t rap_nn_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
   if (n_x_points <= 0 || n_y_points <= 0 || K <= 0) return 0;
   Carver c(nullptr);
@@ -822,61 +847,6 @@ extern "C" int rap_nearest_neighbors(const float* X, const int32_t* x_seg, const
                                   idx_out, d2_out, items, g);
 }
 
-// batched point-to-plane ICP (icp_plane.hip; nn_grid.hip) and the normals it needs (normals.hip)
-struct IcpPlaneWs { NnWork* items; void* partials; void* ranges; double* prev; int32_t* done; double* state; size_t total; };
-static IcpPlaneWs carve_icp_plane(int64_t n, int K, char* basep) {
-  IcpPlaneWs w; Carver c(basep);
-  const size_t max_items = nn_max_items((long)n, K);
-  w.items = (NnWork*)c.take(max_items * sizeof(NnWork));
-  w.partials = c.take(max_items * icp_plane_partial_bytes());
-  w.ranges = c.take((size_t)K * 16);
-  w.prev = (double*)c.take((size_t)K * 8);
-  w.done = (int32_t*)c.take((size_t)K * 4);
-  w.state = (double*)c.take((size_t)K * 12 * 8);
-  w.total = c.total();
-  return w;
-}
-extern "C" size_t rap_icp_plane_workspace_bytes(int64_t n_x_points, int32_t K) {
-  return (n_x_points <= 0 || K <= 0) ? 0 : carve_icp_plane(n_x_points, K, nullptr).total;
-}
-extern "C" int rap_icp_plane(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals, int32_t K,
-                             int64_t NX, int64_t NY, const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
-                             float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged,
-                             float* Xt, void* ws, size_t ws_bytes, void* stream) {
-  if (!X || !x_seg || !Y || !y_seg || !Y_normals || !R || !T || !rmse || !iterations || !converged || K <= 0 || max_iterations <= 0 ||
-      NX <= 0 || NY <= 0 || NX > 0x7fffffffLL / 8 || NY > 0x7fffffffLL / 8 || relative_rmse_thr != relative_rmse_thr ||
-      max_correspondence_distance != max_correspondence_distance)
-    return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  IcpPlaneWs w = carve_icp_plane(NX, K, (char*)ws);
-  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
-  return launch_icp_plane((hipStream_t)stream, X, x_seg, Y, y_seg, Y_normals, K, (long)NX, (long)NY, init_R, init_T, max_iterations,
-                          relative_rmse_thr, max_correspondence_distance > 0.f ? max_correspondence_distance : 0.f, R, T, rmse, iterations,
-                          converged, Xt, w.items, w.partials, w.ranges, w.prev, w.done, w.state);
-}
-extern "C" size_t rap_icp_plane_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
-  if (n_x_points <= 0 || n_y_points <= 0 || K <= 0) return 0;
-  Carver c(nullptr);
-  nn_grid_carve(c, (long)n_y_points, K);
-  return carve_icp_plane(n_x_points, K, nullptr).total + c.total();
-}
-extern "C" int rap_icp_plane_grid(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals,
-                                  int32_t K, int64_t NX, int64_t NY, const float* init_R, const float* init_T, int32_t max_iterations,
-                                  float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse,
-                                  int32_t* iterations, uint8_t* converged, float* Xt, void* ws, size_t ws_bytes, void* stream) {
-  if (!X || !x_seg || !Y || !y_seg || !Y_normals || !R || !T || !rmse || !iterations || !converged || K <= 0 || K > RAP_GRID_MAX_K ||
-      max_iterations <= 0 || NX <= 0 || NY <= 0 || NX > 0x7fffffffLL / 8 || NY > 0x7fffffffLL / 8 ||
-      relative_rmse_thr != relative_rmse_thr || max_correspondence_distance != max_correspondence_distance)
-    return RAP_ERR_INVALID;
-  if (!ws) return RAP_ERR_WORKSPACE;
-  IcpPlaneWs w = carve_icp_plane(NX, K, (char*)ws);
-  Carver c((char*)ws + w.total);
-  const NnGridWs g = nn_grid_carve(c, (long)NY, K);
-  if (w.total + c.total() > ws_bytes) return RAP_ERR_WORKSPACE;
-  return launch_icp_plane_grid((hipStream_t)stream, X, x_seg, Y, y_seg, Y_normals, K, (long)NX, (long)NY, init_R, init_T, max_iterations,
-                               relative_rmse_thr, max_correspondence_distance > 0.f ? max_correspondence_distance : 0.f, R, T, rmse,
-                               iterations, converged, Xt, w.items, w.partials, w.ranges, w.prev, w.done, w.state, g);
-}
 extern "C" size_t rap_normals_workspace_bytes(int64_t n_points, int32_t K) {
   return (n_points <= 0 || K <= 0) ? 0 : align_up(nn_max_items((long)n_points, K) * sizeof(NnWork), 256) + align_up((size_t)K * 4, 256);
 }

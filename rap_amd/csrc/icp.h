@@ -1,31 +1,15 @@
-// Device pieces shared by the brute-force ICP (icp.hip), the grid search (nn_grid.hip) and the nearest-neighbour metrics
-// (nn_metrics.hip): the squared distance every search compares, the segment clamp, the row-vector transform and the moment epilogue
-// of an ICP query block.  Two search paths that share these give the same bits.
+// Device pieces of the batched ICP that its four query kernels and two finish kernels share (icp.hip, icp_plane.hip, nn_grid.hip): the
+// row-vector transform, the head of a query block, the moment epilogues of the two estimators and their partial structs, and the head
+// and the stopping rule of a finish wave.  Two search paths that end in the same epilogue give the same bits.  The search pieces
+// themselves (nn_d2, the segment clamp, the tile) are nn_tile.h's.
 #pragma once
-#include "kernels.h"
+#include "nn_tile.h"
 
-#define ICP_TILE 256
+#define ICP_TILE NN_TILE
 #define ICP_NMOM 17      // sum x (3), sum y (3), sum x_i y_j (9), sum |x|^2, sum |y|^2
 
 struct IcpPartial { double m[ICP_NMOM]; long long count; };
 struct IcpRange { int first, count, x_len, y_len; };
-
-// |q - p|^2 in fp32 from direct differences: the one expression every search compares.  hipcc contracts it to dx*dx rounded, dy*dy fused
-// onto it, dz*dz rounded, one add (v_pk_mul_f32 of dx and dz, v_fma_f32 of dy, v_add_f32 in the tiled kernels; v_mul, v_fmac, v_mul, v_add
-// in the grid walk): the same chain in nn_query_kernel, icp_query_kernel and the grid kernels, checked in their disassembly (DESIGN.md
-// section 7.2).  Pinning the chain with explicit fma / contraction pragmas was tried and costs the tiled kernels their packed math.
-__device__ __forceinline__ float nn_d2(float qx, float qy, float qz, float px, float py, float pz) {
-  const float dx = qx - px, dy = qy - py, dz = qz - pz;
-  return dx * dx + dy * dy + dz * dz;
-}
-
-// (start, len) of row k clamped to [0, limit): an inconsistent table cannot make a kernel index outside the array
-__device__ __forceinline__ void icp_segment(const int32_t* __restrict__ seg, int k, long limit, int& start, int& len) {
-  long s = seg[(size_t)k * 2], n = seg[(size_t)k * 2 + 1];
-  s = s < 0 ? 0 : s > limit ? limit : s;
-  n = n < 0 ? 0 : n > limit - s ? limit - s : n;
-  start = (int)s; len = (int)n;
-}
 
 // p R + T in fp32, row vectors (pytorch3d's _apply_similarity_transform with s = 1)
 __device__ __forceinline__ void icp_apply(const float* __restrict__ R, const float* __restrict__ T, float x, float y, float z, float& ox, float& oy,
@@ -34,6 +18,22 @@ __device__ __forceinline__ void icp_apply(const float* __restrict__ R, const flo
   oy = x * R[1] + y * R[4] + z * R[7] + T[1];
   oz = x * R[2] + y * R[5] + z * R[8] + T[2];
 }
+
+// Head of a query block.  Declares w = its item, prob = the item's problem, active = the lane has a query, (x0, x1, x2) = that query
+// (an inactive lane re-reads the item's last one) and (px, py, pz) = x R + T with the problem's current pose, in fp32: what the search
+// sees.  The whole block returns on an unused item or a finished problem.  A macro: as a function returning "go on" (its results in a
+// struct or in separate references) it moves code in the two grid query kernels.
+#define ICP_QUERY_BEGIN(X, items, R, T, done)                                                                 \
+  const NnWork w = items[blockIdx.x];                                                                         \
+  if (w.x_len <= 0) return;                                                                                   \
+  const int prob = w.pad0;                                                                                    \
+  if (done[prob]) return;                                                                                     \
+  const int q = w.q0 + threadIdx.x;                                                                           \
+  const bool active = q < w.x_len;                                                                            \
+  const size_t qi = (size_t)w.x_start + (active ? q : w.x_len - 1);                                           \
+  const float x0 = X[qi * 3 + 0], x1 = X[qi * 3 + 1], x2 = X[qi * 3 + 2];                                     \
+  float px, py, pz;                                                                                           \
+  icp_apply(R + (size_t)prob * 9, T + (size_t)prob * 3, x0, x1, x2, px, py, pz)
 
 // Epilogue of a block of ICP_TILE queries (one per lane, in X's order): the gated count and the raw moments (double) of the ORIGINAL x
 // and its neighbour y = Y[y_start + besti], summed per wave, then over the four waves in a fixed order, into the item's partial.
@@ -90,7 +90,7 @@ __device__ __forceinline__ void icp_plane_put(double v, double* __restrict__ row
   if ((threadIdx.x & 63) == 0) row[i] = v;
 }
 
-// Epilogue of a block of ICP_TILE queries for the point-to-plane step, built as icp_moments is: (px, py, pz) is the MOVED query (what
+// Epilogue of a block of ICP_TILE queries for the point-to-plane step: (px, py, pz) is the MOVED query (what
 // the search saw, fp32), y = Y[y_start + besti] its neighbour, n = Yn[y_start + besti] the neighbour's normal.  In double:
 // r = (p - y) . n, J = [p x n, n]; the gated pairs with a usable normal are summed per wave, then over the four waves in a fixed order.
 // Every thread of the block calls it.  Both search paths end here, so they return the same bits.
@@ -131,4 +131,32 @@ __device__ __forceinline__ void icp_plane_moments(bool active, int besti, float 
   if (threadIdx.x < ICP_PLANE_NMOM)
     out->m[threadIdx.x] = (red_m[0][threadIdx.x] + red_m[1][threadIdx.x]) + (red_m[2][threadIdx.x] + red_m[3][threadIdx.x]);
   if (threadIdx.x == ICP_PLANE_NMOM) out->count = (long long)(red_n[0] + red_n[1] + red_n[2] + red_n[3]);
+}
+
+// A finish wave (one per problem) starts here: declares m[NMOM] = the item partials of range r added lane-strided in item order, then
+// over the wave, and n = the number of pairs.  A macro: as a function (the range by value or as two ints, m by reference or by pointer)
+// the finish kernels get another register allocation.
+#define ICP_SUM_PARTIALS(NMOM, Partial, partials, r, m, n)                                \
+  double m[NMOM];                                                                         \
+  _Pragma("unroll") for (int i = 0; i < NMOM; ++i) m[i] = 0.0;                            \
+  long long n = 0;                                                                        \
+  for (int i = threadIdx.x; i < r.count; i += 64) {                                       \
+    const Partial* p = partials + r.first + i;                                            \
+    _Pragma("unroll") for (int j = 0; j < NMOM; ++j) m[j] += p->m[j];                     \
+    n += p->count;                                                                        \
+  }                                                                                       \
+  _Pragma("unroll") for (int i = 0; i < NMOM; ++i) m[i] = wave_sum_d(m[i]);               \
+  _Pragma("unroll") for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+
+// ... and ends here, lane 0: pytorch3d's stopping rule on the relative decrease of the rmse, and the bookkeeping of iteration `it`
+__device__ __forceinline__ void icp_finish_end(int k, int it, double rmse, double rel_thr, float* __restrict__ rmse_out,
+                                               int32_t* __restrict__ iterations, uint8_t* __restrict__ converged, double* __restrict__ prev,
+                                               int32_t* __restrict__ done) {
+  const double pv = prev[k];
+  const double rel = pv < 0.0 ? 1.0 : (pv - rmse) / pv;
+  const bool stop = pv == 0.0 || rel <= rel_thr;     // pv == 0: 0 / 0 in pytorch3d, which then runs to the limit with the same transform
+  rmse_out[k] = (float)rmse;
+  iterations[k] = it + 1;
+  if (stop) { converged[k] = 1; done[k] = 1; }
+  prev[k] = rmse;
 }

@@ -289,24 +289,9 @@ int launch_transform_errors_direct(hipStream_t stream, const float* R_gt, const 
                                    const int64_t* ppp, const int64_t* matched, const float* scale, int B, int P, float* rot_pp,
                                    float* trans_pp, float* rot_mean, float* trans_mean);
 
-// batched point-to-point ICP (icp.hip; pytorch3d's iterative_closest_point as reference eval/metrics.py:79, 261 call it).  items:
-// nn_max_items(NX, K) NnWork; partials: icp_partial_bytes() per item; ranges: 16 bytes, prev: 8 bytes, done: 4 bytes per problem
-size_t icp_partial_bytes();
-int launch_icp(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX, long NY,
-               const float* init_R, const float* init_T, int max_iterations, float relative_rmse_thr, float gate, float* R, float* T,
-               float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, NnWork* items, void* partials, void* ranges, double* prev,
-               int32_t* done);
-
-int launch_icp_setup(hipStream_t stream, const int32_t* x_seg, const int32_t* y_seg, int K, long NX, long NY, const float* init_R,
-                     const float* init_T, NnWork* items, void* ranges, float* R, float* T, float* rmse, int32_t* iterations,
-                     uint8_t* converged, double* prev, int32_t* done);
-int launch_icp_finish(hipStream_t stream, const void* partials, const void* ranges, int K, int it, float relative_rmse_thr, float* R, float* T,
-                      float* rmse, int32_t* iterations, uint8_t* converged, double* prev, int32_t* done);
-int launch_icp_apply(hipStream_t stream, const float* X, const NnWork* items, int max_items, const float* R, const float* T, float* Xt);
-
 // exact nearest neighbours over a uniform grid (nn_grid.hip): one index over the y segments of all K problems, built on the device, then
-// queried by ICP (launch_icp_grid: launch_icp's arguments and results, bit for bit) or on its own (launch_nearest_neighbors).  The
-// scratch of the index is carved by nn_grid_carve (host arithmetic in NY and K only; a null base gives the size).
+// queried by ICP (IcpCall::grid: the tiled search's results, bit for bit) or on its own (launch_nearest_neighbors).  The scratch of the
+// index is carved by nn_grid_carve (host arithmetic in NY and K only; a null base gives the size).
 struct NnGridWs {
   void* grids;            // K NnGrid
   unsigned* box;          // K x 8: the bounding box of every problem's y segment as ordered integers
@@ -318,28 +303,34 @@ struct NnGridWs {
   size_t n_cells;         // NY + 8 K + 1
 };
 NnGridWs nn_grid_carve(Carver& c, long NY, int K);
-int launch_icp_grid(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX, long NY,
-                    const float* init_R, const float* init_T, int max_iterations, float relative_rmse_thr, float gate, float* R, float* T,
-                    float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, NnWork* items, void* partials, void* ranges, double* prev,
-                    int32_t* done, const NnGridWs& g);
+int launch_nn_grid_build(hipStream_t stream, const float* Y, const int32_t* y_seg, int K, long NY, const NnGridWs& g);
 int launch_nearest_neighbors(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX,
                              long NY, const float* R, const float* T, float gate, int32_t* idx_out, float* d2_out, NnWork* items,
                              const NnGridWs& g);
 
-// batched point-to-plane ICP (icp_plane.hip; the grid path in nn_grid.hip): launch_icp's / launch_icp_grid's arguments plus the normals
-// of Y.  partials: icp_plane_partial_bytes() per item; state: 12 doubles per problem (the fp64 pose); the rest as launch_icp
+// batched ICP (icp.hip; pytorch3d's iterative_closest_point as reference eval/metrics.py:79, 261 call it): one call of K problems.
+// Y_normals chooses the estimator (null: point-to-point; else point-to-plane, icp_plane.hip), grid the search (null: tiled brute
+// force; else the index above, which the call builds).  items: nn_max_items(NX, K) NnWork; partials: icp_partial_bytes() /
+// icp_plane_partial_bytes() per item; ranges: 16 bytes, prev: 8 bytes, done: 4 bytes per problem; state (point-to-plane only): 12
+// doubles per problem, the fp64 pose.
+struct IcpCall {
+  const float* X; const int32_t* x_seg; const float* Y; const int32_t* y_seg; const float* Y_normals;
+  int K; long NX, NY;
+  const float* init_R; const float* init_T;      // (K,3,3), (K,3) or null: identity
+  int max_iterations; float relative_rmse_thr, gate;
+  float* R; float* T; float* rmse; int32_t* iterations; uint8_t* converged; float* Xt;      // Xt: (NX,3) or null
+  NnWork* items; void* partials; void* ranges; double* prev; int32_t* done; double* state;
+  const NnGridWs* grid;
+};
+size_t icp_partial_bytes();
 size_t icp_plane_partial_bytes();
-int launch_icp_plane_state(hipStream_t stream, const float* R, const float* T, int K, double* state);
-int launch_icp_plane_finish(hipStream_t stream, const void* partials, const void* ranges, int K, int it, float relative_rmse_thr, double* state,
-                            float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, double* prev, int32_t* done);
-int launch_icp_plane(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals,
-                     int K, long NX, long NY, const float* init_R, const float* init_T, int max_iterations, float relative_rmse_thr, float gate,
-                     float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, NnWork* items, void* partials,
-                     void* ranges, double* prev, int32_t* done, double* state);
-int launch_icp_plane_grid(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg,
-                          const float* Y_normals, int K, long NX, long NY, const float* init_R, const float* init_T, int max_iterations,
-                          float relative_rmse_thr, float gate, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt,
-                          NnWork* items, void* partials, void* ranges, double* prev, int32_t* done, double* state, const NnGridWs& g);
+int launch_icp(hipStream_t stream, const IcpCall& c);
+// what launch_icp enqueues from the other files (a kernel is launched from the file that defines it): the query of one iteration on the
+// grid for either estimator (nn_grid.hip); the fp64 state, the tiled query and the finish of iteration `it` of point-to-plane (icp_plane.hip)
+int launch_icp_grid_query(hipStream_t stream, const IcpCall& c);
+int launch_icp_plane_state(hipStream_t stream, const IcpCall& c);
+int launch_icp_plane_query(hipStream_t stream, const IcpCall& c);
+int launch_icp_plane_finish(hipStream_t stream, const IcpCall& c, int it);
 
 // surface normals from the plane fit of every point's neighbourhood (normals.hip; Open3D's estimate_normals as reference
 // dataset_process/utils/dataset_utils.py:325-358 calls it).  items: nn_max_items(N, K) NnWork; repeat: 4 bytes per segment

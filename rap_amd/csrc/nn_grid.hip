@@ -1,9 +1,9 @@
 // Exact nearest neighbours over a uniform grid: a second search path for the batched ICP (icp.hip) and an entry point of its own.
-// For the same inputs it returns, bit for bit, what the brute-force kernels return: the same fp32 distance (nn_d2, icp.h), the same
-// winner (smallest (d2, index) = "strict <, first arg-min"), and for ICP the same epilogue (icp_moments, icp.h) over the same items.
+// For the same inputs it returns, bit for bit, what the brute-force kernels return: the same fp32 distance (nn_d2, nn_tile.h), the same
+// winner (smallest (d2, index) = "strict <, first arg-min"), and for ICP the same query head and epilogue (icp.h) over the same items.
 //
 // The index.  Y never moves during an ICP call, so it is built once per call for all K problems, on the device, without a host read:
-//   nn_grid_plan_kernel     clamps every y segment (icp_segment); a problem whose segment equals an earlier one shares that problem's
+//   nn_grid_plan_kernel     clamps every y segment (nn_segment); a problem whose segment equals an earlier one shares that problem's
 //                           grid; the others take rows and cells from budgets of NY rows and NY + 8 K cells, in problem order.  A
 //                           problem that no longer fits (overlapping but different segments can ask for more than NY rows) is searched
 //                           by a plain loop over its rows instead: slow, and still exact
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void nn_grid_plan_kernel(const int32_t* __rest
   if (blockIdx.x != 0) return;
   for (int k = threadIdx.x; k < K; k += 256) {
     int ys, yn;
-    icp_segment(y_seg, k, NY, ys, yn);
+    nn_segment(y_seg, k, NY, ys, yn);
     grids[k].y_start = ys; grids[k].y_len = yn;
 #pragma unroll
     for (int a = 0; a < 3; ++a) { box[(size_t)k * 8 + a] = 0xffffffffu; box[(size_t)k * 8 + 3 + a] = 0u; }
@@ -365,7 +365,7 @@ __device__ __forceinline__ void grid_search(const NnGrid& g, const float* __rest
 
 __device__ __forceinline__ float grid_gate2(float gate) { return gate > 0.f ? gate * gate * GRID_GATE_MARGIN : __builtin_inff(); }
 
-// icp_query_kernel with the grid search in place of the tiled one: same items, same query transform, same epilogue
+// the two ICP query kernels with the grid search in place of the tiled one: same items, same head, same epilogue
 __global__ __launch_bounds__(ICP_TILE) void icp_grid_query_kernel(const float* __restrict__ X, const float* __restrict__ Y,
                                                                   const NnWork* __restrict__ items, const float* __restrict__ R,
                                                                   const float* __restrict__ T, const int32_t* __restrict__ done, float gate,
@@ -373,23 +373,13 @@ __global__ __launch_bounds__(ICP_TILE) void icp_grid_query_kernel(const float* _
                                                                   const float4* __restrict__ sorted, IcpPartial* __restrict__ partials) {
   __shared__ double red_m[ICP_TILE / 64][ICP_NMOM];
   __shared__ int red_n[ICP_TILE / 64];
-  const NnWork w = items[blockIdx.x];
-  if (w.x_len <= 0) return;
-  const int prob = w.pad0;
-  if (done[prob]) return;
-  const int q = w.q0 + threadIdx.x;
-  const bool active = q < w.x_len;
-  const size_t qi = (size_t)w.x_start + (active ? q : w.x_len - 1);
-  const float x0 = X[qi * 3 + 0], x1 = X[qi * 3 + 1], x2 = X[qi * 3 + 2];
-  float qx, qy, qz;
-  icp_apply(R + (size_t)prob * 9, T + (size_t)prob * 3, x0, x1, x2, qx, qy, qz);
+  ICP_QUERY_BEGIN(X, items, R, T, done);
   float best;
   int besti;
-  grid_search(grids[prob], Y, cell_start, sorted, qx, qy, qz, grid_gate2(gate), best, besti);
+  grid_search(grids[prob], Y, cell_start, sorted, px, py, pz, grid_gate2(gate), best, besti);
   icp_moments(active, besti, best, gate, x0, x1, x2, Y, w.y_start, red_m, red_n, partials + blockIdx.x);
 }
 
-// icp_plane_query_kernel (icp_plane.hip) with the grid search: same items, same query transform, same epilogue
 __global__ __launch_bounds__(ICP_TILE) void icp_plane_grid_query_kernel(const float* __restrict__ X, const float* __restrict__ Y,
                                                                         const float* __restrict__ Yn, const NnWork* __restrict__ items,
                                                                         const float* __restrict__ R, const float* __restrict__ T,
@@ -398,35 +388,25 @@ __global__ __launch_bounds__(ICP_TILE) void icp_plane_grid_query_kernel(const fl
                                                                         const float4* __restrict__ sorted, IcpPlanePartial* __restrict__ partials) {
   __shared__ double red_m[ICP_TILE / 64][ICP_PLANE_NMOM];
   __shared__ int red_n[ICP_TILE / 64];
-  const NnWork w = items[blockIdx.x];
-  if (w.x_len <= 0) return;
-  const int prob = w.pad0;
-  if (done[prob]) return;
-  const int q = w.q0 + threadIdx.x;
-  const bool active = q < w.x_len;
-  const size_t qi = (size_t)w.x_start + (active ? q : w.x_len - 1);
-  float qx, qy, qz;
-  icp_apply(R + (size_t)prob * 9, T + (size_t)prob * 3, X[qi * 3 + 0], X[qi * 3 + 1], X[qi * 3 + 2], qx, qy, qz);
+  ICP_QUERY_BEGIN(X, items, R, T, done);
   float best;
   int besti;
-  grid_search(grids[prob], Y, cell_start, sorted, qx, qy, qz, grid_gate2(gate), best, besti);
-  icp_plane_moments(active, besti, best, gate, qx, qy, qz, Y, Yn, w.y_start, red_m, red_n, partials + blockIdx.x);
+  grid_search(grids[prob], Y, cell_start, sorted, px, py, pz, grid_gate2(gate), best, besti);
+  icp_plane_moments(active, besti, best, gate, px, py, pz, Y, Yn, w.y_start, red_m, red_n, partials + blockIdx.x);
 }
 
-// items of 256 queries of one problem, as icp_setup_kernel lays them out
+// items of 256 queries of one problem, all of a problem or none
 __global__ void nn_grid_items_kernel(const int32_t* __restrict__ x_seg, const int32_t* __restrict__ y_seg, int K, long NX, long NY,
                                      NnWork* __restrict__ items, int max_items) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   int n = 0;
   for (int k = 0; k < K; ++k) {
     int xs, xn, ys, yn;
-    icp_segment(x_seg, k, NX, xs, xn);
-    icp_segment(y_seg, k, NY, ys, yn);
-    const int want = (xn + ICP_TILE - 1) / ICP_TILE;
-    if (xn > 0 && want <= max_items - n)
-      for (int q0 = 0; q0 < xn; q0 += ICP_TILE) { NnWork w = {xs, xn, q0, ys, yn, k, 0, 0}; items[n++] = w; }
+    nn_segment(x_seg, k, NX, xs, xn);
+    nn_segment(y_seg, k, NY, ys, yn);
+    nn_emit_items_whole(items, n, max_items, xs, xn, ys, yn, k);
   }
-  for (; n < max_items; ++n) { NnWork w = {0, 0, 0, 0, 0, 0, 0, 0}; items[n] = w; }
+  nn_zero_items(items, n, max_items);
 }
 
 // idx_out = row in Y of the nearest neighbour of x R + T (x where R is NULL), d2_out its squared distance; -1 / inf where there is none
@@ -450,7 +430,7 @@ __global__ __launch_bounds__(ICP_TILE) void nn_grid_query_kernel(const float* __
   d2_out[qi] = found ? best : __builtin_inff();
 }
 
-static int launch_nn_grid_build(hipStream_t stream, const float* Y, const int32_t* y_seg, int K, long NY, const NnGridWs& g) {
+int launch_nn_grid_build(hipStream_t stream, const float* Y, const int32_t* y_seg, int K, long NY, const NnGridWs& g) {
   NnGrid* grids = (NnGrid*)g.grids;
   const unsigned gx = (unsigned)((NY + 255) / 256 < GRID_BUILD_BLOCKS ? (NY + 255) / 256 : GRID_BUILD_BLOCKS);
   const unsigned nb = (unsigned)((g.n_cells + GRID_SCAN_CHUNK - 1) / GRID_SCAN_CHUNK);
@@ -476,43 +456,18 @@ static int launch_nn_grid_build(hipStream_t stream, const float* Y, const int32_
   return RAP_OK;
 }
 
-int launch_icp_grid(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX, long NY,
-                    const float* init_R, const float* init_T, int max_iterations, float relative_rmse_thr, float gate, float* R, float* T,
-                    float* rmse, int32_t* iterations, uint8_t* converged, float* Xt, NnWork* items, void* partials, void* ranges, double* prev,
-                    int32_t* done, const NnGridWs& g) {
-  const int max_items = (int)nn_max_items(NX, K);
-  int rc = launch_icp_setup(stream, x_seg, y_seg, K, NX, NY, init_R, init_T, items, ranges, R, T, rmse, iterations, converged, prev, done);
-  if (rc) return rc;
-  if ((rc = launch_nn_grid_build(stream, Y, y_seg, K, NY, g))) return rc;
-  for (int it = 0; it < max_iterations; ++it) {
-    hipLaunchKernelGGL(icp_grid_query_kernel, dim3(max_items), dim3(ICP_TILE), 0, stream, X, Y, (const NnWork*)items, (const float*)R,
-                       (const float*)T, (const int32_t*)done, gate, (const NnGrid*)g.grids, (const unsigned*)g.cell_start,
-                       (const float4*)g.sorted, (IcpPartial*)partials);
-    RAP_LAUNCH_CHECK();
-    if ((rc = launch_icp_finish(stream, partials, ranges, K, it, relative_rmse_thr, R, T, rmse, iterations, converged, prev, done))) return rc;
-  }
-  if (Xt) return launch_icp_apply(stream, X, items, max_items, R, T, Xt);
-  return RAP_OK;
-}
-
-int launch_icp_plane_grid(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg,
-                          const float* Y_normals, int K, long NX, long NY, const float* init_R, const float* init_T, int max_iterations,
-                          float relative_rmse_thr, float gate, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged, float* Xt,
-                          NnWork* items, void* partials, void* ranges, double* prev, int32_t* done, double* state, const NnGridWs& g) {
-  const int max_items = (int)nn_max_items(NX, K);
-  int rc = launch_icp_setup(stream, x_seg, y_seg, K, NX, NY, init_R, init_T, items, ranges, R, T, rmse, iterations, converged, prev, done);
-  if (rc) return rc;
-  if ((rc = launch_icp_plane_state(stream, R, T, K, state))) return rc;
-  if ((rc = launch_nn_grid_build(stream, Y, y_seg, K, NY, g))) return rc;
-  for (int it = 0; it < max_iterations; ++it) {
-    hipLaunchKernelGGL(icp_plane_grid_query_kernel, dim3(max_items), dim3(ICP_TILE), 0, stream, X, Y, Y_normals, (const NnWork*)items,
-                       (const float*)R, (const float*)T, (const int32_t*)done, gate, (const NnGrid*)g.grids, (const unsigned*)g.cell_start,
-                       (const float4*)g.sorted, (IcpPlanePartial*)partials);
-    RAP_LAUNCH_CHECK();
-    if ((rc = launch_icp_plane_finish(stream, partials, ranges, K, it, relative_rmse_thr, state, R, T, rmse, iterations, converged, prev, done)))
-      return rc;
-  }
-  if (Xt) return launch_icp_apply(stream, X, items, max_items, R, T, Xt);
+int launch_icp_grid_query(hipStream_t stream, const IcpCall& c) {
+  const NnGridWs& g = *c.grid;
+  const dim3 grid((unsigned)nn_max_items(c.NX, c.K));
+  if (c.Y_normals)
+    hipLaunchKernelGGL(icp_plane_grid_query_kernel, grid, dim3(ICP_TILE), 0, stream, c.X, c.Y, c.Y_normals, (const NnWork*)c.items,
+                       (const float*)c.R, (const float*)c.T, (const int32_t*)c.done, c.gate, (const NnGrid*)g.grids,
+                       (const unsigned*)g.cell_start, (const float4*)g.sorted, (IcpPlanePartial*)c.partials);
+  else
+    hipLaunchKernelGGL(icp_grid_query_kernel, grid, dim3(ICP_TILE), 0, stream, c.X, c.Y, (const NnWork*)c.items, (const float*)c.R,
+                       (const float*)c.T, (const int32_t*)c.done, c.gate, (const NnGrid*)g.grids, (const unsigned*)g.cell_start,
+                       (const float4*)g.sorted, (IcpPartial*)c.partials);
+  RAP_LAUNCH_CHECK();
   return RAP_OK;
 }
 

@@ -5,18 +5,16 @@
 // One kernel does the N^2 work for both: nn_query_kernel -- a block owns 256 query points (one per lane, in registers) and streams
 // the candidate set through LDS in tiles of 256 float4 (one ds_read_b128 per candidate, broadcast to the wave); direct-difference
 // fp32 squared distances, running minimum and FIRST arg-minimum (torch.min tie rule); nothing N^2 ever reaches HBM.
-#include "icp.h"
-
-#define NN_TILE 256
+#include "nn_tile.h"
 
 __global__ void nn_worklist_kernel(const int32_t* __restrict__ cu, int B, int swap_unused, NnWork* __restrict__ items, int max_items) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   int n = 0;
   for (int b = 0; b < B; ++b) {
     const int a = cu[b], e = cu[b + 1];
-    for (int q0 = 0; q0 < e - a && n < max_items; q0 += NN_TILE) { NnWork w = {a, e - a, q0, a, e - a, 0, 0, 0}; items[n++] = w; }
+    n = nn_emit_items(items, n, max_items, a, e - a, a, e - a, 0, 0);
   }
-  for (; n < max_items; ++n) { NnWork w = {0, 0, 0, 0, 0, 0, 0, 0}; items[n] = w; }
+  nn_zero_items(items, n, max_items);
 }
 
 // for every query x_i of the work item: d2[i] = min_j |x_i - y_j|^2 over the item's candidates, idx[i] = first arg-min (item-local)
@@ -30,26 +28,7 @@ __global__ __launch_bounds__(NN_TILE) void nn_query_kernel(const float* __restri
   const bool active = q < w.x_len;
   const size_t qi = (size_t)w.x_start + (active ? q : w.x_len - 1);
   const float qx = X[qi * 3 + 0], qy = X[qi * 3 + 1], qz = X[qi * 3 + 2];
-  float best = __builtin_inff();
-  int besti = -1;
-  for (int k0 = 0; k0 < w.y_len; k0 += NN_TILE) {
-    const int k = k0 + threadIdx.x;
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (k < w.y_len) {
-      const size_t ki = (size_t)w.y_start + k;
-      c.x = Y[ki * 3 + 0]; c.y = Y[ki * 3 + 1]; c.z = Y[ki * 3 + 2];
-    }
-    __syncthreads();
-    tile[threadIdx.x] = c;
-    __syncthreads();
-    const int nk = min(NN_TILE, w.y_len - k0);
-#pragma unroll 8
-    for (int j = 0; j < nk; ++j) {
-      const float4 p = tile[j];
-      const float d2 = nn_d2(qx, qy, qz, p.x, p.y, p.z);
-      if (d2 < best) { best = d2; besti = k0 + j; }      // strict <: the first minimum wins, as torch.min
-    }
-  }
+  NN_TILE_ARGMIN(tile, w.y_len, qx, qy, qz, [&](int k, float4& c) { nn_row(Y, (size_t)w.y_start + k, c); }, best, besti);
   if (active) {
     d2_out[qi] = best;
     if (idx_out) idx_out[qi] = besti;
@@ -124,9 +103,7 @@ int launch_chamfer_rmse(hipStream_t stream, const float* gt, const float* pred, 
 
 __global__ void nn_pair_worklist_kernel(int Ns, int Nt, NnWork* __restrict__ items, int max_items) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  int n = 0;
-  for (int q0 = 0; q0 < Ns && n < max_items; q0 += NN_TILE) { NnWork w = {0, Ns, q0, 0, Nt, 0, 0, 0}; items[n++] = w; }
-  for (; n < max_items; ++n) { NnWork w = {0, 0, 0, 0, 0, 0, 0, 0}; items[n] = w; }
+  nn_zero_items(items, nn_emit_items(items, 0, max_items, 0, Ns, 0, Nt, 0, 0), max_items);
 }
 
 int launch_correspondence_rmse(hipStream_t stream, const float* source_gt, const float* target_gt, const float* source_pred,

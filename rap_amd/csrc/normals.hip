@@ -6,7 +6,7 @@
 // smallest eigenvalue from an fp64 Jacobi (kabsch.h), rounded to fp32.  Fewer than three neighbours: normal and eigenvalues 0.
 //
 //   normals_items_kernel   segment table -> items of 256 queries of one segment (NnWork with x = y = the segment)
-//   normals_kernel         nn_query_kernel's tiled brute-force search: the candidate tile goes through LDS, one ds_read_b128 broadcast
+//   normals_kernel         a tiled brute-force search on nn_tile.h's tile: the candidates go through LDS, one ds_read_b128 broadcast
 //                          per candidate.  Each lane keeps the admission limit in a register: the d2 of its current max_nn-th best
 //                          once its list is full, the radius bound before.  The list of the max_nn best lives in LDS as
 //                          [slot][lane], so the lanes of a wave hit different banks; max_nn x 256 x 8 bytes beside the 4 KB tile
@@ -18,10 +18,10 @@
 //                          numbers).  The covariance pass re-reads the winners by index, in slot order.
 // No atomics, no host read, capturable; a row's bits depend on its own segment only.  There is no grid-index variant: clouds are
 // voxel-downsampled before this step.
-#include "icp.h"
+#include "nn_tile.h"
 #include "kabsch.h"
 
-#define NRM_TILE 256
+#define NRM_TILE NN_TILE
 
 struct NormalsParams {
   const float* P;
@@ -41,9 +41,9 @@ __global__ __launch_bounds__(256) void normals_items_kernel(const int32_t* __res
   if (blockIdx.x != 0) return;
   for (int k = threadIdx.x; k < K; k += 256) {
     int s, len, sj, lj, r = 0;
-    icp_segment(seg, k, N, s, len);
+    nn_segment(seg, k, N, s, len);
     for (int j = 0; j < k && !r; ++j) {
-      icp_segment(seg, j, N, sj, lj);
+      nn_segment(seg, j, N, sj, lj);
       r = sj == s && lj == len;
     }
     repeat[k] = r;
@@ -53,13 +53,11 @@ __global__ __launch_bounds__(256) void normals_items_kernel(const int32_t* __res
   int n = 0;
   for (int k = 0; k < K; ++k) {
     int s, len;
-    icp_segment(seg, k, N, s, len);
+    nn_segment(seg, k, N, s, len);
     if (repeat[k]) continue;
-    const int want = (len + NRM_TILE - 1) / NRM_TILE;
-    if (len > 0 && want <= max_items - n)             // overlapping segments can ask for more items than the list holds: left out whole
-      for (int q0 = 0; q0 < len; q0 += NRM_TILE) { NnWork w = {s, len, q0, s, len, k, 0, 0}; items[n++] = w; }
+    nn_emit_items_whole(items, n, max_items, s, len, s, len, k);
   }
-  for (; n < max_items; ++n) { NnWork w = {0, 0, 0, 0, 0, 0, 0, 0}; items[n] = w; }
+  nn_zero_items(items, n, max_items);
 }
 
 __host__ __device__ inline int normals_slots(int max_nn) { return (max_nn + 3) & ~3; }
@@ -85,15 +83,7 @@ __global__ __launch_bounds__(NRM_TILE) void normals_kernel(const NormalsParams a
   unsigned long long worst = 0ull;                                   // the largest key of a full list
   float limit = active ? a.r2_limit : -1.f;                          // an inactive lane admits nothing
   for (int k0 = 0; k0 < w.y_len; k0 += NRM_TILE) {
-    const int k = k0 + lane;
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (k < w.y_len) {
-      const size_t ki = (size_t)w.y_start + k;
-      c.x = a.P[ki * 3 + 0]; c.y = a.P[ki * 3 + 1]; c.z = a.P[ki * 3 + 2];
-    }
-    __syncthreads();
-    tile[lane] = c;
-    __syncthreads();
+    nn_tile_stage(tile, k0, w.y_len, make_float4(0.f, 0.f, 0.f, 0.f), [&](int k, float4& c) { nn_row(a.P, (size_t)w.y_start + k, c); });
     const int nk = min(NRM_TILE, w.y_len - k0);
 #pragma unroll 8
     for (int j = 0; j < nk; ++j) {

@@ -10,9 +10,9 @@
 // ds_read_b128 per candidate, broadcast to the whole wave); squared distances by direct differences in fp32 (more accurate
 // near the threshold than cdist's |a|^2 + |b|^2 - 2ab expansion), one v_min per pair, sqrt once per query.
 // HBM traffic: 16 B per point per query tile of its sample (L2-resident); VALU-bound at ~6 instructions per pair.
-#include "kernels.h"
+#include "nn_tile.h"
 
-#define OV_TILE 256
+#define OV_TILE NN_TILE
 struct OverlapWork { int seg_start, seg_len, q0, sample; };
 
 // one thread: work items (sample, 256-query tile); unused slots get seg_len = 0
@@ -46,23 +46,17 @@ __global__ __launch_bounds__(OV_TILE) void overlap_min_dist_kernel(const float* 
   const int qp = pid[qi];
   float best = __builtin_inff();
   for (int k0 = 0; k0 < w.seg_len; k0 += OV_TILE) {
-    const int k = k0 + threadIdx.x;
-    float4 c;
-    if (k < w.seg_len) {
+    // a candidate carries its part id in .w
+    nn_tile_stage(tile, k0, w.seg_len, make_float4(0.f, 0.f, 0.f, __int_as_float(-1)), [&](int k, float4& c) {
       const size_t ki = (size_t)(w.seg_start + k);
-      c.x = pts[ki * 3 + 0]; c.y = pts[ki * 3 + 1]; c.z = pts[ki * 3 + 2]; c.w = __int_as_float(pid[ki]);
-    } else {
-      c.x = c.y = c.z = 0.f; c.w = __int_as_float(-1);                      // padding slots are never read (j < nk)
-    }
-    __syncthreads();
-    tile[threadIdx.x] = c;
-    __syncthreads();
+      nn_row(pts, ki, c);
+      c.w = __int_as_float(pid[ki]);
+    });
     const int nk = min(OV_TILE, w.seg_len - k0);
 #pragma unroll 8
     for (int j = 0; j < nk; ++j) {
       const float4 p = tile[j];
-      const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-      const float d2 = dx * dx + dy * dy + dz * dz;
+      const float d2 = nn_d2(qx, qy, qz, p.x, p.y, p.z);
       best = (__float_as_int(p.w) != qp) ? fminf(best, d2) : best;           // other parts only (metrics.py:673-676)
     }
   }

@@ -4,7 +4,7 @@
 // Here: three launches for the whole batch, no host read, nothing of size N x M and no per-point array in HBM.
 //
 //   pair_worklist_kernel   points_per_part / cu -> items of 256 source points of one pair + the item range of every pair
-//   pair_query_kernel      nn_query_kernel's search (target tile through LDS, one ds_read_b128 broadcast per candidate, strict < so the
+//   pair_query_kernel      the tiled search (nn_tile.h: target tile through LDS, one ds_read_b128 broadcast per candidate, strict < so the
 //                          first arg-min wins) on clouds scaled to metres when they are LOADED, with the epilogue fused: the lane that
 //                          found nn(i) forms |src_i - tgt_nn(i)|^2 of the compared clouds and the block reduces {sum (double), count}
 //                          into one partial per item
@@ -15,9 +15,9 @@
 //   * round before you subtract -- the reference scales the clouds in fp32 and THEN measures distances; x * s - y would be contracted
 //     into one fma, a different number.  Every scaled coordinate is formed by mul_rn_nofuse, so d^2 is the direct-difference fp32 value
 //     of the rounded coordinates, exactly what nn_query_kernel computes on a cloud torch scaled beforehand.
-#include "kernels.h"
+#include "nn_tile.h"
 
-#define PM_TILE 256
+#define PM_TILE NN_TILE
 
 struct PairPartial { double sum; long long count; };
 struct PairRange { int first, count, n_source, n_target; };
@@ -34,14 +34,13 @@ __global__ void pair_worklist_kernel(const int64_t* __restrict__ ppp, const int3
     n0 = n0 < 0 ? 0 : n0 > TP - start ? TP - start : n0;
     n1 = n1 < 0 ? 0 : n1 > TP - start - n0 ? TP - start - n0 : n1;
     PairRange r = {n, 0, (int)n0, (int)n1};
-    if (n0 > 0 && n1 > 0)
-      for (long q0 = 0; q0 < n0 && n < max_items; q0 += PM_TILE) {
-        NnWork w = {(int)start, (int)n0, (int)q0, (int)(start + n0), (int)n1, b, 0, 0};
-        items[n++] = w; ++r.count;
-      }
+    if (n0 > 0 && n1 > 0) {
+      n = nn_emit_items(items, n, max_items, start, n0, start + n0, n1, b, 0);
+      r.count = n - r.first;
+    }
     ranges[b] = r;
   }
-  for (; n < max_items; ++n) { NnWork w = {0, 0, 0, 0, 0, 0, 0, 0}; items[n] = w; }
+  nn_zero_items(items, n, max_items);
 }
 
 __device__ __forceinline__ void pm_load_scaled(const float* __restrict__ P, size_t i, float s, float& x, float& y, float& z) {
@@ -77,24 +76,8 @@ __global__ __launch_bounds__(PM_TILE) void pair_query_kernel(const float* __rest
   const size_t qi = (size_t)w.x_start + (active ? q : w.x_len - 1);
   float qx, qy, qz;
   pm_load_scaled(gt, qi, s, qx, qy, qz);
-  float best = __builtin_inff();
-  int besti = -1;
-  for (int k0 = 0; k0 < w.y_len; k0 += PM_TILE) {
-    const int k = k0 + threadIdx.x;
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (k < w.y_len) pm_load_scaled(gt, (size_t)w.y_start + k, s, c.x, c.y, c.z);      // stored to LDS already in metres
-    __syncthreads();
-    tile[threadIdx.x] = c;
-    __syncthreads();
-    const int nk = min(PM_TILE, w.y_len - k0);
-#pragma unroll 8
-    for (int j = 0; j < nk; ++j) {
-      const float4 p = tile[j];
-      const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
-      const float d2 = dx * dx + dy * dy + dz * dz;
-      if (d2 < best) { best = d2; besti = k0 + j; }      // strict <: the first minimum wins, as torch.min
-    }
-  }
+  // the candidates are stored to LDS already in metres
+  NN_TILE_ARGMIN(tile, w.y_len, qx, qy, qz, [&](int k, float4& c) { pm_load_scaled(gt, (size_t)w.y_start + k, s, c.x, c.y, c.z); }, best, besti);
   double se = 0.0;
   int n = 0;
   if (active && besti >= 0 && sqrtf(best) <= thr) {        // the form correspondence_finish_kernel uses

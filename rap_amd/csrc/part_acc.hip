@@ -8,7 +8,7 @@
 //
 // One sync-free call for the whole batch.  Two small kernels lay out a clamped (start, len) table of the part slots and the work list;
 // then:
-//   1. part_nn_kernel: the N^2 work, shaped as nn_query_kernel (nn_metrics.hip).  A block owns up to 256 queries of ONE part (one per
+//   1. part_nn_kernel: the N^2 work, on nn_tile.h's tile.  A block owns up to 256 queries of ONE part (one per
 //      lane, in registers) and streams ALL points of the other cloud of the same sample through LDS once, in tiles of 256 float4 (one
 //      ds_read_b128 per candidate, broadcast to the wave); the running minimum is closed -- stored and reset -- at every candidate-part
 //      boundary, wherever in a tile it falls.  Result: d2[j][x] = min over part j of the other cloud, for every point x and part slot j
@@ -20,9 +20,9 @@
 //      scan as a reduction (RapLsapPick).
 // No floating-point atomics anywhere: two runs give the same bits.
 #include "assign.h"
-#include "icp.h"
+#include "nn_tile.h"
 
-#define PA_TILE 256
+#define PA_TILE NN_TILE
 #define PA_MAX_GRID 1024      // blocks per direction; a block walks the work list with this stride
 
 // seg[(b * P + p)] = (start, len) of part p of sample b, clamped: the sample's span is [cu[b], cu[b+1]) inside [0, TP], the parts follow
@@ -52,13 +52,13 @@ __global__ void part_acc_worklist_kernel(const int32_t* __restrict__ seg, int B,
   int n = 0;
   for (int b = 0; b < B; ++b) {
     int s0, l0, s1, l1;
-    icp_segment(seg, b * P, TP, s0, l0);
-    icp_segment(seg, b * P + P - 1, TP, s1, l1);
+    nn_segment(seg, b * P, TP, s0, l0);
+    nn_segment(seg, b * P + P - 1, TP, s1, l1);
     const int y_len = s1 + l1 - s0;
     for (int p = 0; p < P; ++p) {
       int s, l;
-      icp_segment(seg, b * P + p, TP, s, l);
-      for (int q0 = 0; q0 < l && n < max_items; q0 += PA_TILE) { NnWork w = {s, l, q0, s0, y_len, b, p, 0}; items[n++] = w; }
+      nn_segment(seg, b * P + p, TP, s, l);
+      n = nn_emit_items(items, n, max_items, s, l, s0, y_len, b, p);
     }
   }
   *count = n;
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(PA_TILE) void part_nn_kernel(const float* __restric
     __syncthreads();                          // the previous item's readers of pend / tile are done
     if ((int)threadIdx.x < P) {
       int s, l;
-      icp_segment(seg, w.pad0 * P + threadIdx.x, TP, s, l);
+      nn_segment(seg, w.pad0 * P + threadIdx.x, TP, s, l);
       pend[threadIdx.x] = s + l - w.y_start;
     }
     const int q = w.q0 + threadIdx.x;
@@ -92,15 +92,7 @@ __global__ __launch_bounds__(PA_TILE) void part_nn_kernel(const float* __restric
     while (cj < P && pend[cj] <= (cj ? pend[cj - 1] : 0)) ++cj;
     float best = __builtin_inff();
     for (int k0 = 0; k0 < w.y_len && cj < P; k0 += PA_TILE) {
-      const int k = k0 + threadIdx.x;
-      float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (k < w.y_len) {
-        const size_t ki = (size_t)w.y_start + k;
-        c.x = Y[ki * 3 + 0]; c.y = Y[ki * 3 + 1]; c.z = Y[ki * 3 + 2];
-      }
-      __syncthreads();
-      tile[threadIdx.x] = c;
-      __syncthreads();
+      nn_tile_stage(tile, k0, w.y_len, make_float4(0.f, 0.f, 0.f, 0.f), [&](int k, float4& c) { nn_row(Y, (size_t)w.y_start + k, c); });
       const int nk = min(PA_TILE, w.y_len - k0);
       int j = 0;
       while (j < nk && cj < P) {
@@ -130,10 +122,10 @@ __global__ __launch_bounds__(256) void part_cd_kernel(const float* __restrict__ 
   const int row = blockIdx.x, i = row % P, b = row / P;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   int si, li;
-  icp_segment(seg, row, TP, si, li);
+  nn_segment(seg, row, TP, si, li);
   for (int j = wave; j < P; j += 4) {
     int sj, lj;
-    icp_segment(seg, b * P + j, TP, sj, lj);
+    nn_segment(seg, b * P + j, TP, sj, lj);
     float cd = __builtin_nanf("");
     if (li > 0 && lj > 0) {
       const float* __restrict__ pa = d2a + (size_t)j * TP + si;      // gt_i -> pred_j
@@ -193,7 +185,7 @@ __global__ __launch_bounds__(256) void part_assign_kernel(const int32_t* __restr
     int n = 0;
     for (int p = 0; p < P; ++p) {
       int s, l;
-      icp_segment(seg, b * P + p, TP, s, l);
+      nn_segment(seg, b * P + p, TP, s, l);
       if (l > 0) slot[n++] = p;
     }
     st_n = n;
