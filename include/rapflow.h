@@ -39,7 +39,10 @@ extern "C" {
  * rap_icp_plane_workspace_bytes, rap_icp_plane, rap_icp_plane_grid_workspace_bytes and rap_icp_plane_grid (point-to-plane ICP and the
  * normals it needs); rap_deskew, rap_fuse_frames, rap_submap_overlap with their *_workspace_bytes queries and
  * rap_submap_groups_connected (sweeps and poses -> submaps, their overlap matrix and the connectivity of candidate groups);
- * rap_part_acc_workspace_bytes and rap_part_acc (part accuracy and the part matching that matched_part_ids arguments take). */
+ * rap_part_acc_workspace_bytes and rap_part_acc (part accuracy and the part matching that matched_part_ids arguments take);
+ * rap_knn_workspace_bytes, rap_k_nearest_neighbors, rap_normals_grid_workspace_bytes, rap_estimate_normals_grid,
+ * rap_outlier_grid_workspace_bytes and rap_statistical_outliers_grid (the k nearest rows over the uniform-grid index, and the normal
+ * estimation and the outlier removal on it). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -336,6 +339,21 @@ size_t rap_nn_grid_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32
 int rap_nearest_neighbors(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t n_x_points,
                           int64_t n_y_points, const float* R, const float* T, float max_distance, int32_t* idx_out, float* d2_out, void* ws,
                           size_t ws_bytes, void* stream);
+/* The k nearest rows over the same index, exact.  For every row i of problem k's x segment: the count_out[i] <= k admissible rows of
+ * Y within k's y segment with the smallest (d2, row), in ascending order of (d2, row) -- idx_out[i * k + s] = the row of Y (an index
+ * into Y, not into the segment), d2_out[i * k + s] = its squared distance (fp32, direct differences: the distance of
+ * rap_nearest_neighbors), s < count_out[i]; the unused slots hold -1 and inf.  A row of Y is admissible when d2 is finite and
+ * sqrtf(d2) <= max_distance (max_distance <= 0: no limit); rows of Y with a non-finite coordinate never are, and an x_i with a
+ * non-finite coordinate admits none (count 0).  k in 1 .. 32.  idx_out, d2_out are (n_x_points, k), count_out (n_x_points,); rows of X
+ * outside every segment are not written.  With k = 1, idx_out and d2_out are what rap_nearest_neighbors returns with R = T = NULL, bit
+ * for bit.  The list is put into its order before it is written, so the result is the same from call to call whatever order the index
+ * was built in.  Segment tables, their clamping, the x segments that must not overlap, shared and overlapping y segments, K <= 65535 and
+ * the execution properties: as rap_nearest_neighbors.  ws >= rap_knn_workspace_bytes(n_x_points, n_y_points, K) (host arithmetic, 0 for
+ * non-positive arguments: the terms of rap_nn_grid_workspace_bytes). */
+size_t rap_knn_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K);
+int rap_k_nearest_neighbors(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t n_x_points,
+                            int64_t n_y_points, int32_t k, float max_distance, int32_t* idx_out, float* d2_out, int32_t* count_out,
+                            void* ws, size_t ws_bytes, void* stream);
 
 /* Surface normals of packed clouds: the plane fit of every point's neighbourhood, Open3D's estimate_normals with a hybrid search as the
  * reference calls it (dataset_process/utils/dataset_utils.py:325-358: radius 0.5, max_nn 20).  P (n_points,3) fp32; seg (K,2) int32
@@ -349,12 +367,27 @@ int rap_nearest_neighbors(const float* X, const int32_t* x_seg, const float* Y, 
  * component of largest magnitude is positive (the lowest index among equals).  Fewer than three neighbours, or a non-finite p_i:
  * normal (0,0,0) and eigenvalues 0 -- a stated departure from Open3D's (0,0,1): rap_icp_plane skips a zero normal, it cannot skip a
  * made-up one.  normals (n_points,3); eigenvalues (n_points,3) ascending, or NULL; rows outside every segment are not written.
- * Brute-force search, O(len^2) per segment: meant for voxel-downsampled clouds.  Two launches, no host read, no atomics,
+ * Brute-force search, O(len^2) per segment: for voxel-downsampled clouds; rap_estimate_normals_grid below is the same estimate from
+ * the grid index, for clouds at full resolution.  Two launches, no host read, no atomics,
  * deterministic, a row's bits depend on its own segment only; can be captured into a graph.
  * ws >= rap_normals_workspace_bytes(n_points, K) (host arithmetic; 0 for non-positive arguments). */
 size_t rap_normals_workspace_bytes(int64_t n_points, int32_t K);
 int rap_estimate_normals(const float* P, const int32_t* seg, int32_t K, int64_t n_points, int32_t max_nn, float radius,
                          const float* viewpoint, float* normals, float* eigenvalues, void* ws, size_t ws_bytes, void* stream);
+/* rap_estimate_normals on the uniform-grid index: its argument list and its semantics word for word -- the neighbourhood rule, the fp64
+ * mean and covariance, the eigenvector, both orientation rules, the zero normal below three neighbours, repeated segments worked once,
+ * rows outside every segment not written.  The neighbour SETS are those of rap_estimate_normals (the k-best walk of
+ * rap_k_nearest_neighbors over each segment's own rows is exact).  Mean and covariance are summed over the neighbours in ascending
+ * (d2, j); rap_estimate_normals sums in the order its list filled, so the two may differ in the last bits of the fp64 sums, and
+ * both are within 2e-6 of an fp64 plane fit; bit equality between them is not promised.  O(len) work per segment in place of O(len^2).
+ * Segments that overlap without being equal stay the caller's responsibility.  K <= 65535.  The index is built once per call on the
+ * device; no host read, no allocation, no floating-point atomics, deterministic (the same bits from call to call, and for a segment
+ * whatever else is in the batch); can be captured into a graph.
+ * ws >= rap_normals_grid_workspace_bytes(n_points, K) (host arithmetic, 0 for non-positive arguments: rap_normals_workspace_bytes plus
+ * about 28 bytes per point for the index). */
+size_t rap_normals_grid_workspace_bytes(int64_t n_points, int32_t K);
+int rap_estimate_normals_grid(const float* P, const int32_t* seg, int32_t K, int64_t n_points, int32_t max_nn, float radius,
+                              const float* viewpoint, float* normals, float* eigenvalues, void* ws, size_t ws_bytes, void* stream);
 
 /* Submaps (submaps.hip): the stage of the reference's data preparation before the "views" exist
  * (dataset_process/utils/processing_utils.py:1927-2090).  Common to the four calls below:
@@ -766,6 +799,15 @@ int rap_collate_transform(const void* points, int32_t points_are_f64, const int6
 size_t rap_outlier_workspace_bytes(int64_t N);
 int rap_statistical_outliers(const float* points, int64_t N, int32_t nb_neighbors, double std_ratio, int64_t* inlier_indices,
                              int32_t* count_out, double* stats_out, void* ws, size_t ws_bytes, void* stream);
+/* rap_statistical_outliers with its neighbour search on the uniform-grid index: the same argument list and the same rule.  Only the
+ * first of its five kernels differs: the mean of sqrtf(d2) over the nb_neighbors smallest d2 of every point (itself included; -1
+ * where there is none) comes from the k-best walk of rap_k_nearest_neighbors, summed in double in ascending order as the brute-force
+ * kernel sums it; statistics, count, scan and emit are the same kernels.  O(N) work in place of N^2 pair distances: for raw scans.
+ * The index is built once per call on the device; no host synchronisation, deterministic.
+ * ws >= rap_outlier_grid_workspace_bytes(N) (host arithmetic, 0 for N <= 0: rap_outlier_workspace_bytes plus about 28 bytes per point). */
+size_t rap_outlier_grid_workspace_bytes(int64_t N);
+int rap_statistical_outliers_grid(const float* points, int64_t N, int32_t nb_neighbors, double std_ratio, int64_t* inlier_indices,
+                                  int32_t* count_out, double* stats_out, void* ws, size_t ws_bytes, void* stream);
 
 /* Consistency of a packed batch -- what the reference asserts in split_parts (utils/point_clouds.py:33-52).  rap_sample and the
  * Procrustes entry points REQUIRE sum(points_per_part) == TP and, per sample, sum_p points_per_part[b][p] == cu_seqlens[b+1] -

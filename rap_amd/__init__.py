@@ -8,7 +8,8 @@ from .data import transform_and_collate
 from .evaluator import Evaluator
 from .flow_model import PointCloudDiT
 from .normals import estimate_normals_packed, estimate_point_normals
-from .icp import ICPSolution, align_anchor, compute_transform_errors_icp, icp_packed, iterative_closest_point, nearest_neighbors_packed
+from .icp import (ICPSolution, align_anchor, compute_transform_errors_icp, icp_packed, iterative_closest_point, k_nearest_neighbors_packed,
+                  nearest_neighbors_packed)
 from .metrics import compute_part_acc
 from .modeling import RectifiedPointFlow
 from .procrustes import fit_transformations, rigidify_prediction_with_procrustes, solve_procrustes
@@ -22,7 +23,7 @@ __all__ = ["PointCloudDiT", "RectifiedPointFlow", "fit_transformations", "rigidi
            "solve_procrustes", "euler_step", "flow_sampler", "get_sampler", "compute_rigidity_rmse",
            "average_trajectory_rigidity_rmse", "select_generations_by_rigidity", "compute_overlap_ratio",
            "select_generations_by_overlap", "transform_and_collate", "Evaluator", "iterative_closest_point", "icp_packed", "ICPSolution",
-           "align_anchor", "compute_transform_errors_icp", "compute_part_acc", "nearest_neighbors_packed",
+           "align_anchor", "compute_transform_errors_icp", "compute_part_acc", "nearest_neighbors_packed", "k_nearest_neighbors_packed",
            "estimate_normals_packed", "estimate_point_normals", "deskew_packed", "fuse_frames_packed", "submap_overlap_matrix",
            "groups_connected", "deskewing", "create_submap_from_frames", "calculate_point_cloud_overlap_ratio_fast",
            "check_submap_validity"]

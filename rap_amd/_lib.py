@@ -82,8 +82,12 @@ SIGNATURES = {
                                c_size_t, _P]),
     "rap_nn_grid_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
     "rap_nearest_neighbors": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, c_float, _P, _P, _P, c_size_t, _P]),
+    "rap_knn_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "rap_k_nearest_neighbors": (c_int32, [_P, _P, _P, _P, c_int32, c_int64, c_int64, c_int32, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "rap_normals_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_estimate_normals": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_float, _P, _P, _P, _P, c_size_t, _P]),
+    "rap_normals_grid_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "rap_estimate_normals_grid": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "rap_deskew_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_deskew": (c_int32, [_P, _P, _P, c_int32, c_int64, _P, c_float, _P, _P, _P, c_size_t, _P]),
     "rap_fuse_frames_workspace_bytes": (c_size_t, [c_int64, c_int32]),
@@ -114,6 +118,8 @@ SIGNATURES = {
     "rap_spinnet_describe": (c_int32, [_P, _P, _P, c_int64, _P, c_int32, c_float, c_int32, _P, c_int32, _P, c_size_t, _P]),
     "rap_outlier_workspace_bytes": (c_size_t, [c_int64]),
     "rap_statistical_outliers": (c_int32, [_P, c_int64, c_int32, ctypes.c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "rap_outlier_grid_workspace_bytes": (c_size_t, [c_int64]),
+    "rap_statistical_outliers_grid": (c_int32, [_P, c_int64, c_int32, ctypes.c_double, _P, _P, _P, _P, c_size_t, _P]),
     "rap_check_batch": (c_int32, [_P, _P, c_int32, c_int32, c_int64, _P, _P]),
     "rap_poison_on_flag": (c_int32, [_P, _P, c_int64, _P]),
     "rap_collate_workspace_bytes": (c_size_t, [c_int32, c_int32]),

@@ -862,6 +862,48 @@ extern "C" int rap_estimate_normals(const float* P, const int32_t* seg, int32_t 
   return launch_estimate_normals((hipStream_t)stream, P, seg, K, (long)n_points, max_nn, radius, viewpoint, normals, eigenvalues, items, repeat);
 }
 
+// the k-best walk over the same index (nn_knn.hip): the k nearest rows, and the grid paths of the normal estimation and (further down)
+// of the outlier removal.  Each workspace is the brute-force or 1-NN call's own terms followed by the index
+extern "C" size_t rap_knn_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
+  return rap_nn_grid_workspace_bytes(n_x_points, n_y_points, K);
+}
+extern "C" int rap_k_nearest_neighbors(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int32_t K, int64_t NX,
+                                       int64_t NY, int32_t k, float max_distance, int32_t* idx_out, float* d2_out, int32_t* count_out,
+                                       void* ws, size_t ws_bytes, void* stream) {
+  if (!X || !x_seg || !Y || !y_seg || !idx_out || !d2_out || !count_out || K <= 0 || K > RAP_GRID_MAX_K || NX <= 0 || NY <= 0 ||
+      NX > 0x7fffffffLL / 8 || NY > 0x7fffffffLL / 8 || k < 1 || k > 32 || max_distance != max_distance)
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  Carver c(ws);
+  NnWork* items = (NnWork*)c.take(nn_max_items((long)NX, K) * sizeof(NnWork));
+  const NnGridWs g = nn_grid_carve(c, (long)NY, K);
+  if (c.total() > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_k_nearest_neighbors((hipStream_t)stream, X, x_seg, Y, y_seg, K, (long)NX, (long)NY, k, max_distance, idx_out, d2_out,
+                                    count_out, items, g);
+}
+
+extern "C" size_t rap_normals_grid_workspace_bytes(int64_t n_points, int32_t K) {
+  if (n_points <= 0 || K <= 0) return 0;
+  Carver c(nullptr);
+  nn_grid_carve(c, (long)n_points, K);
+  return rap_normals_workspace_bytes(n_points, K) + c.total();
+}
+extern "C" int rap_estimate_normals_grid(const float* P, const int32_t* seg, int32_t K, int64_t n_points, int32_t max_nn, float radius,
+                                         const float* viewpoint, float* normals, float* eigenvalues, void* ws, size_t ws_bytes,
+                                         void* stream) {
+  if (!P || !seg || !normals || K <= 0 || K > RAP_GRID_MAX_K || n_points <= 0 || n_points > 0x7fffffffLL / 8 || max_nn < 3 || max_nn > 32 ||
+      radius != radius)
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  Carver c(ws);
+  NnWork* items = (NnWork*)c.take(nn_max_items((long)n_points, K) * sizeof(NnWork));
+  int32_t* repeat = (int32_t*)c.take((size_t)K * 4);
+  const NnGridWs g = nn_grid_carve(c, (long)n_points, K);
+  if (c.total() > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_estimate_normals_grid((hipStream_t)stream, P, seg, K, (long)n_points, max_nn, radius, viewpoint, normals, eigenvalues, items,
+                                      repeat, g);
+}
+
 extern "C" int rap_farthest_point_sampling(const float* points, const int32_t* cloud_start, const int32_t* cloud_len,
                                            const int32_t* k_per_cloud, const int32_t* start_idx, int32_t n_clouds, int32_t k_max,
                                            int32_t* indices_out, float* dist_ws, void* stream) {
@@ -989,6 +1031,32 @@ extern "C" int rap_statistical_outliers(const float* points, int64_t N, int32_t 
     return RAP_ERR_INVALID;
   if (!ws || ws_bytes < outlier_workspace_bytes((long)N)) return RAP_ERR_WORKSPACE;
   return launch_statistical_outliers((hipStream_t)stream, points, (long)N, nb_neighbors, std_ratio, inlier_indices, count_out, stats_out, ws);
+}
+
+// ... with the mean neighbour distances from the k-best walk over the grid index (nn_knn.hip): the brute-force call's workspace, then the
+// cloud's one segment, the work items and the index
+struct OutlierGridWs { int32_t* seg; NnWork* items; NnGridWs g; size_t total; };
+static OutlierGridWs carve_outlier_grid(int64_t N, char* base) {
+  OutlierGridWs w;
+  Carver c(base);
+  c.take(outlier_workspace_bytes((long)N));
+  w.seg = (int32_t*)c.take(2 * sizeof(int32_t));
+  w.items = (NnWork*)c.take(nn_max_items((long)N, 1) * sizeof(NnWork));
+  w.g = nn_grid_carve(c, (long)N, 1);
+  w.total = c.total();
+  return w;
+}
+extern "C" size_t rap_outlier_grid_workspace_bytes(int64_t N) { return N <= 0 ? 0 : carve_outlier_grid(N, nullptr).total; }
+
+extern "C" int rap_statistical_outliers_grid(const float* points, int64_t N, int32_t nb_neighbors, double std_ratio, int64_t* inlier_indices,
+                                             int32_t* count_out, double* stats_out, void* ws, size_t ws_bytes, void* stream) {
+  if (!points || !inlier_indices || !count_out || N <= 0 || N > 0x7fffffffLL / 8 || nb_neighbors < 1 || nb_neighbors > 32 || !(std_ratio > 0.0))
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  const OutlierGridWs w = carve_outlier_grid(N, (char*)ws);
+  if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_statistical_outliers_grid((hipStream_t)stream, points, (long)N, nb_neighbors, std_ratio, inlier_indices, count_out, stats_out,
+                                          ws, w.seg, w.items, w.g);
 }
 
 // QKV projection with MultiHeadRMSNorm fused into the epilogue (EPI_H_QKV_NORM): see rapflow.h

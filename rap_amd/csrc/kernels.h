@@ -304,9 +304,21 @@ struct NnGridWs {
 };
 NnGridWs nn_grid_carve(Carver& c, long NY, int K);
 int launch_nn_grid_build(hipStream_t stream, const float* Y, const int32_t* y_seg, int K, long NY, const NnGridWs& g);
+// items of NN_TILE queries of one problem, all of a problem or none: nn_max_items(NX, K) NnWork
+int launch_nn_grid_items(hipStream_t stream, const int32_t* x_seg, const int32_t* y_seg, int K, long NX, long NY, NnWork* items);
 int launch_nearest_neighbors(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX,
                              long NY, const float* R, const float* T, float gate, int32_t* idx_out, float* d2_out, NnWork* items,
                              const NnGridWs& g);
+// the k-best walk over the same index (nn_knn.hip): the k nearest rows as an entry point of its own, and the grid paths of the normal
+// estimation and of the outlier removal's kernel 1.  Each builds the index itself.  items: nn_max_items(NX, K) NnWork; repeat: 4 bytes
+// per segment; seg: 2 ints, the one segment of the outlier cloud (written on the device)
+int launch_k_nearest_neighbors(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX,
+                               long NY, int k, float radius, int32_t* idx_out, float* d2_out, int32_t* count_out, NnWork* items,
+                               const NnGridWs& g);
+int launch_estimate_normals_grid(hipStream_t stream, const float* P, const int32_t* seg, int K, long N, int max_nn, float radius,
+                                 const float* viewpoint, float* normals, float* eigenvalues, NnWork* items, int32_t* repeat, const NnGridWs& g);
+int launch_knn_mean_dist_grid(hipStream_t stream, const float* pts, long N, int k, double* mean_dist, int32_t* seg, NnWork* items,
+                              const NnGridWs& g);
 
 // batched ICP (icp.hip; pytorch3d's iterative_closest_point as reference eval/metrics.py:79, 261 call it): one call of K problems.
 // Y_normals chooses the estimator (null: point-to-point; else point-to-plane, icp_plane.hip), grid the search (null: tiled brute
@@ -336,6 +348,8 @@ int launch_icp_plane_finish(hipStream_t stream, const IcpCall& c, int it);
 // dataset_process/utils/dataset_utils.py:325-358 calls it).  items: nn_max_items(N, K) NnWork; repeat: 4 bytes per segment
 int launch_estimate_normals(hipStream_t stream, const float* P, const int32_t* seg, int K, long N, int max_nn, float radius,
                             const float* viewpoint, float* normals, float* eigenvalues, NnWork* items, int32_t* repeat);
+// its work list alone (the grid path starts from the same one): a segment that repeats an earlier one gets no items
+int launch_normals_items(hipStream_t stream, const int32_t* seg, int K, long N, NnWork* items, int32_t* repeat);
 
 // farthest point sampling (fps.hip; reference dataset_process/utils/point_sampling_utils.py:263-305)
 int launch_fps(hipStream_t stream, const float* pts, const int32_t* cloud_start, const int32_t* cloud_len, const int32_t* Ks,
@@ -360,6 +374,10 @@ int launch_collate_transform(hipStream_t stream, const void* pts, int f64, const
 size_t outlier_workspace_bytes(long N);
 int launch_statistical_outliers(hipStream_t stream, const float* pts, long N, int nb_neighbors, double std_ratio, int64_t* idx_out,
                                 int32_t* count_out, double* stats_out, void* ws);
+// the same call with kernel 1 (the mean neighbour distances) on the grid index (nn_knn.hip); ws: outlier_workspace_bytes(N), laid out as above;
+// seg, items, g: as launch_knn_mean_dist_grid
+int launch_statistical_outliers_grid(hipStream_t stream, const float* pts, long N, int nb_neighbors, double std_ratio, int64_t* idx_out,
+                                     int32_t* count_out, double* stats_out, void* ws, int32_t* seg, NnWork* items, const NnGridWs& g);
 int launch_voxel_coverage(hipStream_t stream, const float* pts, long N, float vs, const long long* h_bounds6, unsigned char* table, long slots,
                           unsigned long long* total);
 // voxel_sort.hip: the same two results from a radix sort, O(N) memory (for grids whose dense table would be large against N)

@@ -31,24 +31,13 @@
 // subtraction together are off by less than 2^-11).  The bound itself is then at most eight roundings away from exact and `best` six from the
 // exact distance: 14 * 2^-24 < 2^-20 relative; the bound is scaled by 1 - 2^-16 (GRID_MARGIN), sixteen times that.  A smaller bound only
 // costs another shell.  The comparison is strict, so a tied candidate with a lower index in an unvisited cell cannot be missed either.
+// The k-best walk over the same index (the k nearest rows, normals, outlier removal) is nn_knn.hip; nn_grid.h holds what the two share.
 #include "icp.h"
+#include "nn_grid.h"
 
 #define GRID_MAX_DIM 1024
-#define GRID_SLACK 0.0009765625f          // 2^-10 cells
-#define GRID_MARGIN 0.9999847412109375f   // 1 - 2^-16
-#define GRID_GATE_MARGIN 1.0000152587890625f   // 1 + 2^-16: d2 > gate^2 (1 + 2^-16) implies sqrtf(d2) > gate after rounding
 #define GRID_SCAN_CHUNK 2048
 #define GRID_BUILD_BLOCKS 128
-
-enum { GRID_NONE = 0, GRID_CELLS = 1, GRID_ROWS = 2 };      // empty y segment; indexed; searched row by row (no budget left)
-
-struct NnGrid {                     // 64 bytes per problem
-  float lo[3], h;
-  float hi[3];
-  int row_base;                     // first entry of this grid's rows in row_cell
-  int dims[3], cell_base;           // first cell of this grid in the tables of the call
-  int y_start, y_len, owner, mode;  // owner: the problem whose build kernels fill this grid (itself, or an earlier one with the same rows)
-};
 
 NnGridWs nn_grid_carve(Carver& c, long NY, int K) {
   NnGridWs w;
@@ -69,13 +58,6 @@ __device__ __forceinline__ unsigned grid_key(float v) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float grid_unkey(unsigned k) { return __builtin_bit_cast(float, k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
-__device__ __forceinline__ bool grid_finite(float x, float y, float z) {
-  const float inf = __builtin_inff();
-  return fabsf(x) < inf && fabsf(y) < inf && fabsf(z) < inf;
-}
-// position in cells along one axis, and the cell it falls into: the ONE definition the build and the query share
-__device__ __forceinline__ float grid_t(float p, float lo, float h) { return (p - lo) / h; }
-__device__ __forceinline__ int grid_cell(float t, int dim) { return (int)fminf(fmaxf(floorf(t), 0.f), (float)(dim - 1)); }
 
 __global__ __launch_bounds__(256) void nn_grid_plan_kernel(const int32_t* __restrict__ y_seg, int K, long NY, NnGrid* __restrict__ grids,
                                                            unsigned* __restrict__ box) {
@@ -363,8 +345,6 @@ __device__ __forceinline__ void grid_search(const NnGrid& g, const float* __rest
   }
 }
 
-__device__ __forceinline__ float grid_gate2(float gate) { return gate > 0.f ? gate * gate * GRID_GATE_MARGIN : __builtin_inff(); }
-
 // the two ICP query kernels with the grid search in place of the tiled one: same items, same head, same epilogue
 __global__ __launch_bounds__(ICP_TILE) void icp_grid_query_kernel(const float* __restrict__ X, const float* __restrict__ Y,
                                                                   const NnWork* __restrict__ items, const float* __restrict__ R,
@@ -471,13 +451,19 @@ int launch_icp_grid_query(hipStream_t stream, const IcpCall& c) {
   return RAP_OK;
 }
 
+int launch_nn_grid_items(hipStream_t stream, const int32_t* x_seg, const int32_t* y_seg, int K, long NX, long NY, NnWork* items) {
+  hipLaunchKernelGGL(nn_grid_items_kernel, dim3(1), dim3(64), 0, stream, x_seg, y_seg, K, NX, NY, items, (int)nn_max_items(NX, K));
+  RAP_LAUNCH_CHECK();
+  return RAP_OK;
+}
+
 int launch_nearest_neighbors(hipStream_t stream, const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, int K, long NX,
                              long NY, const float* R, const float* T, float gate, int32_t* idx_out, float* d2_out, NnWork* items,
                              const NnGridWs& g) {
   const int max_items = (int)nn_max_items(NX, K);
-  hipLaunchKernelGGL(nn_grid_items_kernel, dim3(1), dim3(64), 0, stream, x_seg, y_seg, K, NX, NY, items, max_items);
-  RAP_LAUNCH_CHECK();
-  const int rc = launch_nn_grid_build(stream, Y, y_seg, K, NY, g);
+  int rc = launch_nn_grid_items(stream, x_seg, y_seg, K, NX, NY, items);
+  if (rc) return rc;
+  rc = launch_nn_grid_build(stream, Y, y_seg, K, NY, g);
   if (rc) return rc;
   hipLaunchKernelGGL(nn_grid_query_kernel, dim3(max_items), dim3(ICP_TILE), 0, stream, X, Y, (const NnWork*)items, R, T, gate,
                      (const NnGrid*)g.grids, (const unsigned*)g.cell_start, (const float4*)g.sorted, idx_out, d2_out);

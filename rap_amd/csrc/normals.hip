@@ -16,8 +16,9 @@
 //                          of dependent LDS shifts per insertion, and a wave takes the branch when any of its 64 lanes does: about
 //                          k ln(n / k) insertions per lane are rare, 64 times that per wave are not; DESIGN.md section 7.3 has the
 //                          numbers).  The covariance pass re-reads the winners by index, in slot order.
-// No atomics, no host read, capturable; a row's bits depend on its own segment only.  There is no grid-index variant: clouds are
-// voxel-downsampled before this step.
+// No atomics, no host read, capturable; a row's bits depend on its own segment only.  The grid-index variant for clouds
+// that are not voxel-downsampled first (rap_estimate_normals_grid: the same neighbour sets from the k-best walk) is nn_knn.hip, DESIGN.md
+// section 7.6.
 #include "nn_tile.h"
 #include "kabsch.h"
 
@@ -153,11 +154,17 @@ __global__ __launch_bounds__(NRM_TILE) void normals_kernel(const NormalsParams a
   }
 }
 
+int launch_normals_items(hipStream_t stream, const int32_t* seg, int K, long N, NnWork* items, int32_t* repeat) {
+  hipLaunchKernelGGL(normals_items_kernel, dim3(1), dim3(256), 0, stream, seg, K, N, items, (int)nn_max_items(N, K), repeat);
+  RAP_LAUNCH_CHECK();
+  return RAP_OK;
+}
+
 int launch_estimate_normals(hipStream_t stream, const float* P, const int32_t* seg, int K, long N, int max_nn, float radius,
                             const float* viewpoint, float* normals, float* eigenvalues, NnWork* items, int32_t* repeat) {
   const int max_items = (int)nn_max_items(N, K);
-  hipLaunchKernelGGL(normals_items_kernel, dim3(1), dim3(256), 0, stream, seg, K, N, items, max_items, repeat);
-  RAP_LAUNCH_CHECK();
+  const int rc = launch_normals_items(stream, seg, K, N, items, repeat);
+  if (rc) return rc;
   NormalsParams a;
   a.P = P; a.items = items; a.viewpoint = viewpoint; a.normals = normals; a.eigenvalues = eigenvalues;
   a.radius = radius > 0.f ? radius : 0.f;

@@ -10,6 +10,8 @@
 // 1024 points (float4, 16 KB), each lane keeping its K smallest squared distances as a sorted register array that is updated with
 // a branch-free min/max ladder only when a candidate beats the current K-th (rare after the first tiles).  N^2 direct-difference
 // fp32 distances, no N x N matrix in HBM: MFMA is useless here (3-d points), the bound is VALU issue (8 ops per pair).
+// rap_statistical_outliers_grid replaces kernel 1 alone by the k-best walk over the uniform-grid index (nn_knn.hip, DESIGN.md section
+// 7.6): the same mean distances from O(N) work, for raw scans; kernels 2-5 below serve both.
 #include "kernels.h"
 
 #define OL_TILE 1024
@@ -144,16 +146,23 @@ size_t outlier_workspace_bytes(long N) {
   return align_up((size_t)N * 8, 256) + 256 + align_up((size_t)(nblk + 1) * 4, 256);
 }
 
-int launch_statistical_outliers(hipStream_t stream, const float* pts, long N, int nb_neighbors, double std_ratio, int64_t* idx_out,
-                                int32_t* count_out, double* stats_out, void* ws) {
+// kernel 1 by brute force, or (grid != null) on the uniform-grid index, which nn_knn.hip builds and walks; then the shared tail
+static int outliers(hipStream_t stream, const float* pts, long N, int nb_neighbors, double std_ratio, int64_t* idx_out, int32_t* count_out,
+                    double* stats_out, void* ws, int32_t* seg, NnWork* items, const NnGridWs* grid) {
   char* w = (char*)ws;
   double* md = (double*)w; w += align_up((size_t)N * 8, 256);
   double* stats = (double*)w; w += 256;
   unsigned int* block_cnt = (unsigned int*)w;
   const int n = (int)N;
-  const unsigned grid = (unsigned)((N + 255) / 256);
-  if (nb_neighbors <= 20) hipLaunchKernelGGL(knn_mean_dist_kernel<20>, dim3(grid), dim3(256), 0, stream, pts, n, nb_neighbors, md);
-  else hipLaunchKernelGGL(knn_mean_dist_kernel<32>, dim3(grid), dim3(256), 0, stream, pts, n, nb_neighbors, md);
+  const unsigned nblk256 = (unsigned)((N + 255) / 256);
+  if (grid) {
+    const int rc = launch_knn_mean_dist_grid(stream, pts, N, nb_neighbors, md, seg, items, *grid);
+    if (rc) return rc;
+  } else if (nb_neighbors <= 20) {
+    hipLaunchKernelGGL(knn_mean_dist_kernel<20>, dim3(nblk256), dim3(256), 0, stream, pts, n, nb_neighbors, md);
+  } else {
+    hipLaunchKernelGGL(knn_mean_dist_kernel<32>, dim3(nblk256), dim3(256), 0, stream, pts, n, nb_neighbors, md);
+  }
   RAP_LAUNCH_CHECK();
   hipLaunchKernelGGL(outlier_stats_kernel, dim3(1), dim3(1024), 0, stream, md, n, std_ratio, stats);
   RAP_LAUNCH_CHECK();
@@ -166,4 +175,13 @@ int launch_statistical_outliers(hipStream_t stream, const float* pts, long N, in
   RAP_LAUNCH_CHECK();
   if (stats_out) RAP_HIP_CHECK(hipMemcpyAsync(stats_out, stats, 3 * sizeof(double), hipMemcpyDeviceToDevice, stream));
   return RAP_OK;
+}
+
+int launch_statistical_outliers(hipStream_t stream, const float* pts, long N, int nb_neighbors, double std_ratio, int64_t* idx_out,
+                                int32_t* count_out, double* stats_out, void* ws) {
+  return outliers(stream, pts, N, nb_neighbors, std_ratio, idx_out, count_out, stats_out, ws, nullptr, nullptr, nullptr);
+}
+int launch_statistical_outliers_grid(hipStream_t stream, const float* pts, long N, int nb_neighbors, double std_ratio, int64_t* idx_out,
+                                     int32_t* count_out, double* stats_out, void* ws, int32_t* seg, NnWork* items, const NnGridWs& g) {
+  return outliers(stream, pts, N, nb_neighbors, std_ratio, idx_out, count_out, stats_out, ws, seg, items, &g);
 }

@@ -153,6 +153,45 @@ def nearest_neighbors_packed(X, x_seg, Y, y_seg, R=None, T=None, max_distance: f
     return idx, d2
 
 
+def k_nearest_neighbors_packed(X, x_seg, Y, y_seg, k: int, max_distance: float | None = None):
+    """The exact ``k`` (1 .. 32) nearest neighbours of K problems on packed clouds, through the uniform-grid index
+    (``rap_k_nearest_neighbors``): for every row i of ``X[xs:xs+xn]`` the ``count[i] <= k`` rows of Y within ``Y[ys:ys+yn]`` (and within
+    ``max_distance``; None: no limit) with the smallest (squared distance, row), in ascending order.  -> (idx (NX,k) int32: rows of
+    Y, d2 (NX,k) fp32: squared distances, count (NX,) int32); unused slots hold -1 and inf, and rows of X outside every segment
+    count 0.  Segments as ``nearest_neighbors_packed``, whose result ``k = 1`` reproduces bit for bit.  No host synchronisation."""
+    _require_cuda(X, "X")
+    _require_cuda(Y, "Y")
+    device = X.device
+    X, Y = _f32c(X.reshape(-1, 3)), _f32c(Y.to(device).reshape(-1, 3))
+    xs = x_seg.to(device=device, dtype=torch.int32).reshape(-1, 2).contiguous()
+    ys = y_seg.to(device=device, dtype=torch.int32).reshape(-1, 2).contiguous()
+    K = xs.shape[0]
+    if K == 0 or ys.shape[0] != K:
+        raise ValueError(f"x_seg and y_seg must hold the same positive number of (start, len) rows, got {xs.shape[0]} and {ys.shape[0]}")
+    if not 1 <= int(k) <= 32:
+        raise ValueError(f"k must lie in [1, 32], got {k}")
+    gate = 0.0 if max_distance is None else float(max_distance)
+    if max_distance is not None and not gate > 0.0:
+        raise ValueError("max_distance must be positive (None: no limit)")
+    NX = X.shape[0]
+    idx = torch.full((NX, int(k)), -1, dtype=torch.int32, device=device)
+    d2 = torch.full((NX, int(k)), float("inf"), dtype=torch.float32, device=device)
+    count = torch.zeros((NX,), dtype=torch.int32, device=device)
+    if NX == 0:
+        return idx, d2, count
+    if Y.shape[0] == 0:                                                  # the C ABI wants non-empty arrays; every segment clamps to nothing
+        Y = torch.zeros((1, 3), dtype=torch.float32, device=device)
+        ys = torch.zeros_like(ys)
+    NY = Y.shape[0]
+    lib = _lib.load()
+    ws = workspace(device, lib.rap_knn_workspace_bytes(NX, NY, K))
+    with torch.cuda.device(device):
+        rc = lib.rap_k_nearest_neighbors(_lib.ptr(X), _lib.ptr(xs), _lib.ptr(Y), _lib.ptr(ys), K, NX, NY, int(k), gate, _lib.ptr(idx),
+                                         _lib.ptr(d2), _lib.ptr(count), _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
+    _lib.check(rc, "rap_k_nearest_neighbors")
+    return idx, d2, count
+
+
 def _lengths(lengths, K, N, device):
     if lengths is None:
         return torch.full((K,), N, dtype=torch.int32, device=device)

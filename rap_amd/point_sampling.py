@@ -108,11 +108,15 @@ def voxel_down_sample_torch(points: torch.Tensor, voxel_size: float, path: str |
     return idx[: int(count.cpu())]
 
 
-def remove_statistical_outlier(points: torch.Tensor, nb_neighbors: int = 20, std_ratio: float = 2.5):
+def remove_statistical_outlier(points: torch.Tensor, nb_neighbors: int = 20, std_ratio: float = 2.5, search: str = "brute"):
     """Open3D ``PointCloud.remove_statistical_outlier(nb_neighbors, std_ratio)`` as extract_sample_features.py:378-385 calls it:
     returns ``(points[inlier_indices], inlier_indices)`` -- the filtered cloud and the ascending int64 indices of the kept points.
     Rule (Open3D's published algorithm; the wheel is not in the reference mount: parity unpinned): a point is kept iff the mean
-    distance d to its ``nb_neighbors`` nearest points (itself included) satisfies 0 < d < mean(d) + std_ratio * std(d)."""
+    distance d to its ``nb_neighbors`` nearest points (itself included) satisfies 0 < d < mean(d) + std_ratio * std(d).
+    ``search``: ``"brute"`` (N^2 pair distances, ``rap_statistical_outliers``) or ``"grid"`` (the same neighbours through a uniform-grid
+    index built on the device, ``rap_statistical_outliers_grid``: O(N) work, for raw scans)."""
+    if search not in ("brute", "grid"):
+        raise ValueError(f"search must be one of ('brute', 'grid'), got {search!r}")
     _require_cuda(points, "points")
     device = points.device
     pts = _f32c(points)
@@ -122,11 +126,13 @@ def remove_statistical_outlier(points: torch.Tensor, nb_neighbors: int = 20, std
     lib = _lib.load()
     idx = torch.empty(N, dtype=torch.int64, device=device)
     count = torch.empty(1, dtype=torch.int32, device=device)
-    ws = torch.empty(lib.rap_outlier_workspace_bytes(N), dtype=torch.uint8, device=device)
+    grid = search == "grid"
+    ws = torch.empty((lib.rap_outlier_grid_workspace_bytes if grid else lib.rap_outlier_workspace_bytes)(N), dtype=torch.uint8, device=device)
+    entry = lib.rap_statistical_outliers_grid if grid else lib.rap_statistical_outliers
     with torch.cuda.device(device):
-        rc = lib.rap_statistical_outliers(_lib.ptr(pts), N, int(nb_neighbors), float(std_ratio), _lib.ptr(idx), _lib.ptr(count), _lib.ptr(None),
-                                          _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
-    _lib.check(rc, "rap_statistical_outliers")
+        rc = entry(_lib.ptr(pts), N, int(nb_neighbors), float(std_ratio), _lib.ptr(idx), _lib.ptr(count), _lib.ptr(None),
+                   _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
+    _lib.check(rc, "rap_statistical_outliers_grid" if grid else "rap_statistical_outliers")
     idx = idx[: int(count.cpu())]                       # the caller needs the size (Open3D returns a list)
     return pts[idx], idx
 
