@@ -42,7 +42,8 @@ extern "C" {
  * rap_part_acc_workspace_bytes and rap_part_acc (part accuracy and the part matching that matched_part_ids arguments take);
  * rap_knn_workspace_bytes, rap_k_nearest_neighbors, rap_normals_grid_workspace_bytes, rap_estimate_normals_grid,
  * rap_outlier_grid_workspace_bytes and rap_statistical_outliers_grid (the k nearest rows over the uniform-grid index, and the normal
- * estimation and the outlier removal on it). */
+ * estimation and the outlier removal on it); rap_fps_grid_workspace_bytes, rap_farthest_point_sampling_grid and rap_fps_grid_params
+ * (farthest point sampling over a bucket index: the index lists of rap_farthest_point_sampling, less work per pick). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -512,6 +513,23 @@ int rap_spinnet_describe(const rap_spinnet* m, const float* pts, const int32_t* 
 int rap_farthest_point_sampling(const float* points, const int32_t* cloud_start, const int32_t* cloud_len, const int32_t* k_per_cloud,
                                 const int32_t* start_idx, int32_t n_clouds, int32_t k_max, int32_t* indices_out, float* dist_ws,
                                 void* stream);
+/* rap_farthest_point_sampling over a bucket index: the same tables and, for every input, bit for bit the same indices_out (clamped
+ * starts, K > length, -1 padding, zero-length clouds, duplicate points and non-finite rows included).  One block per cloud sorts the
+ * cloud's rows into the cells of a uniform grid (about points_per_bucket rows per cell, at most max_buckets cells) and keeps per cell
+ * the tight box of its rows, the largest running distance in it and the lowest index that attains it; a pick then updates only the
+ * cells whose box lies closer to it than their largest distance, and the next pick is the best cell's.  A cloud with a non-finite
+ * coordinate is walked by the plain loop inside the same kernel.  The result depends neither on the order the sort leaves inside a
+ * cell nor on the other clouds of the call; no host synchronisation.
+ * total_points: the rows of `points` (the cloud tables are clamped to it, and it sizes the workspace: 20 bytes per point, the sorted
+ * rows and their running distances); workspace >= rap_fps_grid_workspace_bytes(total_points, n_clouds) (host arithmetic; 0 without a
+ * point).  Null pointers and bad counts: RAP_ERR_INVALID; a missing or short workspace: RAP_ERR_WORKSPACE before anything is written.
+ * rap_fps_grid_params returns the two build constants in effect (rap_set_tuning key 22 sets points_per_bucket to one of 1, 8, 16, 32,
+ * 48, 64, 128 and key 23 the block size to 256, 512 or 1024; every setting gives the same indices). */
+size_t rap_fps_grid_workspace_bytes(int64_t total_points, int32_t n_clouds);
+int rap_farthest_point_sampling_grid(const float* points, int64_t total_points, const int32_t* cloud_start, const int32_t* cloud_len,
+                                     const int32_t* k_per_cloud, const int32_t* start_idx, int32_t n_clouds, int32_t k_max,
+                                     int32_t* indices_out, void* workspace, size_t workspace_bytes, void* stream);
+void rap_fps_grid_params(int32_t* points_per_bucket, int32_t* max_buckets);
 
 /* Voxel down-sampling, the first preprocessing step of the same script (reference dataset_process/utils/dataset_utils.py:279-322,
  * voxel_down_sample_torch): per occupied voxel the point closest to the voxel centre (distance quantised to 1000 levels, ties to the
@@ -858,6 +876,8 @@ int rap_profile_collect_ex(float* h_ms_out, int64_t* h_count_out, int32_t n_clas
  *           0: 256-row items, two stages (round 5);
  *           64 / 128: that item size + ring, 66 / 130: 64 rows x 4 / 128 rows x 2 key groups -- forced for every call of at most 8 192 token
  *             rows AND for rap_attention_h16 (the A/B values)}.  (rap_workspace_bytes does not depend on it.)
+ *   key 22 rap_farthest_point_sampling_grid: points per bucket {32 (default), 1, 8, 16, 48, 64, 128}.  Bit-identical results.
+ *   key 23 rap_farthest_point_sampling_grid: threads of the one block per cloud {512 (default), 256, 1024}.  Bit-identical results.
  * Operand range of compute dtype 3 (and of the fp16 residual stream): every paired activation -- LayerNorm output, q / k (also without
  * qk-norm), v, attention output, GEGLU output -- is clipped to +-65 504 before it is split into head and tail (NaN stays NaN), and
  * rap_model_set_compute_dtype(3) refuses weights that are not finite.  scripts/check_checkpoint.py compares the mode with exact fp32 on

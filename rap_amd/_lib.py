@@ -111,6 +111,9 @@ SIGNATURES = {
     "rap_voxel_downsample_sorted": (c_int32, [_P, c_int64, c_float, _P, c_float, _P, _P, _P, c_size_t, _P]),
     "rap_voxel_coverage_sorted": (c_int32, [_P, c_int64, c_float, _P, _P, _P, c_size_t, _P]),
     "rap_farthest_point_sampling": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, _P, _P, _P]),
+    "rap_fps_grid_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "rap_fps_grid_params": (None, [_P, _P]),
+    "rap_farthest_point_sampling_grid": (c_int32, [_P, c_int64, _P, _P, _P, _P, c_int32, c_int32, _P, _P, c_size_t, _P]),
     "rap_spinnet_weight_count": (c_int64, []),
     "rap_spinnet_create": (c_int32, [_P, c_int64, _P, ctypes.POINTER(_P)]),
     "rap_spinnet_destroy": (None, [_P]),

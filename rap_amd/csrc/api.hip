@@ -159,6 +159,7 @@ extern rap_tuning_t g_rap_attn_h16_dma;          // attn_h16.hip
 extern rap_tuning_t g_rap_gemm_f32_persistent;   // gemm_f32.hip
 extern rap_tuning_t g_rap_attn_x2_wpe;           // attn_x2.hip
 extern rap_tuning_t g_rap_attn_h16_small;        // attn_h16.hip, tuning key 20
+extern rap_tuning_t g_rap_fps_grid_per, g_rap_fps_grid_block;      // fps_grid.hip, tuning keys 22 and 23
 rap_tuning_t g_rap_attn_lpt = 1;               // tuning key 15: attention work lists longest-segment-first (1, default) or in segment order (0)
 // tuning key 17: split precision takes over from this many token rows (align_up(TP, 256)) per call; SMALLER calls of a model in compute
 // dtype 3 run the exact-fp32 kernels -- both are fp32-accurate, and below a few thousand tokens every kernel of a layer sits at the launch
@@ -200,6 +201,8 @@ static const TuningRow kTuning[] = {
   {18, &g_rap_ring_blocks, -1, {}},              // four-stage ring of the 128 x 128 16-bit GEMM up to this many blocks per launch (0 = never)
   {19, &g_rap_small_fused, 2, {0, 1}},           // combine + LayerNorm fusion of few-token calls
   {20, &g_rap_attn_h16_small, 7, {0, 1, 2, 64, 128, 66, 130}},   // 16-bit attention of few-token calls: 64 / 128-row work items + four-stage ring
+  {22, &g_rap_fps_grid_per, 7, {1, 8, 16, 32, 48, 64, 128}},     // bucket index of farthest point sampling: points per bucket (identical results)
+  {23, &g_rap_fps_grid_block, 3, {256, 512, 1024}},              // ... and threads of its one block per cloud (identical results)
 };
 extern "C" int rap_set_tuning(int32_t key, int32_t value) {
   for (const TuningRow& r : kTuning) {

@@ -4,6 +4,7 @@
 #include "../../include/rapflow.h"
 #include "half.h"
 #include "kernels.h"
+#include "fps_grid.h"
 
 #include <cmath>
 #include <new>
@@ -910,6 +911,29 @@ extern "C" int rap_farthest_point_sampling(const float* points, const int32_t* c
   if (!points || !cloud_start || !cloud_len || !k_per_cloud || !start_idx || !indices_out || !dist_ws || n_clouds <= 0 || k_max <= 0)
     return RAP_ERR_INVALID;
   return launch_fps((hipStream_t)stream, points, cloud_start, cloud_len, k_per_cloud, start_idx, n_clouds, k_max, dist_ws, indices_out);
+}
+
+// ... over a bucket index (fps_grid.hip): the same tables, the same index lists.  The workspace holds the sorted rows and their running
+// distances, 20 bytes per point; the bucket tables live in LDS, so the number of clouds does not enter
+extern "C" size_t rap_fps_grid_workspace_bytes(int64_t total_points, int32_t n_clouds) {
+  return total_points <= 0 || total_points > 0x7fffffffLL || n_clouds <= 0 ? 0 : fps_grid_workspace_bytes(total_points);
+}
+extern "C" void rap_fps_grid_params(int32_t* points_per_bucket, int32_t* max_buckets) {
+  int per, mb, block;
+  fps_grid_params(&per, &mb, &block);
+  if (points_per_bucket) *points_per_bucket = per;
+  if (max_buckets) *max_buckets = mb;
+}
+extern "C" int rap_farthest_point_sampling_grid(const float* points, int64_t total_points, const int32_t* cloud_start, const int32_t* cloud_len,
+                                                const int32_t* k_per_cloud, const int32_t* start_idx, int32_t n_clouds, int32_t k_max,
+                                                int32_t* indices_out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!points || !cloud_start || !cloud_len || !k_per_cloud || !start_idx || !indices_out || total_points < 0 || total_points > 0x7fffffffLL ||
+      n_clouds <= 0 || k_max <= 0)
+    return RAP_ERR_INVALID;
+  const size_t need = fps_grid_workspace_bytes(total_points);              // 0 without a point: every cloud is empty, every row -1
+  if ((need && !workspace) || workspace_bytes < need) return RAP_ERR_WORKSPACE;
+  return launch_fps_grid((hipStream_t)stream, points, (long)total_points, cloud_start, cloud_len, k_per_cloud, start_idx, n_clouds, k_max, workspace,
+                         indices_out);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -355,6 +355,11 @@ int launch_normals_items(hipStream_t stream, const int32_t* seg, int K, long N, 
 int launch_fps(hipStream_t stream, const float* pts, const int32_t* cloud_start, const int32_t* cloud_len, const int32_t* Ks,
                const int32_t* starts, int C, int Kmax,
                float* dist, int32_t* out);
+// the same index lists over a bucket index built per cloud inside the kernel (fps_grid.hip); total: the rows of pts, which the cloud
+// tables are clamped to; ws: fps_grid_workspace_bytes(total) of fps_grid.h
+int launch_fps_grid(hipStream_t stream, const float* pts, long total, const int32_t* cloud_start, const int32_t* cloud_len, const int32_t* Ks,
+                    const int32_t* starts, int C, int Kmax, void* ws, int32_t* out);
+void fps_grid_params(int* per, int* max_buckets, int* block);
 
 // voxel down-sampling (voxel.hip; reference dataset_process/utils/dataset_utils.py:279-322)
 int launch_voxel_bounds(hipStream_t stream, const float* pts, long N, float vs, long long* bounds6, unsigned int* dmax_bits);

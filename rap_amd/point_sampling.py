@@ -14,10 +14,16 @@ from .flow_model import _f32c, _require_cuda
 
 
 def sample_farthest_points(points: torch.Tensor, lengths: torch.Tensor | None = None, K=50, random_start_point: bool = False,
-                           start_idx: torch.Tensor | None = None):
+                           start_idx: torch.Tensor | None = None, search: str = "brute"):
     """pytorch3d signature: points (N,P,3) zero-padded, lengths (N,), K int or (N,) -> (sampled (N,Kmax,3), idx (N,Kmax) int64),
     padded with 0 / -1 past min(K_n, length_n).  The random start (one ``torch.randint(high=length_n)`` per cloud, in cloud order,
-    as pytorch3d draws it) can be overridden with ``start_idx``."""
+    as pytorch3d draws it) can be overridden with ``start_idx``.
+    ``search``: ``"brute"`` (every pick re-reads the cloud, ``rap_farthest_point_sampling``) or ``"grid"`` (the same index lists, bit
+    for bit, over a bucket index built per cloud on the device, ``rap_farthest_point_sampling_grid``: a pick touches only the buckets
+    it can change.  Faster at every shape measured on one MI355X -- 2.5 x at 4 096 of 20 000 points, 5.9 x at 20 000 of 100 000, 2.6 x
+    for 64 clouds of 16 384, 20 x at 20 000 of 400 000 -- and no shape was found where it is slower)."""
+    if search not in ("brute", "grid"):
+        raise ValueError(f"search must be one of ('brute', 'grid'), got {search!r}")
     _require_cuda(points, "points")
     device = points.device
     N, P, _ = points.shape
@@ -33,24 +39,33 @@ def sample_farthest_points(points: torch.Tensor, lengths: torch.Tensor | None = 
     i32 = lambda t: t.to(device=device, dtype=torch.int32).contiguous()
     cloud_start = i32(torch.arange(N, dtype=torch.int64) * P)
     idx_out = torch.empty((N, Kmax), dtype=torch.int32, device=device)
-    dist = torch.empty((N * P,), dtype=torch.float32, device=device)
     lib = _lib.load()
     len_d, k_d, st_d = i32(lengths), i32(Ks), i32(start_idx)      # named: a temporary's memory is recycled by the next allocation
-    with torch.cuda.device(device):
-        rc = lib.rap_farthest_point_sampling(_lib.ptr(pts), _lib.ptr(cloud_start), _lib.ptr(len_d), _lib.ptr(k_d), _lib.ptr(st_d), N,
-                                             Kmax, _lib.ptr(idx_out), _lib.ptr(dist), _lib.current_stream(device))
-    _lib.check(rc, "rap_farthest_point_sampling")
+    if search == "grid":
+        ws = torch.empty(lib.rap_fps_grid_workspace_bytes(N * P, N), dtype=torch.uint8, device=device)
+        with torch.cuda.device(device):
+            rc = lib.rap_farthest_point_sampling_grid(_lib.ptr(pts), N * P, _lib.ptr(cloud_start), _lib.ptr(len_d), _lib.ptr(k_d), _lib.ptr(st_d),
+                                                      N, Kmax, _lib.ptr(idx_out), _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
+        _lib.check(rc, "rap_farthest_point_sampling_grid")
+    else:
+        dist = torch.empty((N * P,), dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            rc = lib.rap_farthest_point_sampling(_lib.ptr(pts), _lib.ptr(cloud_start), _lib.ptr(len_d), _lib.ptr(k_d), _lib.ptr(st_d), N,
+                                                 Kmax, _lib.ptr(idx_out), _lib.ptr(dist), _lib.current_stream(device))
+        _lib.check(rc, "rap_farthest_point_sampling")
     idx = idx_out.to(torch.int64)
     gathered = torch.gather(pts, 1, idx.clamp_min(0)[..., None].expand(-1, -1, 3))         # data movement only
     sampled = torch.where((idx >= 0)[..., None], gathered, torch.zeros_like(gathered))
     return sampled, idx
 
 
-def apply_batched_fps(batch_augmented_tensor, batch_lengths_tensor, batch_k_tensor, global_seed: int, device):
-    """point_sampling_utils.py:263-305 -> (list of sampled parts (K_i,3), indices (N,Kmax))."""
+def apply_batched_fps(batch_augmented_tensor, batch_lengths_tensor, batch_k_tensor, global_seed: int, device, search: str = "brute"):
+    """point_sampling_utils.py:263-305 -> (list of sampled parts (K_i,3), indices (N,Kmax)).  ``search``: as ``sample_farthest_points``."""
+    if search not in ("brute", "grid"):
+        raise ValueError(f"search must be one of ('brute', 'grid'), got {search!r}")
     torch.manual_seed(global_seed)
     batch = batch_augmented_tensor.contiguous().to(device)
-    _, idx = sample_farthest_points(batch, lengths=batch_lengths_tensor, K=batch_k_tensor, random_start_point=True)
+    _, idx = sample_farthest_points(batch, lengths=batch_lengths_tensor, K=batch_k_tensor, random_start_point=True, search=search)
     parts = [batch[i][idx[i][: int(k)]] for i, k in enumerate(batch_k_tensor)]
     return parts, idx
 

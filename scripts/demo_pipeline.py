@@ -33,6 +33,8 @@ def main():
     ap.add_argument("--dtype", default="bfloat16", choices=["float32", "bfloat16", "float16"])
     ap.add_argument("--raw-factor", type=int, default=8, help="raw scan = this many jittered copies of every view point")
     ap.add_argument("--voxel", type=float, default=0.004, help="voxel size of the down-sampling (normalised units)")
+    ap.add_argument("--fps-search", default="brute", choices=["brute", "grid"],
+                    help="farthest point sampling: every pick re-reads the cloud, or the same picks over a bucket index (DESIGN.md 7.7)")
     ap.add_argument("--out", default="/tmp/rap_demo")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -62,7 +64,8 @@ def main():
     padded = torch.zeros(len(supports), int(lens.max()), 3, device=dev)
     for i, d in enumerate(supports):
         padded[i, : d.shape[0]] = d
-    sampled, _ = sample_farthest_points(padded, lengths=lens, K=torch.minimum(torch.tensor(ns), lens), random_start_point=True)
+    sampled, _ = sample_farthest_points(padded, lengths=lens, K=torch.minimum(torch.tensor(ns), lens), random_start_point=True,
+                                        search=args.fps_search)
     keys = []
     for i, (d, n) in enumerate(zip(supports, ns)):
         k = sampled[i, : min(n, d.shape[0])]
@@ -105,7 +108,7 @@ def main():
                                       out["translations_selected"])
     t_files = time.perf_counter() - t0
     print(json.dumps({"pairs": B, "views": P, "points_per_view": args.points, "generations": args.generations, "dtype": args.dtype,
-                      "raw_points": raw_points, "points_after_voxel_downsampling": kept_points,
+                      "fps_search": args.fps_search, "raw_points": raw_points, "points_after_voxel_downsampling": kept_points,
                       "seconds": {"voxel_downsample_and_fps": t_pre, "miniSpinNet_features": t_feat, "sample_generations_incl_rigidity_selection": t_sample,
                                   "overlap_ratio_selection": t_overlap, "transform_files": t_files},
                       "best_by_rigidity": out["best_gen_indices"].tolist(), "best_by_overlap": best_ov.tolist(),
