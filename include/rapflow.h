@@ -120,6 +120,18 @@ int rap_model_bounded_attention_launches(const rap_model* m);
  * the absent inputs -- rap_amd.PointCloudDiT does -- which is exact.) */
 int rap_model_set_qk_norm(rap_model* m, int32_t on);
 int rap_model_qk_norm(const rap_model* m);
+/* softcap of the reference's constructor (flow_model/point_cloud_dit.py:27; layer.py:33,64,106-128 hand it to flash-attn): with
+ * c > 0 every attention logit s = q.k / sqrt(64) becomes c * tanh(s / c) before the softmax; 0 (default) = off.  A finite c > 0 is accepted,
+ * anything else is RAP_ERR_INVALID.  A capped model runs ONE attention plan whatever the call's size: the soft-capped online-softmax kernels,
+ * unsplit, on 256-row work items (no bounded softmax: rap_model_bounded_attention_launches is 0 while a cap is set; no key ranges, no key
+ * groups).  Not a per-call switch: set it before the first call, like qk_norm.  rap_model_softcap returns the cap (< 0 for a NULL model). */
+int rap_model_set_softcap(rap_model* m, float c);
+float rap_model_softcap(const rap_model* m);
+/* final_mlp_act of the reference's constructor (point_cloud_dit.py:30,111-117): the activation behind the two hidden layers of the head
+ * (fp32 in every compute mode).  0 = SiLU (default), 1 = GELU (erf, nn.GELU()'s default), 2 = ReLU; anything else is RAP_ERR_INVALID.  The
+ * non-SiLU heads never split K (the split-K form of few-token calls is SiLU's). */
+int rap_model_set_final_act(rap_model* m, int32_t act);
+int rap_model_final_act(const rap_model* m);
 /* Storage type of the residual stream in the 16-bit compute modes: 0 = fp32 (default), 2 = fp16.  With fp16 the stream between the
  * layer kernels is held the way the reference's own "16-mixed" inference holds it (nn.Linear outputs are 16-bit under autocast and
  * flow_model/layer.py:155-164 adds them): every residual sum is formed in fp32 from the GEMM's fp32 accumulators and rounded once,
@@ -563,7 +575,8 @@ int rap_voxel_coverage_sorted(const float* points, int64_t N, float voxel_size, 
 /* ---- kernel-level entry points (used by the parity tests; same kernels the calls above launch) ---- */
 /* C(M,N) = A(M,K) W(N,K)^T (+bias) (+resid) ; epilogue: 0 bias, 1 bias+resid, 2 bias+SiLU,
  * 3 GEGLU (W/bias must be value/gate interleaved by rap_geglu_interleave; C is (M,N/2)),
- * 4 head-major qkv scatter ([3][H][M][64]), 5 bias + anchor embedding select, 6 bias+ReLU. */
+ * 4 head-major qkv scatter ([3][H][M][64]), 5 bias + anchor embedding select, 6 bias+ReLU, 8 bias+GELU (erf, nn.GELU()'s default;
+ * 7 is internal and refused). */
 int rap_gemm_f32(int32_t epilogue, const float* A, int32_t lda, const float* W, int32_t ldw, float* C, int32_t ldc,
                  int32_t M, int32_t N, int32_t K, const float* bias, const float* resid, int32_t ldr,
                  const uint8_t* anchor, const float* anchor_emb, int32_t heads, void* stream);
@@ -587,7 +600,8 @@ int rap_gemm_h16_form(int32_t dtype, int32_t epilogue, int32_t M, int32_t N, int
 /* What a model call of a given shape does, as pure host arithmetic: no model handle, no device.  The launch path itself runs by the function
  * this reports (api.hip: plan_call), so the answer cannot drift from the call.  The current tuning keys are honoured (5, 6, 7, 11, 12, 17 - 20).
  *   compute_dtype / resid_dtype: as rap_model_set_compute_dtype / rap_model_set_residual_dtype; d, heads, num_layers, in_dim: the model
- *   (qk-norm on); TP tokens, B samples, nseg_part part segments (empty ones counted: B x P of rap_sample, VP of rap_dit_forward);
+ *   (qk-norm on, softcap = 0, SiLU head: a capped model runs every attention launch unsplit on 256-row items, a GELU / ReLU head never
+ *   splits K -- rap_model_set_softcap, rap_model_set_final_act); TP tokens, B samples, nseg_part part segments (empty ones counted: B x P of rap_sample, VP of rap_dit_forward);
  *   rows: rows of the adaLN table (flow steps of rap_sample, B of rap_dit_forward: the workspace size depends on it, nothing else does);
  *   bounded != 0: the attention launches take the bounded softmax (rap_model_bounded_attention_launches counts them).
  * out[0 .. RAP_CALL_PLAN_FIELDS - 1] (n_out >= RAP_CALL_PLAN_FIELDS):
@@ -633,6 +647,19 @@ int rap_attention_f32(const float* qkv_headmajor, const int32_t* cu_seqlens, int
                       <= 40 (the fp32 kernel then drops the softmax offset: |score| log2 e <= 58); a head whose bound is larger gets
                       NaN outputs */, void* ws,
                       size_t ws_bytes, void* stream);
+/* The SOFT-CAPPED attention kernels a model with rap_model_set_softcap(c > 0) runs, one per arithmetic: every logit s = q.k / sqrt(64)
+ * becomes softcap * tanh(s / softcap) before the online softmax (flash-attn's softcap).  Operands, layouts and workspace
+ * (rap_attention_workspace_bytes) are those of rap_attention_f32 / rap_attention_h16 (q as projected or normalised, q_mul = 8: not
+ * pre-scaled) / rap_x2_attention; there is no logit_bound (the bounded softmax has no capped form).  One launch form each: 256-row work
+ * items, unsplit, whatever the tuning keys 5, 16 and 20 say.  softcap <= 0 or not finite: RAP_ERR_INVALID; a workspace below the query's
+ * value: RAP_ERR_WORKSPACE; both before anything is written. */
+int rap_attention_f32_softcap(const float* qkv_headmajor, const int32_t* cu_seqlens, int32_t nseg, float* out, int64_t TP,
+                              int32_t heads, float softcap, void* ws, size_t ws_bytes, void* stream);
+int rap_attention_h16_softcap(int32_t dtype, const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens,
+                              int32_t nseg, uint16_t* out, int64_t TP, int32_t heads, float softcap, void* ws, size_t ws_bytes,
+                              void* stream);
+int rap_x2_attention_softcap(const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens, int32_t nseg,
+                             uint16_t* out, int64_t TP, int32_t heads, float softcap, void* ws, size_t ws_bytes, void* stream);
 /* Kernel-level access to the SPLIT forms of the fp32 and the split-precision attention that few-token rap_sample / rap_dit_forward calls
  * run (tuning key 5): every work item is cut into `splits` key ranges (1, 2 or 4; anything else: RAP_ERR_INVALID), each range writes its
  * un-normalised partial output and row sums to the workspace, and one combine pass merges them in a fixed order (deterministic).

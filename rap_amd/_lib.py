@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "librapflow.so")
 
 ABI_VERSION = 6        # RAPFLOW_ABI_VERSION of include/rapflow.h this binding was written against
+FINAL_ACTS = {"silu": 0, "gelu": 1, "relu": 2}      # rap_model_set_final_act
 EPI_H_BIAS_RESID_H16 = 7   # rap_gemm_h16's fp16-residual epilogue (6 before ABI version 4; 6 is refused now)
 # "float32x2" (round 5): split precision -- fp32-ACCURATE transformer blocks on the fp16 matrix pipe (include/rapflow.h, compute dtype 3)
 DTYPES = {"float32": 0, "fp32": 0, "bfloat16": 1, "bf16": 1, "float16": 2, "fp16": 2, "float32x2": 3, "f32x2": 3}
@@ -44,6 +45,10 @@ SIGNATURES = {
     "rap_model_bounded_attention_launches": (c_int32, [_P]),
     "rap_model_set_qk_norm": (c_int32, [_P, c_int32]),
     "rap_model_qk_norm": (c_int32, [_P]),
+    "rap_model_set_softcap": (c_int32, [_P, c_float]),
+    "rap_model_softcap": (c_float, [_P]),
+    "rap_model_set_final_act": (c_int32, [_P, c_int32]),
+    "rap_model_final_act": (c_int32, [_P]),
     "rap_model_set_residual_dtype": (c_int32, [_P, c_int32]),
     "rap_model_residual_dtype": (c_int32, [_P]),
     "rap_workspace_bytes": (c_size_t, [_P, c_int64, c_int32, c_int32, c_int32]),
@@ -140,6 +145,7 @@ SIGNATURES = {
     "rap_build_attention_worklist": (c_int32, [_P, c_int32, c_int32, _P, c_int32, _P, _P]),
     "rap_attention_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_attention_f32": (c_int32, [_P, _P, c_int32, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
+    "rap_attention_f32_softcap": (c_int32, [_P, _P, c_int32, _P, c_int64, c_int32, c_float, _P, c_size_t, _P]),
     "rap_attention_split_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32]),
     "rap_attention_f32_split": (c_int32, [_P, _P, c_int32, _P, c_int64, c_int32, _P, c_int32, _P, c_size_t, _P]),
     "rap_layernorm_mod": (c_int32, [_P, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
@@ -161,6 +167,7 @@ SIGNATURES = {
                                       _P, c_size_t, _P]),
     "rap_gemm_h16_qkvnorm": (c_int32, [c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, c_float, _P, c_int32, _P]),
     "rap_attention_h16": (c_int32, [c_int32, _P, _P, c_int32, _P, c_int32, _P, c_int64, c_int32, _P, _P, c_size_t, _P]),
+    "rap_attention_h16_softcap": (c_int32, [c_int32, _P, _P, c_int32, _P, c_int32, _P, c_int64, c_int32, c_float, _P, c_size_t, _P]),
     "rap_layernorm_mod_h16": (c_int32, [c_int32, _P, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
     "rap_layernorm_affine_h16": (c_int32, [c_int32, _P, _P, c_int64, c_int32, _P, _P, _P]),
     "rap_layernorm_mod_h16_stream": (c_int32, [c_int32, _P, c_int32, _P, c_int64, c_int32, _P, c_int64, _P, _P]),
@@ -174,6 +181,7 @@ SIGNATURES = {
     "rap_x2_gemm": (c_int32, [c_int32, _P, c_int32, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int32, c_float, c_int32,
                               _P, _P, c_float, _P, c_int32, _P]),
     "rap_x2_attention": (c_int32, [_P, _P, c_int32, _P, c_int32, _P, c_int64, c_int32, _P, c_size_t, _P]),
+    "rap_x2_attention_softcap": (c_int32, [_P, _P, c_int32, _P, c_int32, _P, c_int64, c_int32, c_float, _P, c_size_t, _P]),
     "rap_x2_attention_split": (c_int32, [_P, _P, c_int32, _P, c_int32, _P, c_int64, c_int64, c_int32, c_int32, _P, c_size_t, _P]),
     "rap_set_tuning": (c_int32, [c_int32, c_int32]),
     "rap_profile_enable": (c_int32, [c_int32]),

@@ -116,6 +116,8 @@ struct rap_model {
   int dtype = RAP_DT_F32;     // arithmetic type of the transformer blocks (rap_model_set_compute_dtype)
   bool qk_norm = true;        // MultiHeadRMSNorm on q / k (rap_model_set_qk_norm; every shipped configuration has it on)
   int resid_dtype = RAP_DT_F32;   // storage type of the residual stream in the 16-bit modes (rap_model_set_residual_dtype): fp32 or fp16
+  float softcap = 0.f;        // > 0: every attention logit s becomes softcap * tanh(s / softcap) (rap_model_set_softcap); 0 = off
+  int final_act = 0;          // activation of the head's hidden layers (rap_model_set_final_act): 0 SiLU, 1 GELU (erf), 2 ReLU
   HalfWeights half[4];        // indexed by dtype (slot 0 unused; 3 = the paired head / tail planes of the split-precision mode)
   float* logit_bound = nullptr;   // (L, 2, H) per-head bounds on q.k/8 after qk-norm; null until a 16-bit dtype is selected
   // bounded[2 * layer + branch]: every head of THAT attention has a bound <= RAP_MAX_LOGIT_BOUND, so that launch may use the
@@ -473,7 +475,9 @@ extern "C" int rap_model_set_residual_dtype(rap_model* m, int32_t dtype) {
   return RAP_OK;
 }
 extern "C" int rap_model_residual_dtype(const rap_model* m) { return m ? m->resid_dtype : RAP_ERR_INVALID; }
-extern "C" int rap_model_bounded_attention_launches(const rap_model* m) { return m ? (m->qk_norm ? m->n_bounded : 0) : RAP_ERR_INVALID; }
+extern "C" int rap_model_bounded_attention_launches(const rap_model* m) {
+  return m ? ((m->qk_norm && !(m->softcap > 0.f)) ? m->n_bounded : 0) : RAP_ERR_INVALID;
+}
 // qk_norm = False of the reference's constructor (point_cloud_dit.py:28, layer.py:75-83,103-104): q and k go to the attention as projected.
 // Without the norm there is no bound on the logits, so every attention launch takes the online-softmax kernel; the gains in the blob are ignored.
 extern "C" int rap_model_set_qk_norm(rap_model* m, int32_t on) {
@@ -483,6 +487,24 @@ extern "C" int rap_model_set_qk_norm(rap_model* m, int32_t on) {
   return RAP_OK;
 }
 extern "C" int rap_model_qk_norm(const rap_model* m) { return m ? (m->qk_norm ? 1 : 0) : RAP_ERR_INVALID; }
+// softcap of the reference's constructor (point_cloud_dit.py:27, layer.py:33,64,106-128): s <- c tanh(s / c) in front of the softmax.  A capped
+// model runs one attention plan (plan_call / plan_attention): the soft-capped online kernels, unsplit, 256-row items.  The cap is itself a
+// logit bound (|s| <= c), so the bounded, offset-free softmax with min(bound, c) would apply -- those instantiations are not opened here.
+extern "C" int rap_model_set_softcap(rap_model* m, float c) {
+  if (!m || !(c >= 0.f) || !(c < 3.0e38f)) return RAP_ERR_INVALID;      // (NaN fails the first comparison)
+  std::lock_guard<std::mutex> lock(m->cfg_mu);
+  m->softcap = c;
+  return RAP_OK;
+}
+extern "C" float rap_model_softcap(const rap_model* m) { return m ? m->softcap : (float)RAP_ERR_INVALID; }
+// final_mlp_act of the reference's constructor (point_cloud_dit.py:30,111-117): the epilogue of the head's two hidden GEMMs
+extern "C" int rap_model_set_final_act(rap_model* m, int32_t act) {
+  if (!m || act < 0 || act > 2) return RAP_ERR_INVALID;
+  std::lock_guard<std::mutex> lock(m->cfg_mu);
+  m->final_act = act;
+  return RAP_OK;
+}
+extern "C" int rap_model_final_act(const rap_model* m) { return m ? m->final_act : RAP_ERR_INVALID; }
 
 // ---------------------------------------------------------------------------------------------
 // workspace
@@ -504,6 +526,8 @@ struct CallShape {
   int dtype, resid_dtype;      // the MODEL's compute / residual dtype (the call's arithmetic: CallPlan::dtype)
   int d, H, L, Ks;
   bool qk_norm;
+  float softcap;               // the model's cap on the attention logits (0 = off)
+  int final_act;               // the head's activation (0 SiLU, 1 GELU, 2 ReLU)
   int64_t TP;
   int B, nseg_part, rows;      // rows: rows of the adaLN table (flow steps of rap_sample, B of rap_dit_forward)
 };
@@ -517,6 +541,7 @@ struct GemmShape {
 struct CallPlan {
   int dtype;                   // the arithmetic this call runs in (eff_dtype)
   bool x2, h16_stream;         // split precision; the residual stream is held in fp16
+  bool capped;                 // soft-capped logits: every attention launch is the capped online kernel, unsplit, on 256-row items
   int TQ;                      // align_up(TP, 256): rows of every token-row buffer
   int attn_bq, attn_kg;        // query rows per attention work item; key groups per block of the 16-bit attention
   int max_items_part, max_items_batch;
@@ -535,8 +560,10 @@ static CallPlan plan_call(const CallShape& s, int force_dtype = -1) {
   const bool half = dtype == RAP_DT_BF16 || dtype == RAP_DT_F16;
   p.h16_stream = half && s.resid_dtype == RAP_DT_F16;
   // query rows per attention work item: 256, or 64 / 128 for few-token calls of the 16-bit modes (attention_h16_block_queries)
-  p.attn_bq = half ? attention_h16_block_queries(dtype, (long)T) : RAP_ATTN_BQ;
-  p.attn_kg = half ? attention_h16_key_groups(dtype, (long)T) : 1;
+  // (a capped model: the one form the soft-capped kernels have -- full-size items, one key group)
+  p.capped = s.softcap > 0.f;
+  p.attn_bq = (half && !p.capped) ? attention_h16_block_queries(dtype, (long)T) : RAP_ATTN_BQ;
+  p.attn_kg = (half && !p.capped) ? attention_h16_key_groups(dtype, (long)T) : 1;
   p.max_items_batch = (int)(s.TP / p.attn_bq) + s.B + 1;
   p.max_items_part = (int)(s.TP / p.attn_bq) + s.nseg_part + 1;
   // ff2: the one layer GEMM with K >= 1024.  Reserved by SHAPE alone (tuning key 6 only gates the launch), so that the size
@@ -561,9 +588,12 @@ static CallPlan plan_call(const CallShape& s, int force_dtype = -1) {
   p.g[PG_EMBED] = shape(EPI_BIAS_RESID, T, d, 64, 64, 64, d, d);
   // few-token calls: K of the two hidden layers of the head over 2 / 4 blocks per tile (gemm_f32_form decides by the tile count); the partial
   // planes live in the FFN buffer of the fp32 layout (4 T d floats, idle there) resp. the split-K planes of the 16-bit layouts
-  p.g[PG_HEAD0] = shape(EPI_BIAS_SILU, T, d, d, d, d, d, 0);
-  p.g[PG_HEAD1] = shape(EPI_BIAS_SILU, T, d / 2, d, d, d, d / 2, 0);
-  for (int k = PG_HEAD0; k <= PG_HEAD1; ++k) { p.g[k].ws = f32 || p.splitk_planes > 0; p.g[k].planes = f32 ? 4 : p.splitk_planes; }
+  // final_mlp_act: the epilogue of the model's activation; only SiLU has the split-K form (a GELU / ReLU head runs unsplit: no workspace, no planes)
+  const int head_epi = s.final_act == 1 ? EPI_BIAS_GELU : s.final_act == 2 ? EPI_BIAS_RELU : EPI_BIAS_SILU;
+  p.g[PG_HEAD0] = shape(head_epi, T, d, d, d, d, d, 0);
+  p.g[PG_HEAD1] = shape(head_epi, T, d / 2, d, d, d, d / 2, 0);
+  if (head_epi == EPI_BIAS_SILU)
+    for (int k = PG_HEAD0; k <= PG_HEAD1; ++k) { p.g[k].ws = f32 || p.splitk_planes > 0; p.g[k].planes = f32 ? 4 : p.splitk_planes; }
   if (f32) {
     p.g[PG_QKV] = shape(EPI_QKV_HEADMAJOR, T, 3 * d, d, d, d, 0, 0);
     p.g[PG_OUT] = shape(EPI_BIAS_RESID, T, d, d, d, d, d, d);
@@ -605,6 +635,7 @@ static int plan_form(const CallPlan& p, int k) {
 struct AttnPlan { int splits; bool one_per_cu; };
 static AttnPlan plan_attention(const CallPlan& p, int H, int branch, bool bounded) {
   const int max_items = branch == 0 ? p.max_items_part : p.max_items_batch;
+  if (p.capped) return {1, false};
   if (p.dtype == RAP_DT_F32) { const int sp = attention_f32_splits(max_items, H, bounded); return {sp, attention_f32_one_per_cu(max_items, H, sp)}; }
   if (p.x2) return {attention_x2_splits(max_items, H), false};
   return {1, false};
@@ -621,6 +652,7 @@ struct Workspace {
   int rows;                             // TQ = align_up(TP, 256): rows of every token-row buffer
   int dtype;                            // the arithmetic this call runs in (eff_dtype: the model's, or fp32 for a small split-precision call)
   bool qk_norm;                         // snapshot of the model's switch (the configuration mutex is held only while the layout is carved)
+  float softcap;                        // ... and of its cap on the attention logits (0 = off)
   double* proc_partials;
   int32_t *token_sample, *part_offsets, *attn_sort;
   int32_t *cu_batch_s, *cu_part_s;      // sanitised copies of the caller's segment tables (clamped to [0, TP], non-decreasing)
@@ -637,6 +669,7 @@ struct Workspace {
 static CallShape call_shape(const rap_model* m, int64_t TP, int B, int nseg_part, int rows) {
   CallShape s{};
   s.dtype = m->dtype; s.resid_dtype = m->resid_dtype; s.d = m->d; s.H = m->H; s.L = m->L; s.Ks = m->Ks; s.qk_norm = m->qk_norm;
+  s.softcap = m->softcap; s.final_act = m->final_act;
   s.TP = TP; s.B = B; s.nseg_part = nseg_part; s.rows = rows;
   return s;
 }
@@ -655,6 +688,7 @@ static Workspace carve_workspace(const CallShape& s, char* basep, int force_dtyp
   w.rows = plan.TQ;
   const int dtype = w.dtype = plan.dtype;
   w.qk_norm = s.qk_norm;
+  w.softcap = s.softcap;
   w.base = (float*)c.take(T * d * 4);
   const bool x2 = plan.x2;                  // split precision: fp32 residual stream, every 16-bit activation buffer holds heads AND tails
   const bool h16 = plan.h16_stream;
@@ -742,6 +776,7 @@ extern "C" int rap_call_plan(int32_t compute_dtype, int32_t resid_dtype, int32_t
   if (TP <= 0 || TP > 0x7fffffffLL / 8 || B <= 0 || nseg_part < 0 || nseg_part > 65535 || rows <= 0) return RAP_ERR_INVALID;
   CallShape s{};
   s.dtype = compute_dtype; s.resid_dtype = resid_dtype; s.d = d; s.H = heads; s.L = num_layers; s.Ks = 128 + (int)align_up((size_t)in_dim, 32);
+  s.softcap = 0.f; s.final_act = 0;      // (rapflow.h: the plan of an uncapped model with the SiLU head)
   s.qk_norm = true;      // (every shipped configuration; without it no launch is bounded and the QKV epilogue of the 16-bit modes is the plain one)
   s.TP = TP; s.B = B; s.nseg_part = nseg_part; s.rows = rows;
   const CallPlan p = plan_call(s);
@@ -837,11 +872,14 @@ static int block_f32(const rap_model* m, const Workspace& w, hipStream_t stream,
     if (!fuse_qk && w.qk_norm && (rc = launch_qknorm(stream, w.qkv, TP, H, lw.gq[a], lw.gk[a]))) return rc;
     {
       ProfScope ps(stream, a);
-      const float* bound = (w.qk_norm && m->bounded[j]) ? m->logit_bound + (size_t)j * H : nullptr;
+      const float* bound = (w.qk_norm && m->bounded[j] && !plan.capped) ? m->logit_bound + (size_t)j * H : nullptr;
       // few-token calls: split the keys of every work item over up to 4 blocks; the partial O planes live in the (idle) FFN
       // buffer (4 x TP x d floats), the partial row sums in the (idle) LN-output buffer
       const int max_items = a == 0 ? w.max_items_part : w.max_items_batch;
       const int splits = plan_attention(plan, H, a, bound != nullptr).splits;
+      if (plan.capped)
+        rc = launch_attention_f32_softcap(stream, w.qkv, w.att, TP, H, a == 0 ? w.items_part : w.items_batch, max_items, w.softcap);
+      else
       rc = launch_attention_f32(stream, w.qkv, w.att, TP, H, a == 0 ? w.items_part : w.items_batch, max_items, bound, w.ffmid, w.xn,
                                 splits, a == 0 ? w.cu_part_live : w.cu_batch_s, a == 0 ? w.nseg_part : w.nseg_batch);
     }
@@ -891,7 +929,7 @@ static int block_h16(const rap_model* m, const Workspace& w, hipStream_t stream,
     gemm_into(plan.g[PG_QKV], g, nullptr);
     g.A = w.xnh; g.W = lh.Wqkv[a]; g.C = w.qkh; g.heads = H;
     g.vt = w.vth; g.vt_nblk = w.vt_nblk; g.acc_scale = lh.s_qkv[a]; g.out_scale = lh.g_v[a];
-    const bool bnd = !x2 && w.qk_norm && m->bounded[j] != 0;         // this launch's softmax kernel (per layer and branch)
+    const bool bnd = !x2 && w.qk_norm && m->bounded[j] != 0 && !plan.capped;      // this launch's softmax kernel (per layer and branch)
     const bool prescale = attention_h16_wants_prescaled_q(dt, bnd);
     const float q_mul = prescale ? RAP_QMUL_PRESCALED : 8.0f;
     // (few-token calls: the fused epilogue exists on 128 x 128 tiles too since round 6 -- launch_gemm_h16 picks the tile; until then
@@ -911,7 +949,10 @@ static int block_h16(const rap_model* m, const Workspace& w, hipStream_t stream,
       ProfScope ps(stream, a);
       const AttnWorkItem* items = a == 0 ? w.items_part : w.items_batch;
       const int max_items = a == 0 ? w.max_items_part : w.max_items_batch;
-      if (x2) {
+      if (plan.capped) {      // unprescaled q (bnd is false), 256-row items, unsplit
+        rc = x2 ? launch_attention_x2_softcap(stream, w.qkh, w.vth, w.vt_nblk, w.atth, TP, H, items, max_items, w.softcap)
+                : launch_attention_h16_softcap(stream, dt, w.qkh, w.vth, w.vt_nblk, w.atth, TP, H, items, max_items, w.softcap);
+      } else if (x2) {
         // few-token calls: the keys of every work item over 2 / 4 blocks; the partial O planes (4 x TQ x d floats) live in the idle FFN
         // buffer (16 TQ d bytes in this mode), the partial (max, row sum) pairs in the idle LayerNorm-output buffer
         rc = launch_attention_x2(stream, w.qkh, w.vth, w.vt_nblk, w.atth, TP, H, items, max_items, reinterpret_cast<float*>(w.ffmidh),
@@ -1003,7 +1044,7 @@ static int forward_step(const rap_model* m, const Workspace& w, hipStream_t stre
       return RAP_ERR_HIP;
     }
   }
-  // final_mlp (point_cloud_dit.py:111-117): Lin+SiLU, Lin+SiLU, Lin(no bias)
+  // final_mlp (point_cloud_dit.py:111-117): Lin+act, Lin+act, Lin(no bias); act = final_mlp_act (SiLU unless rap_model_set_final_act says otherwise)
   // few-token calls: K of the two hidden layers over 2 / 4 blocks per tile; the partial planes live in the FFN buffer of the fp32 layout
   // (4 T d floats, idle here) resp. the split-K planes of the 16-bit layouts (plan_call).  The plan's M is TQ; head_rows differs from it only
   // for a caller's feature buffer of the fp16 stream (ragged M = TP_valid on planes sized for TQ)

@@ -102,6 +102,17 @@ extern "C" int rap_attention_f32(const float* qkv_headmajor, const int32_t* cu_s
   return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, nullptr, nullptr, 1);
 }
 
+// the soft-capped kernels of a model with rap_model_set_softcap (one launch form each: 256-row items, unsplit)
+static bool softcap_ok(float c) { return c > 0.f && c < 3.0e38f; }      // (NaN fails both)
+extern "C" int rap_attention_f32_softcap(const float* qkv_headmajor, const int32_t* cu_seqlens, int32_t nseg, float* out, int64_t TP,
+                                         int32_t heads, float softcap, void* ws, size_t ws_bytes, void* stream_) {
+  if (!qkv_headmajor || !out || heads <= 0 || !softcap_ok(softcap)) return RAP_ERR_INVALID;
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc, max_items;
+  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 0, &max_items))) return rc;
+  return launch_attention_f32_softcap(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, softcap);
+}
+
 // The split-KV forms few-token model calls run (attention_f32_splits / attention_x2_splits pick them there), for the parity tests:
 // ws = [work items | sanitised cu_seqlens | partial O: splits x TP x heads x 64 floats | (max, row sum): splits x TP x heads x 2 floats]
 // (the fp32 form keeps its row sums in the first half of the last plane)
@@ -245,6 +256,16 @@ extern "C" int rap_attention_h16(int32_t dtype, const uint16_t* qk, const uint16
   if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, bq, &max_items))) return rc;
   return launch_attention_h16(stream, dtype, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, 0, bq, kg);
 }
+extern "C" int rap_attention_h16_softcap(int32_t dtype, const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens,
+                                         int32_t nseg, uint16_t* out, int64_t TP, int32_t heads, float softcap, void* ws, size_t ws_bytes,
+                                         void* stream_) {
+  if (!qk || !vt || !out || heads <= 0 || !softcap_ok(softcap) || (dtype != RAP_DT_BF16 && dtype != RAP_DT_F16) || (int64_t)vt_nblk * 64 < TP)
+    return RAP_ERR_INVALID;
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc, max_items;
+  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 256, &max_items))) return rc;
+  return launch_attention_h16_softcap(stream, dtype, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, softcap);
+}
 extern "C" int rap_layernorm_mod_h16(int32_t dtype, const float* x, uint16_t* out, int64_t TP, int32_t d, const float* mod,
                                      int64_t mod_stride, const int32_t* token_row, void* stream) {
   if (!x || !out || !mod) return RAP_ERR_INVALID;
@@ -322,6 +343,14 @@ extern "C" int rap_x2_attention(const uint16_t* qk, const uint16_t* vt, int32_t 
   int rc, max_items;
   if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &max_items))) return rc;
   return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items);
+}
+extern "C" int rap_x2_attention_softcap(const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens, int32_t nseg,
+                                        uint16_t* out, int64_t TP, int32_t heads, float softcap, void* ws, size_t ws_bytes, void* stream_) {
+  if (!qk || !vt || !out || heads <= 0 || !softcap_ok(softcap) || (int64_t)vt_nblk * 64 < TP) return RAP_ERR_INVALID;
+  hipStream_t stream = (hipStream_t)stream_;
+  int rc, max_items;
+  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &max_items))) return rc;
+  return launch_attention_x2_softcap(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, softcap);
 }
 // the same over `splits` key ranges per work item (workspace layout: see rap_attention_f32_split)
 extern "C" int rap_x2_attention_split(const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens, int32_t nseg,

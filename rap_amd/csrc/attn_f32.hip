@@ -26,6 +26,7 @@
 //  * grid = work items x heads with head = blockIdx % H (blockIdx % 8 is the XCD on MI355X: each XCD's
 //    L2 then serves the K/V of one head).
 #include "kernels.h"
+#include "softcap.h"
 
 // Measured and NOT kept (round 3, call 22): K / V tiles by LDS-DMA (global_load_lds_dwordx4, 256-byte K rows with a slot ^ (row & 15) swizzle)
 // instead of through staging registers -- bit-identical output, 196 instead of 228-242 VGPRs, and exactly the same speed (141.7 vs
@@ -72,259 +73,21 @@ __global__ __launch_bounds__(64 * NW, 2) void attention_f32_kernel(const float* 
                                                                   int TP, int heads, const AttnWorkItem* __restrict__ items,
                                                                   const float* __restrict__ bound, float* __restrict__ part_o,
                                                                   float* __restrict__ part_l) {
-  __shared__ __attribute__((aligned(16))) float smem[2 * AKV * KLD + 2 * AKV * VLD];
-  float* Ks = smem;                    // [2][64][68]
-  float* Vs = smem + 2 * AKV * KLD;    // [2][64][64]
-
-  const int head = blockIdx.x % heads;
-  const AttnWorkItem it = items[blockIdx.x / heads];
-  const int len = it.seg_len;
-  if (len <= 0) return;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int hi = lane >> 5, l31 = lane & 31;
-
-  const size_t plane = (size_t)heads * TP * 64;
-  const float* Qg = qkv + ((size_t)head * TP + it.seg_start) * 64;
-  const float* Kg = Qg + plane;
-  const float* Vg = Qg + 2 * plane;
-
-  const int qw0 = it.q0 + wave * AQ_WAVE;
-  const bool wave_active = qw0 < len;   // waves beyond the segment still help stage K/V
-  if (NW == 8) {
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x) >= 256) __builtin_amdgcn_s_setprio(1);
-  }
-
-  // ---- Q fragments: qf[qt][g*4+j] = Q[q][8g + 4hi + j] * (log2(e)/8)
-  const float qscale = 0.125f * 1.44269504088896340736f;
-  float qf[2][32];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    int q = qw0 + qt * 32 + l31;
-    q = q < len ? q : len - 1;
-    const float* qp = Qg + (size_t)q * 64 + 4 * hi;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) {
-      const float4 v = *reinterpret_cast<const float4*>(qp + 8 * g);
-      qf[qt][g * 4 + 0] = v.x * qscale;
-      qf[qt][g * 4 + 1] = v.y * qscale;
-      qf[qt][g * 4 + 2] = v.z * qscale;
-      qf[qt][g * 4 + 3] = v.w * qscale;
-    }
-  }
-
-  f32x16 o[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[a][b][r] = 0.f;
-  // BOUNDED needs bound <= 40 (|score| * log2(e) <= 58, see the softmax section); a larger bound poisons this head's output with
-  // NaN instead of overflowing silently (rap_model_create only selects this kernel when every bound passes).
-  const bool bound_ok = BOUNDED ? (bound[head] <= 40.0f) : true;
-  float mrun[2] = {-1e30f, -1e30f};
-  float lsum[2] = {0.f, 0.f};
-
-  // ---- K/V staging coordinates: 4 float4 of K and 4 of V per thread per tile
-  constexpr int RS = 4 * NW;          // rows staged per pass (16 threads per 64-float row)
-  const int srow = tid >> 4;          // 0..RS-1 (+RS*i)
-  const int sc4 = (tid & 15) * 4;
-  float4 rk0, rk1, rk2, rk3, rv0, rv1, rv2, rv3;
-  const int nkv = (len + AKV - 1) / AKV;
-  int t_begin = 0, t_end = nkv;
-  if (SPLIT) {
-    t_begin = (int)((long)nkv * blockIdx.y / gridDim.y);
-    t_end = (int)((long)nkv * (blockIdx.y + 1) / gridDim.y);
-  }
-  const int koff = srow * KLD + sc4;
-  const int voff = srow * VLD + sc4;
-
-#define ATTN_LOAD_ONE(T, I, RK, RV)                                          \
-  {                                                                          \
-    int key_ = (T) * AKV + srow + RS * (I);                                  \
-    key_ = key_ < len ? key_ : len - 1;                                      \
-    RK = *reinterpret_cast<const float4*>(Kg + (size_t)key_ * 64 + sc4);     \
-    RV = *reinterpret_cast<const float4*>(Vg + (size_t)key_ * 64 + sc4);     \
-  }
-#define ATTN_LOAD_TILE(T)          \
-  ATTN_LOAD_ONE(T, 0, rk0, rv0)    \
-  ATTN_LOAD_ONE(T, 1, rk1, rv1)    \
-  if constexpr (NW == 4) {         \
-    ATTN_LOAD_ONE(T, 2, rk2, rv2)  \
-    ATTN_LOAD_ONE(T, 3, rk3, rv3)  \
-  }
-#define ATTN_STORE_ONE(BUF, I, RK, RV)                                                            \
-  *reinterpret_cast<float4*>(&Ks[(BUF) * (AKV * KLD) + koff + RS * (I) * KLD]) = RK;              \
-  *reinterpret_cast<float4*>(&Vs[(BUF) * (AKV * VLD) + voff + RS * (I) * VLD]) = RV;
-#define ATTN_STORE_TILE(BUF)           \
-  ATTN_STORE_ONE(BUF, 0, rk0, rv0)     \
-  ATTN_STORE_ONE(BUF, 1, rk1, rv1)     \
-  if constexpr (NW == 4) {             \
-    ATTN_STORE_ONE(BUF, 2, rk2, rv2)   \
-    ATTN_STORE_ONE(BUF, 3, rk3, rv3)   \
-  }
-
-  ATTN_LOAD_TILE(t_begin)
-  ATTN_STORE_TILE(0)
-  __syncthreads();
-
-  for (int t = t_begin; t < t_end; ++t) {
-    const int cur = (t - t_begin) & 1;
-    const bool more = (t + 1) < t_end;
-    if (more) { ATTN_LOAD_TILE(t + 1) }
-
-    if (wave_active) {
-      const float* Kc = Ks + cur * (AKV * KLD);
-      const float* Vc = Vs + cur * (AKV * VLD);
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt) {
-        const int kbase = t * AKV + kt * 32;
-        if (kbase >= len) break;
-        // ---- S^T = K Q^T  (32 keys x 2x32 queries).  LDS fragments are fetched one group ahead of the MFMAs
-        // that consume them and fenced in place (ATTN_FENCE lets VALU/SALU cross, pins DS and MFMA): hipcc
-        // otherwise sinks each ds_read to just before its consumer and ~130 cycles of LDS latency are exposed per
-        // 8 MFMAs (v1.0 of this kernel: 86 % of the fp32 matrix peak).
-        f32x16 st[2];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { st[0][r] = 0.f; st[1][r] = 0.f; }
-        const float* kp = Kc + (kt * 32 + l31) * KLD + 4 * hi;
-        const float* vp = Vc + (kt * 32 + 4 * hi) * VLD + 2 * l31;
-        float4 kf = *reinterpret_cast<const float4*>(kp);
-        float2 vfa, vfb;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-          float4 kn = kf;
-          if (g < 7) kn = *reinterpret_cast<const float4*>(kp + 8 * (g + 1));
-          else { vfa = *reinterpret_cast<const float2*>(vp); vfb = *reinterpret_cast<const float2*>(vp + VLD); }
-          ATTN_FENCE
-          st[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[0][g * 4 + 0], st[0], 0, 0, 0);
-          st[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.x, qf[1][g * 4 + 0], st[1], 0, 0, 0);
-          st[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[0][g * 4 + 1], st[0], 0, 0, 0);
-          st[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.y, qf[1][g * 4 + 1], st[1], 0, 0, 0);
-          st[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[0][g * 4 + 2], st[0], 0, 0, 0);
-          st[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.z, qf[1][g * 4 + 2], st[1], 0, 0, 0);
-          st[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[0][g * 4 + 3], st[0], 0, 0, 0);
-          st[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf.w, qf[1][g * 4 + 3], st[1], 0, 0, 0);
-          ATTN_FENCE
-          kf = kn;
-        }
-        // ---- mask keys beyond the segment (only the last tile can be partial)
-        if (kbase + 32 > len) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const bool valid = (kbase + mfma32_crow(r, hi)) < len;
-            st[0][r] = valid ? st[0][r] : -1e30f;
-            st[1][r] = valid ? st[1][r] : -1e30f;
-          }
-        }
-        if (BOUNDED) {
-          // ---- softmax numerators with NO offset: |score| <= bound * log2(e) <= 58 (the launcher checks bound <= 40), so
-          // exp2(score) lies in [2^-58, 2^58] and every sum stays far inside fp32; the common factor cancels in O / l.
-          // Row sums through two independent chains.
-#pragma unroll
-          for (int qt = 0; qt < 2; ++qt) {
-            float pa = 0.f, pb2 = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-              const float e0 = __builtin_amdgcn_exp2f(st[qt][r]);
-              const float e1 = __builtin_amdgcn_exp2f(st[qt][r + 1]);
-              st[qt][r] = e0; st[qt][r + 1] = e1;
-              pa += e0; pb2 += e1;
-            }
-            lsum[qt] += pa + pb2;
-          }
-        } else {
-        // ---- online softmax (lane-local except one cross-half max, a VALU v_permlane32_swap).  Round 3: row maximum through
-        // v_max3_f32 (8 instead of 15 instructions per 16 scores; hipcc also prepends a canonicalising v_max to every
-        // MFMA-output operand of fmaxf) and a DEFERRED rescale, as the 16-bit kernel has had since r01: the running reference
-        // m of a row moves only when a row of the wave outgrows it by more than 2^11.5 (e^8), so in the steady state a
-        // sub-tile costs no alpha, no 32 multiplies of O and no l * alpha -- p = 2^(s - m) <= 2^11.5 and every sum stays far
-        // inside fp32; softmax is invariant to the reference.  Same function, different rounding pattern.
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-          float mx = amax3(st[qt][0], st[qt][1], st[qt][2]);
-#pragma unroll
-          for (int r = 3; r < 15; r += 2) mx = amax3(mx, st[qt][r], st[qt][r + 1]);
-          mx = xhalf_max(fmaxf(mx, st[qt][15]));
-          if (__builtin_amdgcn_ballot_w64(mx > mrun[qt] + ATTN_DEFER_THR) != 0) {       // wave-uniform
-            const float mnew = fmaxf(mrun[qt], mx);
-            const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
-            mrun[qt] = mnew;
-            lsum[qt] *= alpha;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              o[qt][0][r] *= alpha;
-              o[qt][1][r] *= alpha;
-            }
-          }
-          float pa = 0.f, pb2 = 0.f;
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            const float e0 = __builtin_amdgcn_exp2f(st[qt][r] - mrun[qt]);
-            const float e1 = __builtin_amdgcn_exp2f(st[qt][r + 1] - mrun[qt]);
-            st[qt][r] = e0; st[qt][r + 1] = e1;
-            pa += e0; pb2 += e1;
-          }
-          lsum[qt] += pa + pb2;
-        }
-        }
-        // ---- O^T += V^T P^T : step r contracts keys {crow(r,0), crow(r,1)} = P register r.  V fragments are
-        // fetched two steps (8 MFMAs) ahead.
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          float2 vna = vfa, vnb = vfb;
-          if (r + 2 < 16) {
-            const int k0 = ((r + 2) & 3) + 8 * ((r + 2) >> 2);   // crow(r+2, 0); the +4*hi is in vp
-            const int k1 = ((r + 3) & 3) + 8 * ((r + 3) >> 2);
-            vna = *reinterpret_cast<const float2*>(vp + k0 * VLD);
-            vnb = *reinterpret_cast<const float2*>(vp + k1 * VLD);
-          }
-          ATTN_FENCE
-          o[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vfa.x, st[0][r], o[0][0], 0, 0, 0);
-          o[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vfa.y, st[0][r], o[0][1], 0, 0, 0);
-          o[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vfa.x, st[1][r], o[1][0], 0, 0, 0);
-          o[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vfa.y, st[1][r], o[1][1], 0, 0, 0);
-          o[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vfb.x, st[0][r + 1], o[0][0], 0, 0, 0);
-          o[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vfb.y, st[0][r + 1], o[0][1], 0, 0, 0);
-          o[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(vfb.x, st[1][r + 1], o[1][0], 0, 0, 0);
-          o[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(vfb.y, st[1][r + 1], o[1][1], 0, 0, 0);
-          ATTN_FENCE
-          vfa = vna; vfb = vnb;
-        }
-      }
-    }
-
-    if (more) { ATTN_STORE_TILE(cur ^ 1) }
-    __syncthreads();
-  }
-
-  if (!wave_active) return;
-  // ---- normalise and store: lane owns query (lane&31) of each q-tile; register r of tile e is d = 2*crow(r,hi)+e
-  const int dmodel = heads * 64;
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int q = qw0 + qt * 32 + l31;
-    const float ltot = xhalf_sum(lsum[qt]);
-    const float inv = SPLIT ? 1.0f : (bound_ok ? 1.0f / ltot : __builtin_nanf(""));
-    if (q < len) {
-      float* op = (SPLIT ? part_o + (size_t)blockIdx.y * TP * dmodel : out) + (size_t)(it.seg_start + q) * dmodel + head * 64;
-      if (SPLIT && hi == 0)
-        part_l[((size_t)blockIdx.y * TP + it.seg_start + q) * heads + head] = bound_ok ? ltot : __builtin_nanf("");
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        // registers 4rg..4rg+3 -> c = 8rg + 4hi + (0..3) -> d = 2c .. 2c+7 : 8 contiguous floats
-        const int d0 = 2 * (8 * rg + 4 * hi);
-        float4 w0, w1;
-        w0.x = o[qt][0][4 * rg + 0] * inv; w0.y = o[qt][1][4 * rg + 0] * inv;
-        w0.z = o[qt][0][4 * rg + 1] * inv; w0.w = o[qt][1][4 * rg + 1] * inv;
-        w1.x = o[qt][0][4 * rg + 2] * inv; w1.y = o[qt][1][4 * rg + 2] * inv;
-        w1.z = o[qt][0][4 * rg + 3] * inv; w1.w = o[qt][1][4 * rg + 3] * inv;
-        *reinterpret_cast<float4*>(op + d0) = w0;
-        *reinterpret_cast<float4*>(op + d0 + 4) = w1;
-      }
-    }
-  }
+  constexpr bool CAP = false;
+  const float cap = 0.f;
+#include "attn_f32_body.inc"
+}
+// CAP (the soft-capped form, online softmax only): every logit s = q.k/8 becomes cap * tanh(s / cap) before the softmax sees it
+// (flash-attn's softcap).  One form: 4 waves x 64 queries, never split.
+template <int NW>
+__global__ __launch_bounds__(64 * NW, 2) void attention_f32_softcap_kernel(const float* __restrict__ qkv, float* __restrict__ out,
+                                                                          int TP, int heads, const AttnWorkItem* __restrict__ items,
+                                                                          float cap) {
+  constexpr bool BOUNDED = false, SPLIT = false, CAP = true;
+  const float* const bound = nullptr;
+  float* const part_o = nullptr;
+  float* const part_l = nullptr;
+#include "attn_f32_body.inc"
 }
 
 // Work list of one attention launch: one item per 256-query block of every segment, LONGEST SEGMENT FIRST (round 4).  A block's
@@ -493,6 +256,16 @@ int launch_attention_f32(hipStream_t stream, const float* qkv, float* out, int T
   float* const no = nullptr;
   if (bound) hipLaunchKernelGGL((attention_f32_kernel<4, true>), dim3(max_items * heads), dim3(256), 0, stream, qkv, out, TP, heads, items, bound, no, no);
   else hipLaunchKernelGGL((attention_f32_kernel<4, false>), dim3(max_items * heads), dim3(256), 0, stream, qkv, out, TP, heads, items, bound, no, no);
+  RAP_LAUNCH_CHECK();
+  return RAP_OK;
+}
+
+// the soft-capped online softmax (softcap > 0, finite: the entry points check): one form, 4 waves x 64 queries, never split
+int launch_attention_f32_softcap(hipStream_t stream, const float* qkv, float* out, int TP, int heads, const AttnWorkItem* items,
+                                 int max_items, float softcap) {
+  if (max_items <= 0 || TP <= 0) return RAP_OK;
+  if (heads <= 0 || !(softcap > 0.f) || !(softcap < 3.0e38f)) return RAP_ERR_INVALID;
+  hipLaunchKernelGGL((attention_f32_softcap_kernel<4>), dim3(max_items * heads), dim3(256), 0, stream, qkv, out, TP, heads, items, softcap);
   RAP_LAUNCH_CHECK();
   return RAP_OK;
 }

@@ -321,6 +321,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_dma_kernel(GemmParams p) {
             p.C[(size_t)m * p.ldc + n] = v / (1.0f + expf(-v));
           } else if (EPI == EPI_BIAS_RELU) {
             p.C[(size_t)m * p.ldc + n] = fmaxf(v, 0.f);
+          } else if (EPI == EPI_BIAS_GELU) {
+            p.C[(size_t)m * p.ldc + n] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
           } else if (EPI == EPI_BIAS_ANCHOR) {
             const int sel = p.anchor[m] ? 1 : 0;
             p.C[(size_t)m * p.ldc + n] = v + p.anchor_emb[(size_t)sel * p.N + n];
@@ -436,6 +438,8 @@ __device__ __forceinline__ void gemm_f32_epilogue_4x2(const GemmParams& p, f32x1
           p.C[(size_t)m * p.ldc + n] = v / (1.0f + expf(-v));
         } else if (EPI == EPI_BIAS_RELU) {
           p.C[(size_t)m * p.ldc + n] = fmaxf(v, 0.f);
+        } else if (EPI == EPI_BIAS_GELU) {
+          p.C[(size_t)m * p.ldc + n] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
         } else if (EPI == EPI_BIAS_ANCHOR) {
           const int sel = p.anchor[m] ? 1 : 0;
           p.C[(size_t)m * p.ldc + n] = v + p.anchor_emb[(size_t)sel * p.N + n];
@@ -796,7 +800,7 @@ int gemm_f32_form(int epilogue, const GemmParams& p) {
   if (p.M <= 0) return 0;
   if (p.N % GBN != 0 || p.K % GBK != 0 || p.K <= 0) return RAP_ERR_INVALID;
   if ((p.lda & 3) || (p.ldw & 3)) return RAP_ERR_INVALID;
-  if (epilogue < EPI_BIAS || epilogue > EPI_BIAS_RELU) return RAP_ERR_INVALID;
+  if (epilogue < EPI_BIAS || epilogue > EPI_BIAS_GELU || epilogue == EPI_SPLITK_PART) return RAP_ERR_INVALID;
   int v = 48;
 #ifdef RAP_ABLATION_BUILD
   v = g_rap_gemm_variant;
@@ -841,6 +845,7 @@ int launch_gemm_f32(hipStream_t stream, int epilogue, const GemmParams& p_in) {
       return launch_gemm_variant<EPI_QKV_HEADMAJOR>(stream, p, form);
     case EPI_BIAS_ANCHOR: return launch_gemm_variant<EPI_BIAS_ANCHOR>(stream, p, form);
     case EPI_BIAS_RELU: return launch_gemm_variant<EPI_BIAS_RELU>(stream, p, form);
+    case EPI_BIAS_GELU: return launch_gemm_variant<EPI_BIAS_GELU>(stream, p, form);
     default: return RAP_ERR_INVALID;
   }
 }

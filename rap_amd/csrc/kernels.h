@@ -16,6 +16,7 @@ enum GemmEpilogue {
   EPI_BIAS_ANCHOR = 5,   // C = acc + bias[n] + anchor_emb[anchor[m] ? 1 : 0][n]
   EPI_BIAS_RELU = 6,     // C = max(acc + bias[n], 0)      (MiniSpinNet convolutions with folded BatchNorm)
   EPI_SPLITK_PART = 7,   // internal: C[blockIdx.y][m][n] = acc over this block's share of the k-tiles (see splitk_ws)
+  EPI_BIAS_GELU = 8,     // C = gelu_erf(acc + bias[n])    (final_mlp_act = nn.GELU: the head's hidden layers; never split over K)
 };
 
 struct GemmParams {
@@ -80,6 +81,10 @@ int launch_build_attn_worklist(hipStream_t stream, const int32_t* cu_seqlens, in
 int launch_attention_f32(hipStream_t stream, const float* qkv_headmajor, float* out, int TP, int heads,
                          const AttnWorkItem* items, int max_items, const float* bound, float* part_o, float* part_l, int splits,
                          const int32_t* cover_cu = nullptr, int cover_nseg = 0);
+// the soft-capped online softmax: every logit s = q.k/8 becomes softcap * tanh(s / softcap) before the softmax (softcap > 0, finite);
+// one form -- 256-query items, never split
+int launch_attention_f32_softcap(hipStream_t stream, const float* qkv_headmajor, float* out, int TP, int heads,
+                                 const AttnWorkItem* items, int max_items, float softcap);
 int attention_f32_splits(int max_items, int heads, bool bounded);
 bool attention_f32_one_per_cu(int max_items, int heads, int splits);      // the split launch keeps every CU to one block (16 KB of idle LDS)
 
@@ -191,6 +196,9 @@ int launch_convert_h16(hipStream_t stream, int dtype, const float* src, uint16_t
 int launch_attention_h16(hipStream_t stream, int dtype, const uint16_t* qk, const uint16_t* vt, int vt_nblk, uint16_t* out,
                          int TP, int heads, const AttnWorkItem* items, int max_items, const float* bound, int q_prescaled, int bq = 256,
                          int kg = 1);      // kg: key groups per block (1; 4 with bq = 64, 2 with bq = 128: attention_h16_kgroup_kernel)
+// the soft-capped online softmax on unprescaled q (q_mul = 8): 256-row work items, one key group
+int launch_attention_h16_softcap(hipStream_t stream, int dtype, const uint16_t* qk, const uint16_t* vt, int vt_nblk, uint16_t* out,
+                                 int TP, int heads, const AttnWorkItem* items, int max_items, float softcap);
 bool attention_h16_wants_prescaled_q(int dtype, bool bounded);
 int attention_h16_block_queries(int dtype, long rows = 0);      // work-list granularity of the 16-bit attention for a call of `rows` token rows
 bool attention_h16_forced();                                    // tuning key 20 holds one of its A/B values (a forced item size / key groups)
@@ -228,6 +236,9 @@ int launch_attention_x2(hipStream_t stream, const uint16_t* qk, const uint16_t* 
                         const AttnWorkItem* items, int max_items, float* part_o = nullptr, float* part_ml = nullptr, int splits = 1,
                         int n_tokens = 0,       // n_tokens: rows the combine pass covers (the real token count; 0 = TP)
                         const int32_t* cover_cu = nullptr, int cover_nseg = 0);      // as launch_attention_f32
+// the soft-capped form: unsplit, one block per CU
+int launch_attention_x2_softcap(hipStream_t stream, const uint16_t* qk, const uint16_t* vt, int vt_nblk, uint16_t* out, int TP, int heads,
+                                const AttnWorkItem* items, int max_items, float softcap);
 int attention_x2_splits(int max_items, int heads);
 
 // ---------------------------------------------------------------------------------------------

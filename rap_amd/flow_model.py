@@ -9,6 +9,7 @@ PyTorch is used for device memory and the current stream only.
 from __future__ import annotations
 
 import collections
+import math
 import os
 import ctypes
 
@@ -50,6 +51,24 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.float32).contiguous()
 
 
+def _final_act_code(act) -> int:
+    """final_mlp_act of the reference's constructor (point_cloud_dit.py:30,111-117: ``final_mlp_act()`` is instantiated twice) -> the code
+    of rap_model_set_final_act.  None / nn.SiLU, nn.GELU (erf) and nn.ReLU, as a class or an instance; anything else is refused, never ignored."""
+    if act is None:
+        return _lib.FINAL_ACTS["silu"]
+    nn = torch.nn
+    is_a = (lambda c: issubclass(act, c)) if isinstance(act, type) else (lambda c: isinstance(act, c))
+    if is_a(nn.SiLU):
+        return _lib.FINAL_ACTS["silu"]
+    if is_a(nn.ReLU):
+        return _lib.FINAL_ACTS["relu"]
+    if is_a(nn.GELU):
+        if not isinstance(act, type) and getattr(act, "approximate", "none") != "none":
+            raise NotImplementedError("final_mlp_act: nn.GELU(approximate='tanh') has no native epilogue (the erf form has)")
+        return _lib.FINAL_ACTS["gelu"]
+    raise NotImplementedError(f"final_mlp_act must be None, nn.SiLU, nn.GELU or nn.ReLU (class or instance), got {act!r}")
+
+
 _IncompatibleKeys = collections.namedtuple("IncompatibleKeys", ["missing_keys", "unexpected_keys"])   # torch.nn.Module's return type
 
 
@@ -68,8 +87,16 @@ class PointCloudDiT:
             raise NotImplementedError("in_dim must be a multiple of 4 in [0, 512]")
         if out_dim != 3:
             raise NotImplementedError("out_dim must be 3")
-        if dropout_rate != 0.0 or softcap != 0.0:
-            raise NotImplementedError("dropout / softcap are 0 in inference (layer.py:28-29)")
+        if dropout_rate != 0.0:
+            raise NotImplementedError("dropout is 0 in inference (layer.py:28-29)")
+        # softcap (point_cloud_dit.py:27; layer.py:33,64,106-128 hand it to flash-attn): every attention logit s becomes softcap * tanh(s / softcap)
+        # before the softmax; 0 = off.  final_mlp_act (point_cloud_dit.py:30,111-117): the activation of the head's two hidden layers.
+        softcap = float(softcap)
+        if not math.isfinite(softcap) or softcap < 0.0:
+            raise ValueError(f"softcap must be finite and >= 0, got {softcap}")
+        self.softcap = softcap
+        self.final_mlp_act = final_mlp_act
+        self._final_act = _final_act_code(final_mlp_act)
         # qk_norm / scale_emb_on / local_feat_concat_on (point_cloud_dit.py:28,33-34): every shipped configuration leaves them True; since
         # round 5 the other settings are honoured too (VERDICT r04 missing 3).  The two embedding switches only narrow emb_proj's input
         # (embedding.py:116-118,169-177): the native embedding GEMM runs on the full-width packing with ZERO weight columns for an absent
@@ -197,6 +224,11 @@ class PointCloudDiT:
             _lib.check(rc, "rap_model_create")
             if not self.qk_norm:
                 _lib.check(lib.rap_model_set_qk_norm(handle, 0), "rap_model_set_qk_norm")
+            # (every native handle is configured here, so both switches survive .to() and a re-created handle)
+            if self.softcap > 0.0:
+                _lib.check(lib.rap_model_set_softcap(handle, self.softcap), "rap_model_set_softcap")
+            if self._final_act:
+                _lib.check(lib.rap_model_set_final_act(handle, self._final_act), "rap_model_set_final_act")
             torch.cuda.current_stream(device).synchronize()   # blob may be freed after this
         self._handle, self._device = handle, device
 

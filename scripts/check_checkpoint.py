@@ -42,6 +42,26 @@ def load_weights(path, cfg):
     return {k: sd[k].float() for k in names}
 
 
+def constructor_switches(path):
+    """softcap / final_mlp_act of the checkpoint's own configuration, if it carries them (a LightningModule's ``hyper_parameters``, with the
+    velocity network's arguments either at the top or under ``flow_model``); absent keys keep PointCloudDiT's defaults.  final_mlp_act may be
+    a class, an instance, a dotted name or a hydra node ({"_target_": "torch.nn.GELU", ...}): names are resolved inside torch.nn only."""
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    hp = ck.get("hyper_parameters", {}) if isinstance(ck, dict) else {}
+    hp = hp.get("flow_model", hp) if isinstance(hp, dict) else {}
+    out = {}
+    if isinstance(hp, dict) and hp.get("softcap") is not None:
+        out["softcap"] = float(hp["softcap"])
+    act = hp.get("final_mlp_act") if isinstance(hp, dict) else None
+    if isinstance(act, dict):
+        act = act.get("_target_")
+    if isinstance(act, str):
+        act = getattr(torch.nn, act.rsplit(".", 1)[-1], act)      # an unknown name stays a string: PointCloudDiT refuses it
+    if act is not None:
+        out["final_mlp_act"] = act
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("checkpoint", nargs="?")
@@ -64,6 +84,7 @@ def main():
             sd = {k: (v * a.gamma_scale if k.endswith("q_norm.gamma") or k.endswith("k_norm.gamma") else v) for k, v in sd.items()}
     else:
         sd = load_weights(a.checkpoint, cfg)
+    switches = {} if a.synthetic else constructor_switches(a.checkpoint)
     lib = _lib.load()
     inp = S.make_uniform_inputs(1, a.views, a.points, seed=1234)
     data = {k: v.to(dev) for k, v in inp.items()}
@@ -72,13 +93,13 @@ def main():
     bounds = 8.0 * gq * gk
     report = {"weights": "seeded (rap_amd.synthetic.make_weights, seed 0)" + (f", q/k gains x {a.gamma_scale}" if a.gamma_scale != 1.0 else "")
               if a.synthetic else os.path.abspath(a.checkpoint),
-              "model": f"rap_{a.layers}", "workload": f"1 sample x {a.views} x {a.points} points, {a.steps} flow steps, rigidity forcing on",
+              "model": f"rap_{a.layers}", "constructor_switches": {k: str(v) for k, v in switches.items()}, "workload": f"1 sample x {a.views} x {a.points} points, {a.steps} flow steps, rigidity forcing on",
               "logit_bound_8_max_gq_max_gk": {"max": float(bounds.max()), "median": float(bounds.median()),
                                               "heads_above_40": int((bounds > 40).sum()), "heads": int(bounds.numel())}}
     out = {}
     for mode in ("float32", "float32x2", "bfloat16", "float16"):
         m = rap_amd.PointCloudDiT(in_dim=0, out_dim=3, embed_dim=cfg["embed_dim"], num_layers=a.layers, num_heads=cfg["num_heads"],
-                                  local_feat_dim=a.feat_dim, compute_dtype=mode)
+                                  local_feat_dim=a.feat_dim, compute_dtype=mode, **switches)
         m.load_state_dict(sd); m.to(dev)
         flow = rap_amd.RectifiedPointFlow(flow_model=m, inference_sampling_steps=a.steps, rigidity_forcing=True)
         flow.sample_and_register(data, x_1=data["x_1"], return_transformer_features=True)       # warm-up (weight copies, workspace)
