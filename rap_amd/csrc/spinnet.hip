@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void spin_patch_kernel(const float* __restrict
 // materialised (K*140, 9 Cin) matrix cost 3.4 of the 8 ms per 2048-keypoint chunk) and no padding of the 32- / 64-channel layers to 128
 // output columns (r01: 4x / 2x the MFMA work on those layers).
 //   C[(k,h,w)][n] = bias[n] + sum_{tap=(dy,dx)} sum_ci  y[k][h+dy-1][(w+dx-1) mod 20][ci] * Wt[n][tap*Cin + ci]      (+ ReLU)
-// Structure = gemm_f32_dma_kernel (LDS-DMA tiles, XOR slot swizzle, v_mfma_f32_32x32x2_f32, two LDS stages, two blocks per CU): the
+// Structure = gemm_f32_tile_kernel<EPI, 2, 2, 2, 2>, the 128 x 128 fp32 GEMM (LDS-DMA tiles, XOR slot swizzle, v_mfma_f32_32x32x2_f32, two LDS stages, two blocks per CU): the
 // contraction index is ordered tap-major, so a 32-float k-tile lies inside ONE tap (Cin is a multiple of 32) and the A row piece of a
 // pixel is 128 contiguous bytes of the shifted input pixel -- the per-lane DMA source address does the im2col gather; rows outside the
 // elevation range (zero pad) read a zero page.  Activations are channels-last with exactly Cin / Cout floats per pixel.
