@@ -43,7 +43,9 @@ extern "C" {
  * rap_knn_workspace_bytes, rap_k_nearest_neighbors, rap_normals_grid_workspace_bytes, rap_estimate_normals_grid,
  * rap_outlier_grid_workspace_bytes and rap_statistical_outliers_grid (the k nearest rows over the uniform-grid index, and the normal
  * estimation and the outlier removal on it); rap_fps_grid_workspace_bytes, rap_farthest_point_sampling_grid and rap_fps_grid_params
- * (farthest point sampling over a bucket index: the index lists of rap_farthest_point_sampling, less work per pick). */
+ * (farthest point sampling over a bucket index: the index lists of rap_farthest_point_sampling, less work per pick);
+ * rap_orient_normals_workspace_bytes and rap_orient_normals (a consistent orientation of existing normals over the minimum spanning
+ * forest of the k-NN graph). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -401,6 +403,43 @@ int rap_estimate_normals(const float* P, const int32_t* seg, int32_t K, int64_t 
 size_t rap_normals_grid_workspace_bytes(int64_t n_points, int32_t K);
 int rap_estimate_normals_grid(const float* P, const int32_t* seg, int32_t K, int64_t n_points, int32_t max_nn, float radius,
                               const float* viewpoint, float* normals, float* eigenvalues, void* ws, size_t ws_bytes, void* stream);
+/* A consistent orientation for normals that exist already: the step the reference ends its normal estimation with (Open3D's
+ * orient_normals_consistent_tangent_plane(k), dataset_process/utils/dataset_utils.py:325-358), restated as a pure function of integers
+ * and signs.  P (n_points,3) and normals (n_points,3) fp32, normals in and out; seg (K,2) as rap_estimate_normals_grid takes it: (start,
+ * len) rows clamped on the device, which must not overlap, a segment that repeats an earlier one exactly worked once (with the earlier
+ * one's viewpoint), K <= 65535.  Rows outside every segment are not written, in normals and in component_out, and a segment's result
+ * depends on that segment only.
+ *   Vertices.  Row i of a segment is a vertex when its coordinates are finite and its normal is finite and not the zero vector.  Every
+ * other row of a segment keeps its normal bits and gets component_out = -1.
+ *   Graph.  There is an undirected edge {i, j} when both are vertices, i != j, and j is among the k nearest rows of i or i among those
+ * of j.  "The k nearest rows" is the list rap_k_nearest_neighbors returns for a self-search of the segment (x_seg = y_seg = the
+ * segment, max_distance 0): the smallest (d2, row), no distance limit, the row itself counted, as Open3D counts it; rows with a
+ * non-finite coordinate are in no list.  A list slot whose row is not a vertex gives no edge.  k in 2 .. 32.
+ *   Weight.  d = n_i . n_j in fp32 from the normals as passed in, in ONE expression, fma(z_i, z_j, fma(y_i, y_j, x_i * x_j)): the x
+ * product rounded, y and z fused onto it; products commute, so both ends compute the same bits.  w = 1 - |d| (fp32).  Edges are ordered
+ * as real numbers by (w, lo, hi), lo < hi the two row indices: a total order, so the minimum spanning forest is unique.  (A d that is
+ * not finite -- normals beyond 1e19 -- orders by the bits of w like any other value; the result is still a function of the input.)
+ *   Propagation.  Along a tree edge the child is flipped when d < 0 against its parent's current direction: sign(v) = sign(seed) times
+ * the product over the tree path of (d < 0 ? -1 : +1), d from the input normals; d == 0 does not flip.
+ *   Seed, one per connected component: the vertex with the largest z, the lowest row among equals (-0 == 0).  It is flipped when
+ * n_z < 0; with viewpoint (K,3), when n . (viewpoint[k] - p) < 0, summed in double from the fp32 values as rap_estimate_normals
+ * tests it.
+ *   Outputs.  normals[i] is the input normal or its exact negation: only the three sign bits change.  component_out (n_points) int32 or
+ * NULL: the row of P (an index into P, not into the segment) of the seed of i's component.
+ *   Departure from Open3D, unpinned (Open3D is not part of the reference tree): Open3D adds the edges of a Euclidean minimum spanning
+ * tree over a Delaunay tetrahedralisation, so its graph is connected, and starts from one seed.  Here each connected component of the
+ * k-NN graph is oriented on its own from its own seed, and component_out says which rows belong together.
+ *   k outside 2 .. 32, a NULL P, seg or normals, K or n_points out of range: RAP_ERR_INVALID; a NULL or short workspace:
+ * RAP_ERR_WORKSPACE; both before any launch, nothing written.  The lists come from the k-best walk of rap_k_nearest_neighbors;
+ * the forest from Boruvka rounds with integer 64-bit minima (no floating-point atomics), one launch per step: 16 launches plus, for t <
+ * floor(log2 n_points), 3 + max(1, ceil(log2(n_points >> t))) per round t -- a function of n_points alone, so the call can be captured
+ * into a graph; rounds after the last merge leave at their first instruction.  No host read, no allocation, the same bits from call to
+ * call and for a segment whatever else is in the batch.
+ * ws >= rap_orient_normals_workspace_bytes(n_points, K) (host arithmetic, 0 for non-positive arguments: the terms of
+ * rap_normals_grid_workspace_bytes plus about 290 bytes per point, the lists at k = 32 and the forest). */
+size_t rap_orient_normals_workspace_bytes(int64_t n_points, int32_t K);
+int rap_orient_normals(const float* P, const int32_t* seg, int32_t K, int64_t n_points, int32_t k, const float* viewpoint, float* normals,
+                       int32_t* component_out, void* ws, size_t ws_bytes, void* stream);
 
 /* Submaps (submaps.hip): the stage of the reference's data preparation before the "views" exist
  * (dataset_process/utils/processing_utils.py:1927-2090).  Common to the four calls below:

@@ -7,7 +7,7 @@ One hot path of PRBonn/RAP, rebuilt as hand-written HIP kernels behind the refer
 from .data import transform_and_collate
 from .evaluator import Evaluator
 from .flow_model import PointCloudDiT
-from .normals import estimate_normals_packed, estimate_point_normals
+from .normals import estimate_normals_packed, estimate_point_normals, orient_normals_packed
 from .icp import (ICPSolution, align_anchor, compute_transform_errors_icp, icp_packed, iterative_closest_point, k_nearest_neighbors_packed,
                   nearest_neighbors_packed)
 from .metrics import compute_part_acc
@@ -24,6 +24,6 @@ __all__ = ["PointCloudDiT", "RectifiedPointFlow", "fit_transformations", "rigidi
            "average_trajectory_rigidity_rmse", "select_generations_by_rigidity", "compute_overlap_ratio",
            "select_generations_by_overlap", "transform_and_collate", "Evaluator", "iterative_closest_point", "icp_packed", "ICPSolution",
            "align_anchor", "compute_transform_errors_icp", "compute_part_acc", "nearest_neighbors_packed", "k_nearest_neighbors_packed",
-           "estimate_normals_packed", "estimate_point_normals", "deskew_packed", "fuse_frames_packed", "submap_overlap_matrix",
+           "estimate_normals_packed", "estimate_point_normals", "orient_normals_packed", "deskew_packed", "fuse_frames_packed", "submap_overlap_matrix",
            "groups_connected", "deskewing", "create_submap_from_frames", "calculate_point_cloud_overlap_ratio_fast",
            "check_submap_validity"]

@@ -93,6 +93,8 @@ SIGNATURES = {
     "rap_estimate_normals": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_float, _P, _P, _P, _P, c_size_t, _P]),
     "rap_normals_grid_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_estimate_normals_grid": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_float, _P, _P, _P, _P, c_size_t, _P]),
+    "rap_orient_normals_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "rap_orient_normals": (c_int32, [_P, _P, c_int32, c_int64, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "rap_deskew_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "rap_deskew": (c_int32, [_P, _P, _P, c_int32, c_int64, _P, c_float, _P, _P, _P, c_size_t, _P]),
     "rap_fuse_frames_workspace_bytes": (c_size_t, [c_int64, c_int32]),

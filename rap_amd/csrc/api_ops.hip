@@ -934,6 +934,24 @@ extern "C" int rap_estimate_normals_grid(const float* P, const int32_t* seg, int
                                       repeat, g);
 }
 
+// a consistent orientation for normals that exist already (orient.hip): the lists of the k-best walk, then the spanning forest
+extern "C" size_t rap_orient_normals_workspace_bytes(int64_t n_points, int32_t K) {
+  if (n_points <= 0 || K <= 0) return 0;
+  Carver c(nullptr);
+  orient_carve(c, (long)n_points, K);
+  return c.total();
+}
+extern "C" int rap_orient_normals(const float* P, const int32_t* seg, int32_t K, int64_t n_points, int32_t k, const float* viewpoint,
+                                  float* normals, int32_t* component_out, void* ws, size_t ws_bytes, void* stream) {
+  if (!P || !seg || !normals || K <= 0 || K > RAP_GRID_MAX_K || n_points <= 0 || n_points > 0x7fffffffLL / 8 || k < 2 || k > 32)
+    return RAP_ERR_INVALID;
+  if (!ws) return RAP_ERR_WORKSPACE;
+  Carver c(ws);
+  const OrientWs w = orient_carve(c, (long)n_points, K);
+  if (c.total() > ws_bytes) return RAP_ERR_WORKSPACE;
+  return launch_orient_normals((hipStream_t)stream, P, seg, K, (long)n_points, k, viewpoint, normals, component_out, w);
+}
+
 extern "C" int rap_farthest_point_sampling(const float* points, const int32_t* cloud_start, const int32_t* cloud_len,
                                            const int32_t* k_per_cloud, const int32_t* start_idx, int32_t n_clouds, int32_t k_max,
                                            int32_t* indices_out, float* dist_ws, void* stream) {

@@ -330,6 +330,23 @@ int launch_estimate_normals_grid(hipStream_t stream, const float* P, const int32
                                  const float* viewpoint, float* normals, float* eigenvalues, NnWork* items, int32_t* repeat, const NnGridWs& g);
 int launch_knn_mean_dist_grid(hipStream_t stream, const float* pts, long N, int k, double* mean_dist, int32_t* seg, NnWork* items,
                               const NnGridWs& g);
+// the lists of a self-search of every segment (the work list of launch_estimate_normals_grid, no radius): idx_out, d2_out (N,k), count_out (N)
+int launch_knn_self_rows(hipStream_t stream, const float* P, const int32_t* seg, int K, long N, int k, int32_t* idx_out, float* d2_out,
+                         int32_t* count_out, NnWork* items, int32_t* repeat, const NnGridWs& g);
+
+// consistent orientation of normals over the minimum spanning forest of the k-NN graph (orient.hip; Open3D's
+// orient_normals_consistent_tangent_plane as reference dataset_process/utils/dataset_utils.py:325-358 calls it).  The scratch is carved by
+// orient_carve (host arithmetic in N and K only; a null base gives the size); orient_rounds / orient_jumps: the launch counts
+struct OrientWs {
+  NnWork* items; int32_t* repeat; NnGridWs g;
+  int32_t* idx; unsigned* wkey; int32_t* count;      // (N,32) each: the lists and the edge weights; (N)
+  unsigned* lab; unsigned* ptr; unsigned long long* best; unsigned* besthi; unsigned long long* seed; int32_t* flags;
+};
+OrientWs orient_carve(Carver& c, long N, int K);
+int orient_rounds(long N);
+int orient_jumps(long N, int round);
+int launch_orient_normals(hipStream_t stream, const float* P, const int32_t* seg, int K, long N, int k, const float* viewpoint, float* normals,
+                          int32_t* component_out, const OrientWs& w);
 
 // batched ICP (icp.hip; pytorch3d's iterative_closest_point as reference eval/metrics.py:79, 261 call it): one call of K problems.
 // Y_normals chooses the estimator (null: point-to-point; else point-to-plane, icp_plane.hip), grid the search (null: tiled brute

@@ -311,6 +311,19 @@ int launch_estimate_normals_grid(hipStream_t stream, const float* P, const int32
   return knn_launch(stream, KNN_NORMALS, a, (int)nn_max_items(N, K));
 }
 
+// the lists themselves for a self-search (orient.hip): the work list and the cell-order walk of the normal estimation, the output of
+// rap_k_nearest_neighbors without a radius
+int launch_knn_self_rows(hipStream_t stream, const float* P, const int32_t* seg, int K, long N, int k, int32_t* idx_out, float* d2_out,
+                         int32_t* count_out, NnWork* items, int32_t* repeat, const NnGridWs& g) {
+  int rc = launch_normals_items(stream, seg, K, N, items, repeat);
+  if (rc) return rc;
+  rc = launch_nn_grid_build(stream, P, seg, K, N, g);
+  if (rc) return rc;
+  KnnParams a = knn_params(P, P, items, g, k, 0.f, true);
+  a.idx_out = idx_out; a.d2_out = d2_out; a.count_out = count_out;
+  return knn_launch(stream, KNN_ROWS_OUT, a, (int)nn_max_items(N, K));
+}
+
 __global__ void knn_whole_segment_kernel(int32_t* __restrict__ seg, int n) {
   if (blockIdx.x == 0 && threadIdx.x == 0) { seg[0] = 0; seg[1] = n; }
 }
