@@ -45,7 +45,8 @@ extern "C" {
  * estimation and the outlier removal on it); rap_fps_grid_workspace_bytes, rap_farthest_point_sampling_grid and rap_fps_grid_params
  * (farthest point sampling over a bucket index: the index lists of rap_farthest_point_sampling, less work per pick);
  * rap_orient_normals_workspace_bytes and rap_orient_normals (a consistent orientation of existing normals over the minimum spanning
- * forest of the k-NN graph). */
+ * forest of the k-NN graph); rap_scene_refine_workspace_bytes and rap_scene_refine (joint multi-view point-to-plane refinement of the
+ * poses of a registered scene). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -527,6 +528,60 @@ int rap_icp_plane_grid(const float* X, const int32_t* x_seg, const float* Y, con
                        int64_t n_x_points, int64_t n_y_points, const float* init_R, const float* init_T, int32_t max_iterations,
                        float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations,
                        uint8_t* converged, float* Xt, void* ws, size_t ws_bytes, void* stream);
+
+/* Joint multi-view refinement of registered scenes: ONE point-to-plane Gauss-Newton problem per scene over the poses of all its views,
+ * every directed edge (source view a, target view b) contributing as a rap_icp_plane step would.  Unpinned: the reference has no
+ * counterpart (it runs pytorch3d's pairwise ICP only); the yardstick is the fp64 restatement of this comment in
+ * tests/scene_refine_oracle.py.
+ * Inputs.  P (n_points,3) and normals (n_points,3) fp32, every view in its OWN frame.  view_seg (V,2) int32: (start, len) rows of every
+ * view, clamped to the array on the device as rap_icp's segments are (len <= 0: an empty view); views must not overlap.  scene_seg (S,2)
+ * int32: (first view, number of views), clamped to the view table likewise; every scene owns a contiguous run of the view table and
+ * scenes must not overlap.  edges (E,2) int32: (a, b), directed; an edge is IGNORED (edge_count = 0, edge_rmse = NaN, no contribution)
+ * when a or b is out of range, a == b, the two views belong to different scenes or to no scene or to a scene that is left out (below),
+ * either view is empty, or the row budget (below) is spent.  A duplicate edge counts twice.  fixed (V,) uint8 marks the views whose pose
+ * is not a variable; NULL: the first view of every scene.  A scene without a fixed view is legal (the minimum-norm step below resolves
+ * the gauge).  init_R (V,3,3), init_T (V,3), or both NULL for the identity: the row-vector convention of rap_icp, world = x R_v + T_v.
+ * Per scene, from the fp64 state R_v, T_v = the fp32 init, for it in 0 .. max_iterations-1:
+ *   1. for every live edge e = (a, b), in double: R_e = R_a R_b^T, T_e = (T_a - T_b) R_b^T, both rounded to fp32 (a's rows in b's frame);
+ *      q_i = x_i R_e + T_e in fp32 for every row x_i of view a;  nn(i) = first arg-min over view b's rows of the fp32 direct-difference
+ *      distance, as in rap_icp;  the pairs that count are those with sqrtf(d2_i) <= max_correspondence_distance (<= 0: no gate) whose
+ *      normal n = normals[nn(i)] is finite and not 0;  over them, in double, with y = b's row nn(i):  r = (q - y) . n,  J = [q x n, n],
+ *      A_e = sum J J^T,  b_e = sum J r,  e_e = sum r^2,  n_e = the number of pairs (rap_icp_plane's sums, in b's frame);
+ *   2. n = sum_e n_e;  n == 0: rmse = inf, converged = 0, stop with the poses (and the iteration count) the scene had;
+ *      rmse = sqrt(sum_e e_e / n): the residual of the poses that ENTERED this iteration, one update behind the returned poses;
+ *   3. the system of the scene over world-frame twists xi_v = (omega_v, tau_v), which act on world points as p <- p dR^T + tau:
+ *      with M_b = [[R_b, 0], [-R_b [T_b]x, R_b]] (column form, xi_local = M_b xi_world):  A_w = M_b^T A_e M_b,  g_w = M_b^T b_e;
+ *      in ascending edge order A_w is added to the blocks (a,a) and (b,b) of H and subtracted from (a,b) and (b,a), g_w is added to
+ *      g[a] and subtracted from g[b] (the residual depends on the relative pose only: J_b = -J_a).  Equivalently the sums over
+ *      J_w = [p_w x n_w, n_w] with p_w = q R_b + T_b, n_w = n R_b.  The rows and columns of fixed views are struck;
+ *   4. xi = -H^+ g, H^+ without the eigenvalues <= 1e-12 lambda_max (fp64 cyclic Jacobi): the minimum-norm step.  A view without a live
+ *      edge does not move, a planar scene does not slide in its plane, a scene without a fixed view does not drift;
+ *   5. every free view: dR = exp([omega_v]x),  R_v <- R_v dR^T,  T_v <- T_v dR^T + tau_v, kept in fp64 between iterations; the outputs
+ *      R, T are always the fp32 rounding of the state.  A view whose step is exactly zero, a fixed view, and a view outside every
+ *      (admitted) scene keep the fp32 init bit for bit;
+ *   6. iterations = it + 1;  rel = 1 in the first iteration, else (prev - rmse) / prev;  prev == 0 or rel <= relative_rmse_thr:
+ *      converged = 1, stop.  Every scene stops on its own.
+ * Outputs: R (V,3,3), T (V,3) fp32; rmse (S,) fp32, iterations (S,) int32, converged (S,) uint8; edge_rmse (E,) fp32 and edge_count (E,)
+ * int32, or NULL: sqrt(e_e / n_e) (NaN where n_e == 0) and n_e of the LAST iteration the edge's scene ran.
+ * Limits.  max_views in 2 .. 16: it sizes the solve (96 unknowns; H and its eigenvectors, two 96 x 96 fp64 matrices, live in the 160 KB
+ * LDS of a compute unit).  A scene with more views than max_views is LEFT OUT: rmse = NaN, iterations = 0, converged = 0, poses = init.
+ * row_budget: the caller's upper bound on the rows of the source views summed over the live edges; the work list holds
+ * row_budget / 256 + E + 1 items; edges are admitted in ascending order while sum len(a) <= row_budget, all of an edge or none, and an
+ * edge that does not fit is ignored (later, shorter ones are still tried).  V, E <= 65535; n_points <= (2^31 - 1) / 8 as in every call on
+ * the grid index.  RAP_ERR_INVALID: NULL P, normals, view_seg, scene_seg, edges, R, T, rmse, iterations or converged; sizes that are not
+ * positive or out of range; NaN thresholds; max_iterations <= 0.  RAP_ERR_WORKSPACE: ws NULL or ws_bytes below
+ * rap_scene_refine_workspace_bytes(...) (host arithmetic; 0 for arguments the call would refuse).  Both before any launch, with nothing
+ * written.
+ * Execution: 10 + 4 * max_iterations launches enqueued up front (set-up, the grid index of rap_icp_grid with one grid per view, then per
+ * iteration edge poses, the query, the per-edge sums and one block per scene); no host read, no allocation, no floating-point
+ * atomics; the same bits from call to call whatever the workspace held; a scene's bits do not depend on the rest of the batch (the
+ * order of a scene's edges among themselves does: it is the order of the sums of step 3); the call can be captured into a graph. */
+size_t rap_scene_refine_workspace_bytes(int64_t n_points, int32_t V, int32_t S, int32_t E, int64_t row_budget, int32_t max_views);
+int rap_scene_refine(const float* P, const float* normals, const int32_t* view_seg, int32_t V, int64_t n_points, const int32_t* scene_seg,
+                     int32_t S, const int32_t* edges, int32_t E, int64_t row_budget, int32_t max_views, const uint8_t* fixed,
+                     const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
+                     float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged,
+                     float* edge_rmse, int32_t* edge_count, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- MiniSpinNet local feature extractor (the step before the path) ----
  * Replaces MiniSpinNet.forward (reference dataset_process/utils/spinnet/patch_embedder.py:49-183 with patchnet.py:16-84 and

@@ -14,6 +14,7 @@ from .metrics import compute_part_acc
 from .modeling import RectifiedPointFlow
 from .procrustes import fit_transformations, rigidify_prediction_with_procrustes, solve_procrustes
 from .sampler import euler_step, flow_sampler, get_sampler
+from .scene import SceneRefinement, refine_registration, refine_scene_packed
 from .submaps import (calculate_point_cloud_overlap_ratio_fast, check_submap_validity, create_submap_from_frames, deskew_packed, deskewing,
                       fuse_frames_packed, groups_connected, submap_overlap_matrix)
 from .selection import (average_trajectory_rigidity_rmse, compute_overlap_ratio, compute_rigidity_rmse,
@@ -26,4 +27,4 @@ __all__ = ["PointCloudDiT", "RectifiedPointFlow", "fit_transformations", "rigidi
            "align_anchor", "compute_transform_errors_icp", "compute_part_acc", "nearest_neighbors_packed", "k_nearest_neighbors_packed",
            "estimate_normals_packed", "estimate_point_normals", "orient_normals_packed", "deskew_packed", "fuse_frames_packed", "submap_overlap_matrix",
            "groups_connected", "deskewing", "create_submap_from_frames", "calculate_point_cloud_overlap_ratio_fast",
-           "check_submap_validity"]
+           "check_submap_validity", "refine_scene_packed", "refine_registration", "SceneRefinement"]

@@ -35,6 +35,9 @@ def main():
     ap.add_argument("--voxel", type=float, default=0.004, help="voxel size of the down-sampling (normalised units)")
     ap.add_argument("--fps-search", default="brute", choices=["brute", "grid"],
                     help="farthest point sampling: every pick re-reads the cloud, or the same picks over a bucket index (DESIGN.md 7.7)")
+    ap.add_argument("--refine", action="store_true",
+                    help="polish the selected poses on the views' own clouds before they are written: joint multi-view point-to-plane "
+                         "refinement, every sample one scene (rap_amd.refine_registration, DESIGN.md 7.9)")
     ap.add_argument("--out", default="/tmp/rap_demo")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -100,19 +103,28 @@ def main():
                                                              torch.stack([g["t"] for g in out["generations"]]), inp["cu_seqlens"])
     sync(); t_overlap = time.perf_counter() - t0
 
+    # 3b. optional: joint refinement of the selected poses on the condition clouds (the first part of every sample stays fixed)
+    rot_sel, trans_sel, extra = out["rotations_selected"], out["translations_selected"], {}
+    if args.refine:
+        t0 = time.perf_counter()
+        rot_sel, trans_sel, refine_rmse = rap_amd.refine_registration(data["pointclouds"], data["points_per_part"], rot_sel.to(dev), trans_sel.to(dev),
+                                                                      cu_seqlens_batch=data["cu_seqlens"],
+                                                                      max_correspondence_distance=0.05)
+        sync()
+        extra = {"refine_seconds": time.perf_counter() - t0, "refine_rmse": refine_rmse.cpu().tolist()}
+
     # 4. transform files of the rigidity-selected generation (evaluator.py:383-490); synthetic GT = identity
     gt = {"rotations": torch.eye(3).expand(B, P, 3, 3).contiguous(), "translations": torch.zeros(B, P, 3), "scales": inp["scales"],
           "points_per_part": inp["points_per_part"]}
     t0 = time.perf_counter()
-    paths = save_transformation_files(gt, args.out, "synthetic", list(range(B)), "selected", out["rotations_selected"],
-                                      out["translations_selected"])
+    paths = save_transformation_files(gt, args.out, "synthetic", list(range(B)), "selected", rot_sel, trans_sel)
     t_files = time.perf_counter() - t0
     print(json.dumps({"pairs": B, "views": P, "points_per_view": args.points, "generations": args.generations, "dtype": args.dtype,
                       "fps_search": args.fps_search, "raw_points": raw_points, "points_after_voxel_downsampling": kept_points,
                       "seconds": {"voxel_downsample_and_fps": t_pre, "miniSpinNet_features": t_feat, "sample_generations_incl_rigidity_selection": t_sample,
                                   "overlap_ratio_selection": t_overlap, "transform_files": t_files},
                       "best_by_rigidity": out["best_gen_indices"].tolist(), "best_by_overlap": best_ov.tolist(),
-                      "rigidity_rmse_m": out["rigidity_rmse"].cpu().tolist(), "files_written": len(paths), "out_dir": args.out}))
+                      "rigidity_rmse_m": out["rigidity_rmse"].cpu().tolist(), "files_written": len(paths), "out_dir": args.out, **extra}))
 
 
 if __name__ == "__main__":
