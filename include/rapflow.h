@@ -46,7 +46,8 @@ extern "C" {
  * (farthest point sampling over a bucket index: the index lists of rap_farthest_point_sampling, less work per pick);
  * rap_orient_normals_workspace_bytes and rap_orient_normals (a consistent orientation of existing normals over the minimum spanning
  * forest of the k-NN graph); rap_scene_refine_workspace_bytes and rap_scene_refine (joint multi-view point-to-plane refinement of the
- * poses of a registered scene). */
+ * poses of a registered scene); rap_icp_plane_robust, rap_icp_plane_grid_robust and rap_scene_refine_robust with their
+ * *_workspace_bytes queries, and the RAP_LOSS_* codes (the point-to-plane estimators under a robust loss). */
 #define RAPFLOW_ABI_VERSION 6
 
 /* return codes of every int-returning entry point */
@@ -582,6 +583,51 @@ int rap_scene_refine(const float* P, const float* normals, const int32_t* view_s
                      const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
                      float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged,
                      float* edge_rmse, int32_t* edge_count, void* ws, size_t ws_bytes, void* stream);
+
+/* Robust losses for the three point-to-plane calls above.  loss: one of the codes below; loss_scale: its scale k > 0, in the units of the
+ * clouds.  Which pairs count is UNCHANGED: the neighbour, the gate and the usable-normal rule are the sibling's.  For every counted pair,
+ * in double, from the residual r the sibling forms:
+ *   RAP_LOSS_NONE    w = 1                                    rho = r^2 / 2
+ *   RAP_LOSS_HUBER   w = 1 if |r| <= k, else k / |r|          rho = r^2 / 2 if |r| <= k, else k (|r| - k / 2)
+ *   RAP_LOSS_CAUCHY  w = 1 / (1 + (r/k)^2)                    rho = (k^2 / 2) log1p((r/k)^2)
+ *   RAP_LOSS_TUKEY   w = (1 - (r/k)^2)^2 if |r| <= k, else 0  rho = (k^2 / 6) (1 - (1 - (r/k)^2)^3) if |r| <= k, else k^2 / 6
+ * and the sums of the sibling become (iteratively reweighted Gauss-Newton)
+ *   A = sum w J J^T,  b = sum w J r,  e = sum 2 rho,  W = sum w,  n = the number of counted pairs (zero-weight pairs included).
+ * rmse = sqrt(e / n) (the plain rmse for RAP_LOSS_NONE); rap_scene_refine_robust's edge_rmse = sqrt(e_e / n_e) likewise, edge_count
+ * stays n_e, and step 1's A_e, b_e, e_e are the weighted sums.  The stopping rule acts on this rmse.  W == 0 (every weight zero) is
+ * treated as n == 0: rmse = inf, converged = 0, stop with the pose(s) and the iteration count the problem or scene had.  Everything else
+ * is the sibling's algorithm word for word.  With RAP_LOSS_NONE loss_scale is ignored and the call returns the bits of its sibling.
+ * weights (n_x_points,) fp32 or NULL (the two pairwise calls): the weight every source row had in the LAST iteration its problem ran, the
+ * one of the pose that entered that iteration; 0 for a row that was gated out or matched a row without a usable normal, and for the
+ * rows of a problem that ran no iteration; rows outside every segment are not written.
+ * RAP_ERR_INVALID, before any launch and with nothing written: a loss code outside 0 .. 3; loss != RAP_LOSS_NONE with a loss_scale that
+ * is not finite and positive; whatever the sibling refuses.  ws >= the call's own *_workspace_bytes (the sibling's arguments; host
+ * arithmetic, 0 for arguments the call would refuse; the partial sums also carry W, so it is larger than the sibling's).  The execution
+ * properties are the siblings': the caller's stream, no host read, no allocation, no floating-point atomics, the same bits from call
+ * to call whatever the workspace held, a problem's or scene's bits independent of the rest of the batch, capturable into a graph
+ * (one launch more than the sibling where weights is given). */
+#define RAP_LOSS_NONE 0
+#define RAP_LOSS_HUBER 1
+#define RAP_LOSS_CAUCHY 2
+#define RAP_LOSS_TUKEY 3
+size_t rap_icp_plane_robust_workspace_bytes(int64_t n_x_points, int32_t K);
+int rap_icp_plane_robust(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals, int32_t K,
+                         int64_t n_x_points, int64_t n_y_points, const float* init_R, const float* init_T, int32_t max_iterations,
+                         float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations,
+                         uint8_t* converged, float* Xt, int32_t loss, float loss_scale, float* weights, void* ws, size_t ws_bytes,
+                         void* stream);
+size_t rap_icp_plane_grid_robust_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K);
+int rap_icp_plane_grid_robust(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals, int32_t K,
+                              int64_t n_x_points, int64_t n_y_points, const float* init_R, const float* init_T, int32_t max_iterations,
+                              float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse,
+                              int32_t* iterations, uint8_t* converged, float* Xt, int32_t loss, float loss_scale, float* weights, void* ws,
+                              size_t ws_bytes, void* stream);
+size_t rap_scene_refine_robust_workspace_bytes(int64_t n_points, int32_t V, int32_t S, int32_t E, int64_t row_budget, int32_t max_views);
+int rap_scene_refine_robust(const float* P, const float* normals, const int32_t* view_seg, int32_t V, int64_t n_points,
+                            const int32_t* scene_seg, int32_t S, const int32_t* edges, int32_t E, int64_t row_budget, int32_t max_views,
+                            const uint8_t* fixed, const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
+                            float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged,
+                            float* edge_rmse, int32_t* edge_count, int32_t loss, float loss_scale, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- MiniSpinNet local feature extractor (the step before the path) ----
  * Replaces MiniSpinNet.forward (reference dataset_process/utils/spinnet/patch_embedder.py:49-183 with patchnet.py:16-84 and

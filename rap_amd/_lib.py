@@ -111,6 +111,15 @@ SIGNATURES = {
     "rap_scene_refine_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int64, c_int32]),
     "rap_scene_refine": (c_int32, [_P, _P, _P, c_int32, c_int64, _P, c_int32, _P, c_int32, c_int64, c_int32, _P, _P, _P, c_int32, c_float,
                                    c_float, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "rap_icp_plane_robust_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "rap_icp_plane_robust": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, c_int32, c_float, c_float, _P, _P, _P, _P, _P, _P,
+                                       c_int32, c_float, _P, _P, c_size_t, _P]),
+    "rap_icp_plane_grid_robust_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "rap_icp_plane_grid_robust": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int64, _P, _P, c_int32, c_float, c_float, _P, _P, _P, _P, _P,
+                                            _P, c_int32, c_float, _P, _P, c_size_t, _P]),
+    "rap_scene_refine_robust_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int64, c_int32]),
+    "rap_scene_refine_robust": (c_int32, [_P, _P, _P, c_int32, c_int64, _P, c_int32, _P, c_int32, c_int64, c_int32, _P, _P, _P, c_int32, c_float,
+                                          c_float, _P, _P, _P, _P, _P, _P, _P, c_int32, c_float, _P, c_size_t, _P]),
     "rap_voxel_bounds": (c_int32, [_P, c_int64, c_float, _P, _P, _P]),
     "rap_voxel_table_slots": (c_int64, [_P]),
     "rap_voxel_workspace_bytes": (c_size_t, [_P]),

@@ -778,11 +778,12 @@ extern "C" int rap_transform_errors_direct(const float* R_gt, const float* t_gt,
 #define RAP_GRID_MAX_K 65535      // the build kernels take the problem from blockIdx.y
 struct IcpWs { NnWork* items; void* partials; void* ranges; double* prev; int32_t* done; double* state; size_t total; };
 // plane: the larger partials of the point-to-plane estimator, and its fp64 pose after everything else
-static IcpWs carve_icp(int64_t n, int K, bool plane, char* basep) {
+// robust: the partials of the robust point-to-plane calls, which also carry the sum of the weights
+static IcpWs carve_icp(int64_t n, int K, bool plane, char* basep, bool robust = false) {
   IcpWs w; Carver c(basep);
   const size_t max_items = nn_max_items((long)n, K);
   w.items = (NnWork*)c.take(max_items * sizeof(NnWork));
-  w.partials = c.take(max_items * (plane ? icp_plane_partial_bytes() : icp_partial_bytes()));
+  w.partials = c.take(max_items * (robust ? icp_plane_robust_partial_bytes() : plane ? icp_plane_partial_bytes() : icp_partial_bytes()));
   w.ranges = c.take((size_t)K * 16);
   w.prev = (double*)c.take((size_t)K * 8);
   w.done = (int32_t*)c.take((size_t)K * 4);
@@ -790,11 +791,11 @@ static IcpWs carve_icp(int64_t n, int K, bool plane, char* basep) {
   w.total = c.total();
   return w;
 }
-static size_t icp_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int K, bool plane, bool grid) {
+static size_t icp_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int K, bool plane, bool grid, bool robust = false) {
   if (n_x_points <= 0 || K <= 0 || (grid && n_y_points <= 0)) return 0;
   Carver c(nullptr);
   if (grid) nn_grid_carve(c, (long)n_y_points, K);
-  return carve_icp(n_x_points, K, plane, nullptr).total + c.total();
+  return carve_icp(n_x_points, K, plane, nullptr, robust).total + c.total();
 }
 // c: the entry point's arguments, with the caller's max_correspondence_distance in gate; the workspace pointers are filled in here
 static int icp_entry(IcpCall c, bool plane, bool grid, void* ws, size_t ws_bytes, void* stream) {
@@ -802,8 +803,11 @@ static int icp_entry(IcpCall c, bool plane, bool grid, void* ws, size_t ws_bytes
       c.K <= 0 || (grid && c.K > RAP_GRID_MAX_K) || c.max_iterations <= 0 || c.NX <= 0 || c.NY <= 0 || c.NX > 0x7fffffffLL / 8 ||
       c.NY > 0x7fffffffLL / 8 || c.relative_rmse_thr != c.relative_rmse_thr || c.gate != c.gate)
     return RAP_ERR_INVALID;
+  if (c.robust && (c.loss < RAP_LOSS_NONE || c.loss > RAP_LOSS_TUKEY ||
+                   (c.loss != RAP_LOSS_NONE && !(c.loss_scale > 0.f && c.loss_scale < __builtin_inff()))))
+    return RAP_ERR_INVALID;
   if (!ws) return RAP_ERR_WORKSPACE;
-  const IcpWs w = carve_icp(c.NX, c.K, plane, (char*)ws);
+  const IcpWs w = carve_icp(c.NX, c.K, plane, (char*)ws, c.robust != 0);
   Carver gc((char*)ws + w.total);
   NnGridWs g = {};
   if (grid) g = nn_grid_carve(gc, c.NY, c.K);
@@ -851,6 +855,33 @@ extern "C" int rap_icp_plane_grid(const float* X, const int32_t* x_seg, const fl
                                   int32_t* iterations, uint8_t* converged, float* Xt, void* ws, size_t ws_bytes, void* stream) {
   const IcpCall c = {X, x_seg, Y, y_seg, Y_normals, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
                      max_correspondence_distance, R, T, rmse, iterations, converged, Xt};
+  return icp_entry(c, true, true, ws, ws_bytes, stream);
+}
+// the robust twins (robust_loss.h): the siblings' calls with IcpCall::robust set
+extern "C" size_t rap_icp_plane_robust_workspace_bytes(int64_t n_x_points, int32_t K) {
+  return icp_workspace_bytes(n_x_points, 0, K, true, false, true);
+}
+extern "C" size_t rap_icp_plane_grid_robust_workspace_bytes(int64_t n_x_points, int64_t n_y_points, int32_t K) {
+  return icp_workspace_bytes(n_x_points, n_y_points, K, true, true, true);
+}
+extern "C" int rap_icp_plane_robust(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals,
+                                    int32_t K, int64_t NX, int64_t NY, const float* init_R, const float* init_T, int32_t max_iterations,
+                                    float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse,
+                                    int32_t* iterations, uint8_t* converged, float* Xt, int32_t loss, float loss_scale, float* weights,
+                                    void* ws, size_t ws_bytes, void* stream) {
+  IcpCall c = {X, x_seg, Y, y_seg, Y_normals, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
+               max_correspondence_distance, R, T, rmse, iterations, converged, Xt};
+  c.robust = 1; c.loss = loss; c.loss_scale = loss_scale; c.weights = weights;
+  return icp_entry(c, true, false, ws, ws_bytes, stream);
+}
+extern "C" int rap_icp_plane_grid_robust(const float* X, const int32_t* x_seg, const float* Y, const int32_t* y_seg, const float* Y_normals,
+                                         int32_t K, int64_t NX, int64_t NY, const float* init_R, const float* init_T, int32_t max_iterations,
+                                         float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse,
+                                         int32_t* iterations, uint8_t* converged, float* Xt, int32_t loss, float loss_scale, float* weights,
+                                         void* ws, size_t ws_bytes, void* stream) {
+  IcpCall c = {X, x_seg, Y, y_seg, Y_normals, K, (long)NX, (long)NY, init_R, init_T, max_iterations, relative_rmse_thr,
+               max_correspondence_distance, R, T, rmse, iterations, converged, Xt};
+  c.robust = 1; c.loss = loss; c.loss_scale = loss_scale; c.weights = weights;
   return icp_entry(c, true, true, ws, ws_bytes, stream);
 }
 

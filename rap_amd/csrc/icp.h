@@ -4,6 +4,7 @@
 // themselves (nn_d2, the segment clamp, the tile) are nn_tile.h's.
 #pragma once
 #include "nn_tile.h"
+#include "robust_loss.h"
 
 #define ICP_TILE NN_TILE
 #define ICP_NMOM 17      // sum x (3), sum y (3), sum x_i y_j (9), sum |x|^2, sum |y|^2
@@ -75,7 +76,10 @@ __device__ __forceinline__ void icp_moments(bool active, int besti, float best, 
 
 // ---- point-to-plane (icp_plane.hip; the grid path in nn_grid.hip) ----
 #define ICP_PLANE_NMOM 28      // upper triangle of A = sum J J^T, row by row (21), b = sum J r (6), e = sum r^2
-struct IcpPlanePartial { double m[ICP_PLANE_NMOM]; long long count; };
+struct IcpPlanePartial { static constexpr int NRED = ICP_PLANE_NMOM; double m[ICP_PLANE_NMOM]; long long count; };
+// ... of the robust calls: A = sum w J J^T, b = sum w J r, e = sum 2 rho, and behind them W = sum w (robust_loss.h)
+#define ICP_PLANE_WMOM (ICP_PLANE_NMOM + 1)
+struct IcpPlaneWPartial { static constexpr int NRED = ICP_PLANE_WMOM; double m[ICP_PLANE_WMOM]; long long count; };
 
 // the neighbour's normal counts when every component is finite and it is not the zero vector ("no estimate", normals.hip)
 __device__ __forceinline__ bool icp_normal_ok(float nx, float ny, float nz) {
@@ -94,10 +98,17 @@ __device__ __forceinline__ void icp_plane_put(double v, double* __restrict__ row
 // the search saw, fp32), y = Y[y_start + besti] its neighbour, n = Yn[y_start + besti] the neighbour's normal.  In double:
 // r = (p - y) . n, J = [p x n, n]; the gated pairs with a usable normal are summed per wave, then over the four waves in a fixed order.
 // Every thread of the block calls it.  Both search paths end here, so they return the same bits.
+// Partial = IcpPlaneWPartial (the robust calls): every pair enters with its weight w(r) of loss LOSS at scale k, e sums 2 rho(r), W = sum w
+// is carried as a 29th moment, and an active lane stores its weight (0 for a pair that does not count) to wrow[its row] where wrow is
+// given.  LOSS none there multiplies nothing and sums the statements of the plain partial: the same bits.
+template <int LOSS, class Partial>
 __device__ __forceinline__ void icp_plane_moments(bool active, int besti, float best, float gate, float px, float py, float pz,
                                                   const float* __restrict__ Y, const float* __restrict__ Yn, int y_start,
-                                                  double (*red_m)[ICP_PLANE_NMOM], int* red_n, IcpPlanePartial* __restrict__ out) {
+                                                  double (*red_m)[Partial::NRED], int* red_n, Partial* __restrict__ out, double k = 0.0,
+                                                  float* __restrict__ wrow = nullptr, size_t qi = 0) {
+  constexpr bool weighted = Partial::NRED == ICP_PLANE_WMOM;
   double J[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, r = 0.0;
+  double wt = 0.0, e = 0.0;
   int n = 0;
   if (active && besti >= 0 && (!(gate > 0.f) || sqrtf(best) <= gate)) {
     const size_t ti = (size_t)y_start + besti;
@@ -112,26 +123,48 @@ __device__ __forceinline__ void icp_plane_moments(bool active, int besti, float 
       J[2] = p[0] * nv[1] - p[1] * nv[0];
       J[3] = nv[0]; J[4] = nv[1]; J[5] = nv[2];
       n = 1;
+      if (weighted) {
+        wt = 1.0;
+        if (LOSS != RAP_LOSS_NONE) {
+          double rho;
+          rap_robust<LOSS>(r, k, wt, rho);
+          e = 2.0 * rho;
+        }
+      }
     }
   }
+  if (weighted && wrow && active) wrow[qi] = (float)wt;
+  double Jw[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) Jw[i] = weighted && LOSS != RAP_LOSS_NONE ? wt * J[i] : J[i];
   double* row = red_m[threadIdx.x >> 6];
   int at = 0;
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
 #pragma unroll
-    for (int j = i; j < 6; ++j) icp_plane_put(J[i] * J[j], row, at++);
+    for (int j = i; j < 6; ++j) icp_plane_put(Jw[i] * J[j], row, at++);
   }
 #pragma unroll
-  for (int i = 0; i < 6; ++i) icp_plane_put(J[i] * r, row, 21 + i);
-  icp_plane_put(r * r, row, 27);
+  for (int i = 0; i < 6; ++i) icp_plane_put(Jw[i] * r, row, 21 + i);
+  icp_plane_put(weighted && LOSS != RAP_LOSS_NONE ? e : r * r, row, 27);
+  if (weighted) icp_plane_put(wt, row, ICP_PLANE_NMOM);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
   if ((threadIdx.x & 63) == 0) red_n[threadIdx.x >> 6] = n;
   __syncthreads();
-  if (threadIdx.x < ICP_PLANE_NMOM)
+  if (threadIdx.x < Partial::NRED)
     out->m[threadIdx.x] = (red_m[0][threadIdx.x] + red_m[1][threadIdx.x]) + (red_m[2][threadIdx.x] + red_m[3][threadIdx.x]);
-  if (threadIdx.x == ICP_PLANE_NMOM) out->count = (long long)(red_n[0] + red_n[1] + red_n[2] + red_n[3]);
+  if (threadIdx.x == Partial::NRED) out->count = (long long)(red_n[0] + red_n[1] + red_n[2] + red_n[3]);
 }
+
+// F<loss>(args...) for the run-time loss code (checked by the entry point: 0 .. 3)
+#define RAP_LOSS_DISPATCH(loss, F, ...)                       \
+  switch (loss) {                                             \
+    case RAP_LOSS_HUBER: F<RAP_LOSS_HUBER>(__VA_ARGS__); break;   \
+    case RAP_LOSS_CAUCHY: F<RAP_LOSS_CAUCHY>(__VA_ARGS__); break; \
+    case RAP_LOSS_TUKEY: F<RAP_LOSS_TUKEY>(__VA_ARGS__); break;   \
+    default: F<RAP_LOSS_NONE>(__VA_ARGS__); break;                \
+  }
 
 // A finish wave (one per problem) starts here: declares m[NMOM] = the item partials of range r added lane-strided in item order, then
 // over the wave, and n = the number of pairs.  A macro: as a function (the range by value or as two ints, m by reference or by pointer)

@@ -17,6 +17,9 @@
 //                                the iteration (so the reported rmse is one update behind the returned R, T), the 6 x 6 solve, the update,
 //                                the stopping rule
 //   icp_apply_kernel (icp.hip)   optional Xt
+// The robust calls (rap_icp_plane_robust; IcpCall::robust) run icp_plane_query_robust_kernel<loss> and icp_plane_finish_robust_kernel in
+// their place: the same statements on weighted sums (robust_loss.h, the epilogue in icp.h), a partial that also carries W = sum w, and
+// icp_plane_weights_zero_kernel once before the loop where per-row weights are asked for.
 // No host read, no allocation, no floating-point atomics; a problem's bits depend on its own segments only.
 #include "icp.h"
 #include "kabsch.h"
@@ -24,6 +27,7 @@
 #define ICP_PLANE_RCOND 1e-12
 
 size_t icp_plane_partial_bytes() { return sizeof(IcpPlanePartial); }
+size_t icp_plane_robust_partial_bytes() { return sizeof(IcpPlaneWPartial); }
 
 __global__ __launch_bounds__(256) void icp_plane_state_kernel(const float* __restrict__ R, const float* __restrict__ T, int K,
                                                               double* __restrict__ state) {
@@ -45,65 +49,77 @@ __global__ __launch_bounds__(ICP_TILE) void icp_plane_query_kernel(const float* 
   __shared__ int red_n[ICP_TILE / 64];
   ICP_QUERY_BEGIN(X, items, R, T, done);
   NN_TILE_ARGMIN(tile, w.y_len, px, py, pz, [&](int k, float4& c) { nn_row(Y, (size_t)w.y_start + k, c); }, best, besti);
-  icp_plane_moments(active, besti, best, gate, px, py, pz, Y, Yn, w.y_start, red_m, red_n, partials + blockIdx.x);
+  icp_plane_moments<RAP_LOSS_NONE>(active, besti, best, gate, px, py, pz, Y, Yn, w.y_start, red_m, red_n, partials + blockIdx.x);
 }
 
-__global__ __launch_bounds__(64) void icp_plane_finish_kernel(const IcpPlanePartial* __restrict__ partials, const IcpRange* __restrict__ ranges,
-                                                              int it, double rel_thr, double* __restrict__ state, float* __restrict__ R_out,
-                                                              float* __restrict__ T_out, float* __restrict__ rmse_out,
-                                                              int32_t* __restrict__ iterations, uint8_t* __restrict__ converged,
-                                                              double* __restrict__ prev, int32_t* __restrict__ done) {
-  const int k = blockIdx.x;
-  if (done[k]) return;
-  const IcpRange r = ranges[k];
-  ICP_SUM_PARTIALS(ICP_PLANE_NMOM, IcpPlanePartial, partials, r, m, n);
-  if (threadIdx.x != 0) return;
-  if (n == 0) {                                      // no gated pair with a usable normal: stop with the R, T it had
-    rmse_out[k] = __builtin_inff();
-    done[k] = 1;
-    return;
-  }
-  const double rmse = sqrt(fmax(m[27] / (double)n, 0.0));
-  double A[6][6], b[6], xi[6];
-  int at = 0;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-#pragma unroll
-    for (int j = i; j < 6; ++j) { A[i][j] = m[at]; A[j][i] = m[at]; ++at; }
-    b[i] = m[21 + i];
-  }
-  rap_pinv6_step(A, b, ICP_PLANE_RCOND, xi);
-  double dR[3][3], S[12];
-  rap_rodrigues(xi, dR);
-  double* st = state + (size_t)k * 12;
-  // rows of [R; T] times dR^T: out[i][j] = sum_l in[i][l] dR[j][l]
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const double a0 = st[3 * i + 0], a1 = st[3 * i + 1], a2 = st[3 * i + 2];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) S[3 * i + j] = a0 * dR[j][0] + a1 * dR[j][1] + a2 * dR[j][2] + (i == 3 ? xi[3 + j] : 0.0);
-  }
-#pragma unroll
-  for (int i = 0; i < 12; ++i) st[i] = S[i];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R_out[(size_t)k * 9 + i] = (float)S[i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) T_out[(size_t)k * 3 + i] = (float)S[9 + i];
-  icp_finish_end(k, it, rmse, rel_thr, rmse_out, iterations, converged, prev, done);
+// the robust call's query: the same search, the weighted epilogue, the optional per-row weights
+template <int LOSS>
+__global__ __launch_bounds__(ICP_TILE) void icp_plane_query_robust_kernel(const float* __restrict__ X, const float* __restrict__ Y,
+                                                                          const float* __restrict__ Yn, const NnWork* __restrict__ items,
+                                                                          const float* __restrict__ R, const float* __restrict__ T,
+                                                                          const int32_t* __restrict__ done, float gate, double scale,
+                                                                          float* __restrict__ weights, IcpPlaneWPartial* __restrict__ partials) {
+  __shared__ float4 tile[ICP_TILE];
+  __shared__ double red_m[ICP_TILE / 64][ICP_PLANE_WMOM];
+  __shared__ int red_n[ICP_TILE / 64];
+  ICP_QUERY_BEGIN(X, items, R, T, done);
+  NN_TILE_ARGMIN(tile, w.y_len, px, py, pz, [&](int k, float4& c) { nn_row(Y, (size_t)w.y_start + k, c); }, best, besti);
+  icp_plane_moments<LOSS>(active, besti, best, gate, px, py, pz, Y, Yn, w.y_start, red_m, red_n, partials + blockIdx.x, scale, weights, qi);
 }
+
+// weights = 0 on every row of every problem that has items (a problem that runs no iteration keeps that)
+__global__ __launch_bounds__(ICP_TILE) void icp_plane_weights_zero_kernel(const NnWork* __restrict__ items, float* __restrict__ weights) {
+  const NnWork w = items[blockIdx.x];
+  const int q = w.q0 + threadIdx.x;
+  if (q < w.x_len) weights[(size_t)w.x_start + q] = 0.f;
+}
+
+#define FINISH_KERNEL icp_plane_finish_kernel
+#define FINISH_PARTIAL IcpPlanePartial
+#include "icp_plane_finish.inc"
+#undef FINISH_KERNEL
+#undef FINISH_PARTIAL
+#define FINISH_KERNEL icp_plane_finish_robust_kernel
+#define FINISH_PARTIAL IcpPlaneWPartial
+#include "icp_plane_finish.inc"
+#undef FINISH_KERNEL
+#undef FINISH_PARTIAL
 
 int launch_icp_plane_state(hipStream_t stream, const IcpCall& c) {
   hipLaunchKernelGGL(icp_plane_state_kernel, dim3((c.K + 255) / 256), dim3(256), 0, stream, (const float*)c.R, (const float*)c.T, c.K, c.state);
   RAP_LAUNCH_CHECK();
+  if (c.robust && c.weights) {
+    hipLaunchKernelGGL(icp_plane_weights_zero_kernel, dim3((unsigned)nn_max_items(c.NX, c.K)), dim3(ICP_TILE), 0, stream,
+                       (const NnWork*)c.items, c.weights);
+    RAP_LAUNCH_CHECK();
+  }
   return RAP_OK;
 }
+template <int LOSS>
+static void icp_plane_query_robust(hipStream_t stream, const IcpCall& c) {
+  hipLaunchKernelGGL(icp_plane_query_robust_kernel<LOSS>, dim3((unsigned)nn_max_items(c.NX, c.K)), dim3(ICP_TILE), 0, stream, c.X, c.Y,
+                     c.Y_normals, (const NnWork*)c.items, (const float*)c.R, (const float*)c.T, (const int32_t*)c.done, c.gate,
+                     (double)c.loss_scale, c.weights, (IcpPlaneWPartial*)c.partials);
+}
 int launch_icp_plane_query(hipStream_t stream, const IcpCall& c) {
+  if (c.robust) {
+    RAP_LOSS_DISPATCH(c.loss, icp_plane_query_robust, stream, c);
+    RAP_LAUNCH_CHECK();
+    return RAP_OK;
+  }
   hipLaunchKernelGGL(icp_plane_query_kernel, dim3((unsigned)nn_max_items(c.NX, c.K)), dim3(ICP_TILE), 0, stream, c.X, c.Y, c.Y_normals,
                      (const NnWork*)c.items, (const float*)c.R, (const float*)c.T, (const int32_t*)c.done, c.gate, (IcpPlanePartial*)c.partials);
   RAP_LAUNCH_CHECK();
   return RAP_OK;
 }
 int launch_icp_plane_finish(hipStream_t stream, const IcpCall& c, int it) {
+  if (c.robust) {
+    hipLaunchKernelGGL(icp_plane_finish_robust_kernel, dim3(c.K), dim3(64), 0, stream, (const IcpPlaneWPartial*)c.partials,
+                       (const IcpRange*)c.ranges, it, (double)c.relative_rmse_thr, c.state, c.R, c.T, c.rmse, c.iterations, c.converged, c.prev,
+                       c.done);
+    RAP_LAUNCH_CHECK();
+    return RAP_OK;
+  }
   hipLaunchKernelGGL(icp_plane_finish_kernel, dim3(c.K), dim3(64), 0, stream, (const IcpPlanePartial*)c.partials, (const IcpRange*)c.ranges, it,
                      (double)c.relative_rmse_thr, c.state, c.R, c.T, c.rmse, c.iterations, c.converged, c.prev, c.done);
   RAP_LAUNCH_CHECK();

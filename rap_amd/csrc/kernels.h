@@ -361,9 +361,13 @@ struct IcpCall {
   float* R; float* T; float* rmse; int32_t* iterations; uint8_t* converged; float* Xt;      // Xt: (NX,3) or null
   NnWork* items; void* partials; void* ranges; double* prev; int32_t* done; double* state;
   const NnGridWs* grid;
+  // the robust point-to-plane calls (rap_icp_plane_robust): partials are then icp_plane_robust_partial_bytes() per item; loss: a
+  // RAP_LOSS_* code, loss_scale: its k; weights: (NX,) or null
+  int robust, loss; float loss_scale; float* weights;
 };
 size_t icp_partial_bytes();
 size_t icp_plane_partial_bytes();
+size_t icp_plane_robust_partial_bytes();
 int launch_icp(hipStream_t stream, const IcpCall& c);
 // what launch_icp enqueues from the other files (a kernel is launched from the file that defines it): the query of one iteration on the
 // grid for either estimator (nn_grid.hip); the fp64 state, the tiled query and the finish of iteration `it` of point-to-plane (icp_plane.hip)

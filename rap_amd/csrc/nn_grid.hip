@@ -299,7 +299,26 @@ __global__ __launch_bounds__(ICP_TILE) void icp_plane_grid_query_kernel(const fl
   float best;
   int besti;
   grid_search(grids[prob], Y, cell_start, sorted, px, py, pz, grid_gate2(gate), best, besti);
-  icp_plane_moments(active, besti, best, gate, px, py, pz, Y, Yn, w.y_start, red_m, red_n, partials + blockIdx.x);
+  icp_plane_moments<RAP_LOSS_NONE>(active, besti, best, gate, px, py, pz, Y, Yn, w.y_start, red_m, red_n, partials + blockIdx.x);
+}
+
+// ... and the robust call's (rap_icp_plane_grid_robust): the weighted epilogue, the optional per-row weights
+template <int LOSS>
+__global__ __launch_bounds__(ICP_TILE) void icp_plane_grid_query_robust_kernel(const float* __restrict__ X, const float* __restrict__ Y,
+                                                                               const float* __restrict__ Yn, const NnWork* __restrict__ items,
+                                                                               const float* __restrict__ R, const float* __restrict__ T,
+                                                                               const int32_t* __restrict__ done, float gate,
+                                                                               const NnGrid* __restrict__ grids,
+                                                                               const unsigned* __restrict__ cell_start,
+                                                                               const float4* __restrict__ sorted, double scale,
+                                                                               float* __restrict__ weights, IcpPlaneWPartial* __restrict__ partials) {
+  __shared__ double red_m[ICP_TILE / 64][ICP_PLANE_WMOM];
+  __shared__ int red_n[ICP_TILE / 64];
+  ICP_QUERY_BEGIN(X, items, R, T, done);
+  float best;
+  int besti;
+  grid_search(grids[prob], Y, cell_start, sorted, px, py, pz, grid_gate2(gate), best, besti);
+  icp_plane_moments<LOSS>(active, besti, best, gate, px, py, pz, Y, Yn, w.y_start, red_m, red_n, partials + blockIdx.x, scale, weights, qi);
 }
 
 // items of 256 queries of one problem, all of a problem or none
@@ -363,10 +382,21 @@ int launch_nn_grid_build(hipStream_t stream, const float* Y, const int32_t* y_se
   return RAP_OK;
 }
 
+template <int LOSS>
+static void icp_plane_grid_query_robust(hipStream_t stream, const IcpCall& c) {
+  const NnGridWs& g = *c.grid;
+  hipLaunchKernelGGL(icp_plane_grid_query_robust_kernel<LOSS>, dim3((unsigned)nn_max_items(c.NX, c.K)), dim3(ICP_TILE), 0, stream, c.X, c.Y,
+                     c.Y_normals, (const NnWork*)c.items, (const float*)c.R, (const float*)c.T, (const int32_t*)c.done, c.gate,
+                     (const NnGrid*)g.grids, (const unsigned*)g.cell_start, (const float4*)g.sorted, (double)c.loss_scale, c.weights,
+                     (IcpPlaneWPartial*)c.partials);
+}
+
 int launch_icp_grid_query(hipStream_t stream, const IcpCall& c) {
   const NnGridWs& g = *c.grid;
   const dim3 grid((unsigned)nn_max_items(c.NX, c.K));
-  if (c.Y_normals)
+  if (c.robust) {
+    RAP_LOSS_DISPATCH(c.loss, icp_plane_grid_query_robust, stream, c);
+  } else if (c.Y_normals)
     hipLaunchKernelGGL(icp_plane_grid_query_kernel, grid, dim3(ICP_TILE), 0, stream, c.X, c.Y, c.Y_normals, (const NnWork*)c.items,
                        (const float*)c.R, (const float*)c.T, (const int32_t*)c.done, c.gate, (const NnGrid*)g.grids,
                        (const unsigned*)g.cell_start, (const float4*)g.sorted, (IcpPlanePartial*)c.partials);

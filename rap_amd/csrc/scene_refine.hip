@@ -44,18 +44,20 @@ struct SceneWs {
 
 static long scene_max_items(int64_t row_budget, int E) { return (long)(row_budget / NN_TILE) + E + 1; }
 
-static SceneWs scene_carve(void* base, int64_t n_points, int V, int S, int E, int64_t row_budget) {
+// robust: partials and edge_mom hold IcpPlaneWPartial (the moments and W = sum w) behind the same pointers
+static SceneWs scene_carve(void* base, int64_t n_points, int V, int S, int E, int64_t row_budget, bool robust = false) {
+  const size_t partial = robust ? sizeof(IcpPlaneWPartial) : sizeof(IcpPlanePartial);
   SceneWs w; Carver c(base);
   const size_t max_items = (size_t)scene_max_items(row_budget, E);
   w.items = (NnWork*)c.take(max_items * sizeof(NnWork));
-  w.partials = (IcpPlanePartial*)c.take(max_items * sizeof(IcpPlanePartial));
+  w.partials = (IcpPlanePartial*)c.take(max_items * partial);
   w.edges = (SceneEdge*)c.take((size_t)E * sizeof(SceneEdge));
   w.edge_scene = (int32_t*)c.take((size_t)E * 4);
   w.edge_order = (int32_t*)c.take((size_t)E * 4);
   w.edone = (int32_t*)c.take((size_t)E * 4);
   w.edge_R = (float*)c.take((size_t)E * 9 * 4);
   w.edge_T = (float*)c.take((size_t)E * 3 * 4);
-  w.edge_mom = (IcpPlanePartial*)c.take((size_t)E * sizeof(IcpPlanePartial));
+  w.edge_mom = (IcpPlanePartial*)c.take((size_t)E * partial);
   w.edge_w = (double*)c.take((size_t)E * SCENE_EDGE_W * 8);
   w.views = (SceneView*)c.take((size_t)V * sizeof(SceneView));
   w.state = (double*)c.take((size_t)V * 12 * 8);
@@ -78,9 +80,14 @@ struct SceneShared {
   long long tot_n;
   int n;
 };
-static size_t scene_lds_bytes(int max_views) {
+// ... of the robust call: the weight sums beside the counts
+struct SceneSharedW : SceneShared {
+  double chunk_w[SCENE_CHUNK];
+  double tot_w;
+};
+static size_t scene_lds_bytes(int max_views, bool robust = false) {
   const size_t n = 6 * (size_t)max_views;
-  return align_up(sizeof(SceneShared), 16) + (2 * n * n + 2 * n) * sizeof(double);
+  return align_up(robust ? sizeof(SceneSharedW) : sizeof(SceneShared), 16) + (2 * n * n + 2 * n) * sizeof(double);
 }
 
 __global__ __launch_bounds__(256) void scene_setup_kernel(const int32_t* __restrict__ view_seg, int V, long N, const int32_t* __restrict__ scene_seg,
@@ -209,67 +216,24 @@ __global__ __launch_bounds__(ICP_TILE) void scene_query_kernel(const float* __re
   float best;
   int besti;
   grid_search(grids[w.pad1], P, cell_start, sorted, px, py, pz, grid_gate2(gate), best, besti);
-  icp_plane_moments(active, besti, best, gate, px, py, pz, P, Pn, w.y_start, red_m, red_n, partials + blockIdx.x);
+  icp_plane_moments<RAP_LOSS_NONE>(active, besti, best, gate, px, py, pz, P, Pn, w.y_start, red_m, red_n, partials + blockIdx.x);
 }
 
-__global__ __launch_bounds__(64) void scene_edge_kernel(const IcpPlanePartial* __restrict__ partials, const SceneEdge* __restrict__ edges,
-                                                        const int32_t* __restrict__ edone, const double* __restrict__ state,
-                                                        IcpPlanePartial* __restrict__ edge_mom, double* __restrict__ edge_w,
-                                                        float* __restrict__ edge_rmse, int32_t* __restrict__ edge_count) {
-  __shared__ double sA[36], sM[36], sb[6];
-  const int e = blockIdx.x;
-  if (edone[e]) return;
-  const SceneEdge r = edges[e];
-  ICP_SUM_PARTIALS(ICP_PLANE_NMOM, IcpPlanePartial, partials, r, m, n);
-  const int t = threadIdx.x;
-  if (t == 0) {
-    IcpPlanePartial* o = edge_mom + e;
-#pragma unroll
-    for (int i = 0; i < ICP_PLANE_NMOM; ++i) o->m[i] = m[i];
-    o->count = n;
-    if (edge_rmse) edge_rmse[e] = n > 0 ? (float)sqrt(fmax(m[27] / (double)n, 0.0)) : __builtin_nanf("");
-    if (edge_count) edge_count[e] = (int32_t)n;
-    // M^T = [[C, [t]x C], [0, C]] with C = R_b^T (the column form of the target's rotation) and t = T_b:
-    // J_w = [p_w x n_w, n_w] = M^T [q x n, n] for p_w = C q + t, n_w = C n
-    const double* s = state + (size_t)r.b * 12;
-    const double tx[3][3] = {{0.0, -s[11], s[10]}, {s[11], 0.0, -s[9]}, {-s[10], s[9], 0.0}};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double c = s[3 * j + i];
-        sM[6 * i + j] = c;
-        sM[6 * (i + 3) + (j + 3)] = c;
-        sM[6 * (i + 3) + j] = 0.0;
-        sM[6 * i + (j + 3)] = tx[i][0] * s[3 * j + 0] + tx[i][1] * s[3 * j + 1] + tx[i][2] * s[3 * j + 2];
-      }
-    }
-    int at = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-      for (int j = i; j < 6; ++j) { sA[6 * i + j] = m[at]; sA[6 * j + i] = m[at]; ++at; }
-      sb[i] = m[21 + i];
-    }
-  }
-  __syncthreads();
-  double* out = edge_w + (size_t)e * SCENE_EDGE_W;
-  if (t < 36) {
-    // A_w[i][j] = sum_k M^T[i][k] (sum_l A[k][l] M^T[j][l]); entry (i, j) with i > j repeats the statements of (j, i): the same bits
-    const int i0 = t / 6, j0 = t % 6, i = i0 < j0 ? i0 : j0, j = i0 < j0 ? j0 : i0;
-    double acc = 0.0;
-    for (int k = 0; k < 6; ++k) {
-      double row = 0.0;
-      for (int l = 0; l < 6; ++l) row += sA[6 * k + l] * sM[6 * j + l];
-      acc += sM[6 * i + k] * row;
-    }
-    out[t] = acc;
-  } else if (t < SCENE_EDGE_W) {
-    const int i = t - 36;
-    double acc = 0.0;
-    for (int k = 0; k < 6; ++k) acc += sM[6 * i + k] * sb[k];
-    out[t] = acc;
-  }
+// the robust call's query (rap_scene_refine_robust): the weighted epilogue of icp.h
+template <int LOSS>
+__global__ __launch_bounds__(ICP_TILE) void scene_query_robust_kernel(const float* __restrict__ P, const float* __restrict__ Pn,
+                                                                      const NnWork* __restrict__ items, const float* __restrict__ R,
+                                                                      const float* __restrict__ T, const int32_t* __restrict__ done, float gate,
+                                                                      const NnGrid* __restrict__ grids, const unsigned* __restrict__ cell_start,
+                                                                      const float4* __restrict__ sorted, double scale,
+                                                                      IcpPlaneWPartial* __restrict__ partials) {
+  __shared__ double red_m[ICP_TILE / 64][ICP_PLANE_WMOM];
+  __shared__ int red_n[ICP_TILE / 64];
+  ICP_QUERY_BEGIN(P, items, R, T, done);
+  float best;
+  int besti;
+  grid_search(grids[w.pad1], P, cell_start, sorted, px, py, pz, grid_gate2(gate), best, besti);
+  icp_plane_moments<LOSS>(active, besti, best, gate, px, py, pz, P, Pn, w.y_start, red_m, red_n, partials + blockIdx.x, scale);
 }
 
 struct SceneSolveArgs {
@@ -278,109 +242,28 @@ struct SceneSolveArgs {
   int32_t* done; int it; double rel_thr;
 };
 
-__global__ __launch_bounds__(SCENE_THREADS) void scene_solve_kernel(SceneSolveArgs p) {
-  extern __shared__ __align__(16) unsigned char scene_lds[];
-  const int sc = blockIdx.x;
-  if (p.done[sc]) return;
-  SceneShared* sh = (SceneShared*)scene_lds;
-  double* mem = (double*)(scene_lds + ((sizeof(SceneShared) + 15) / 16) * 16);
-  const int tid = threadIdx.x;
-  const SceneTab st = p.scenes[sc];
-  if (tid == 0) {
-    int nf = 0;
-    for (int l = 0; l < st.count; ++l) sh->slot[l] = p.views[st.first + l].fixed ? -1 : nf++;
-    sh->n = 6 * nf;
-    sh->tot_err = 0.0;
-    sh->tot_n = 0;
-  }
-  __syncthreads();
-  const int n = sh->n;
-  double* A = mem;
-  double* V = A + n * n;
-  double* g = V + n * n;
-  double* x = g + n;
-  for (int i = tid; i < n * n + n; i += SCENE_THREADS) A[i < n * n ? i : i + n * n] = 0.0;      // A, then g behind V
-  for (int c0 = 0; c0 < st.edge_count; c0 += SCENE_CHUNK) {
-    const int nc = min(SCENE_CHUNK, st.edge_count - c0);
-    __syncthreads();
-    if (tid < nc) {
-      const int e = p.edge_order[st.edge_first + c0 + tid];
-      const SceneEdge se = p.edges[e];
-      const long long ne = p.edge_mom[e].count;
-      sh->chunk_e[tid] = e;
-      sh->chunk_n[tid] = (int)ne;
-      sh->chunk_err[tid] = p.edge_mom[e].m[27];
-      sh->chunk_a[tid] = (short)sh->slot[se.a - st.first];
-      sh->chunk_b[tid] = (short)sh->slot[se.b - st.first];
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double err = sh->tot_err;
-      long long cnt = sh->tot_n;
-      for (int c = 0; c < nc; ++c) { err += sh->chunk_err[c]; cnt += sh->chunk_n[c]; }
-      sh->tot_err = err; sh->tot_n = cnt;
-    }
-    for (int idx = tid; idx < n * n + n; idx += SCENE_THREADS) {
-      double acc;
-      if (idx < n * n) {
-        const int i = idx / n, j = idx % n, vi = i / 6, vj = j / 6, off = (i % 6) * 6 + j % 6;
-        acc = A[idx];
-        for (int c = 0; c < nc; ++c) {
-          if (sh->chunk_n[c] == 0) continue;
-          const int a = sh->chunk_a[c], b = sh->chunk_b[c];
-          if (vi == vj) {
-            if (a == vi || b == vi) acc += p.edge_w[(size_t)sh->chunk_e[c] * SCENE_EDGE_W + off];
-          } else if ((a == vi && b == vj) || (a == vj && b == vi)) {
-            acc -= p.edge_w[(size_t)sh->chunk_e[c] * SCENE_EDGE_W + off];
-          }
-        }
-        A[idx] = acc;
-      } else {
-        const int i = idx - n * n, vi = i / 6;
-        acc = g[i];
-        for (int c = 0; c < nc; ++c) {
-          if (sh->chunk_n[c] == 0) continue;
-          const double gw = p.edge_w[(size_t)sh->chunk_e[c] * SCENE_EDGE_W + 36 + i % 6];
-          if (sh->chunk_a[c] == vi) acc += gw;
-          if (sh->chunk_b[c] == vi) acc -= gw;
-        }
-        g[i] = acc;
-      }
-    }
-  }
-  __syncthreads();
-  const long long cnt = sh->tot_n;
-  if (cnt == 0) {                                    // no pair with a usable normal in the whole scene: stop with the poses it had
-    if (tid == 0) { p.rmse[sc] = __builtin_inff(); p.done[sc] = 1; }
-    return;
-  }
-  sym_solve_pinv_step(A, V, g, x, n, SCENE_RCOND, &sh->solve, tid, SCENE_THREADS, [] { __syncthreads(); });
-  if (tid < st.count && sh->slot[tid] >= 0) {
-    const double* xi = x + 6 * sh->slot[tid];
-    if (xi[0] != 0.0 || xi[1] != 0.0 || xi[2] != 0.0 || xi[3] != 0.0 || xi[4] != 0.0 || xi[5] != 0.0) {      // a zero step keeps every bit
-      const int v = st.first + tid;
-      double dR[3][3], S[12];
-      rap_rodrigues(xi, dR);
-      double* s = p.state + (size_t)v * 12;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const double a0 = s[3 * i + 0], a1 = s[3 * i + 1], a2 = s[3 * i + 2];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) S[3 * i + j] = a0 * dR[j][0] + a1 * dR[j][1] + a2 * dR[j][2] + (i == 3 ? xi[3 + j] : 0.0);
-      }
-#pragma unroll
-      for (int i = 0; i < 12; ++i) s[i] = S[i];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) p.R[(size_t)v * 9 + i] = (float)S[i];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) p.T[(size_t)v * 3 + i] = (float)S[9 + i];
-    }
-  }
-  if (tid == 0) {
-    const double rmse = sqrt(fmax(sh->tot_err / (double)cnt, 0.0));
-    icp_finish_end(sc, p.it, rmse, p.rel_thr, p.rmse, p.iterations, p.converged, p.prev, p.done);
-  }
-}
+#define SCENE_IF_WEIGHTED(...)
+#define SCENE_EDGE_KERNEL scene_edge_kernel
+#define SCENE_SOLVE_KERNEL scene_solve_kernel
+#define SCENE_PARTIAL IcpPlanePartial
+#define SCENE_SHARED SceneShared
+#include "scene_refine_sums.inc"
+#undef SCENE_IF_WEIGHTED
+#undef SCENE_EDGE_KERNEL
+#undef SCENE_SOLVE_KERNEL
+#undef SCENE_PARTIAL
+#undef SCENE_SHARED
+#define SCENE_IF_WEIGHTED(...) __VA_ARGS__
+#define SCENE_EDGE_KERNEL scene_edge_robust_kernel
+#define SCENE_SOLVE_KERNEL scene_solve_robust_kernel
+#define SCENE_PARTIAL IcpPlaneWPartial
+#define SCENE_SHARED SceneSharedW
+#include "scene_refine_sums.inc"
+#undef SCENE_IF_WEIGHTED
+#undef SCENE_EDGE_KERNEL
+#undef SCENE_SOLVE_KERNEL
+#undef SCENE_PARTIAL
+#undef SCENE_SHARED
 
 extern "C" size_t rap_scene_refine_workspace_bytes(int64_t n_points, int32_t V, int32_t S, int32_t E, int64_t row_budget, int32_t max_views) {
   if (n_points <= 0 || n_points > 0x7fffffffLL / 8 || V <= 0 || V > 65535 || S <= 0 || E <= 0 || E > 65535 || row_budget <= 0 ||
@@ -389,19 +272,36 @@ extern "C" size_t rap_scene_refine_workspace_bytes(int64_t n_points, int32_t V, 
   return scene_carve(nullptr, n_points, V, S, E, row_budget).total;
 }
 
-extern "C" int rap_scene_refine(const float* P, const float* normals, const int32_t* view_seg, int32_t V, int64_t n_points,
-                                const int32_t* scene_seg, int32_t S, const int32_t* edges, int32_t E, int64_t row_budget, int32_t max_views,
-                                const uint8_t* fixed, const float* init_R, const float* init_T, int32_t max_iterations,
-                                float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse,
-                                int32_t* iterations, uint8_t* converged, float* edge_rmse, int32_t* edge_count, void* ws, size_t ws_bytes,
-                                void* stream_) {
+extern "C" size_t rap_scene_refine_robust_workspace_bytes(int64_t n_points, int32_t V, int32_t S, int32_t E, int64_t row_budget,
+                                                          int32_t max_views) {
+  if (!rap_scene_refine_workspace_bytes(n_points, V, S, E, row_budget, max_views)) return 0;
+  return scene_carve(nullptr, n_points, V, S, E, row_budget, true).total;
+}
+
+template <int LOSS>
+static void scene_query_robust(hipStream_t stream, unsigned max_items, const float* P, const float* normals, const SceneWs& w, float gate,
+                               double scale) {
+  hipLaunchKernelGGL(scene_query_robust_kernel<LOSS>, dim3(max_items), dim3(ICP_TILE), 0, stream, P, normals, (const NnWork*)w.items,
+                     (const float*)w.edge_R, (const float*)w.edge_T, (const int32_t*)w.edone, gate, (const NnGrid*)w.grid.grids,
+                     (const unsigned*)w.grid.cell_start, (const float4*)w.grid.sorted, scale, (IcpPlaneWPartial*)w.partials);
+}
+
+// both entry points; robust: the weighted kernels with loss (a RAP_LOSS_* code, checked here) at loss_scale
+static int scene_entry(const float* P, const float* normals, const int32_t* view_seg, int32_t V, int64_t n_points, const int32_t* scene_seg,
+                       int32_t S, const int32_t* edges, int32_t E, int64_t row_budget, int32_t max_views, const uint8_t* fixed,
+                       const float* init_R, const float* init_T, int32_t max_iterations, float relative_rmse_thr,
+                       float max_correspondence_distance, float* R, float* T, float* rmse, int32_t* iterations, uint8_t* converged,
+                       float* edge_rmse, int32_t* edge_count, bool robust, int32_t loss, float loss_scale, void* ws, size_t ws_bytes,
+                       void* stream_) {
   if (!P || !normals || !view_seg || !scene_seg || !edges || !R || !T || !rmse || !iterations || !converged || n_points <= 0 ||
       n_points > 0x7fffffffLL / 8 || V <= 0 || V > 65535 || S <= 0 || E <= 0 || E > 65535 || row_budget <= 0 ||
       row_budget / NN_TILE > 0x7fffffffLL / 64 || max_views < 2 || max_views > SCENE_MAX_VIEWS || max_iterations <= 0 ||
       relative_rmse_thr != relative_rmse_thr || max_correspondence_distance != max_correspondence_distance)
     return RAP_ERR_INVALID;
+  if (robust && (loss < RAP_LOSS_NONE || loss > RAP_LOSS_TUKEY || (loss != RAP_LOSS_NONE && !(loss_scale > 0.f && loss_scale < __builtin_inff()))))
+    return RAP_ERR_INVALID;
   if (!ws) return RAP_ERR_WORKSPACE;
-  const SceneWs w = scene_carve(ws, n_points, V, S, E, row_budget);
+  const SceneWs w = scene_carve(ws, n_points, V, S, E, row_budget, robust);
   if (w.total > ws_bytes) return RAP_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   const int max_items = (int)scene_max_items(row_budget, E);
@@ -411,22 +311,53 @@ extern "C" int rap_scene_refine(const float* P, const float* normals, const int3
   RAP_LAUNCH_CHECK();
   int rc = launch_nn_grid_build(stream, P, view_seg, V, (long)n_points, w.grid);
   if (rc) return rc;
-  const int lds = (int)scene_lds_bytes(max_views);
+  const int lds = (int)scene_lds_bytes(max_views, robust);
   for (int it = 0; it < max_iterations; ++it) {
     hipLaunchKernelGGL(scene_edge_pose_kernel, dim3((E + 255) / 256), dim3(256), 0, stream, (const SceneEdge*)w.edges,
                        (const int32_t*)w.edge_scene, E, (const double*)w.state, (const int32_t*)w.done, w.edge_R, w.edge_T, w.edone);
     RAP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scene_query_kernel, dim3((unsigned)max_items), dim3(ICP_TILE), 0, stream, P, normals, (const NnWork*)w.items,
-                       (const float*)w.edge_R, (const float*)w.edge_T, (const int32_t*)w.edone, gate, (const NnGrid*)w.grid.grids,
-                       (const unsigned*)w.grid.cell_start, (const float4*)w.grid.sorted, w.partials);
-    RAP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(scene_edge_kernel, dim3(E), dim3(64), 0, stream, (const IcpPlanePartial*)w.partials, (const SceneEdge*)w.edges,
-                       (const int32_t*)w.edone, (const double*)w.state, w.edge_mom, w.edge_w, edge_rmse, edge_count);
-    RAP_LAUNCH_CHECK();
+    if (robust) {
+      RAP_LOSS_DISPATCH(loss, scene_query_robust, stream, (unsigned)max_items, P, normals, w, gate, (double)loss_scale);
+      RAP_LAUNCH_CHECK();
+      hipLaunchKernelGGL(scene_edge_robust_kernel, dim3(E), dim3(64), 0, stream, (const IcpPlaneWPartial*)w.partials,
+                         (const SceneEdge*)w.edges, (const int32_t*)w.edone, (const double*)w.state, (IcpPlaneWPartial*)w.edge_mom, w.edge_w,
+                         edge_rmse, edge_count);
+      RAP_LAUNCH_CHECK();
+    } else {
+      hipLaunchKernelGGL(scene_query_kernel, dim3((unsigned)max_items), dim3(ICP_TILE), 0, stream, P, normals, (const NnWork*)w.items,
+                         (const float*)w.edge_R, (const float*)w.edge_T, (const int32_t*)w.edone, gate, (const NnGrid*)w.grid.grids,
+                         (const unsigned*)w.grid.cell_start, (const float4*)w.grid.sorted, w.partials);
+      RAP_LAUNCH_CHECK();
+      hipLaunchKernelGGL(scene_edge_kernel, dim3(E), dim3(64), 0, stream, (const IcpPlanePartial*)w.partials, (const SceneEdge*)w.edges,
+                         (const int32_t*)w.edone, (const double*)w.state, w.edge_mom, w.edge_w, edge_rmse, edge_count);
+      RAP_LAUNCH_CHECK();
+    }
     const SceneSolveArgs a = {w.scenes, w.views, w.edges, w.edge_order, w.edge_mom, w.edge_w, w.state, R, T, rmse, iterations, converged,
                               w.prev, w.done, it, (double)relative_rmse_thr};
-    rc = rap_launch_dyn_lds(scene_solve_kernel, dim3(S), dim3(SCENE_THREADS), lds, stream, a);
+    rc = robust ? rap_launch_dyn_lds(scene_solve_robust_kernel, dim3(S), dim3(SCENE_THREADS), lds, stream, a)
+                : rap_launch_dyn_lds(scene_solve_kernel, dim3(S), dim3(SCENE_THREADS), lds, stream, a);
     if (rc) return rc;
   }
   return RAP_OK;
+}
+
+extern "C" int rap_scene_refine(const float* P, const float* normals, const int32_t* view_seg, int32_t V, int64_t n_points,
+                                const int32_t* scene_seg, int32_t S, const int32_t* edges, int32_t E, int64_t row_budget, int32_t max_views,
+                                const uint8_t* fixed, const float* init_R, const float* init_T, int32_t max_iterations,
+                                float relative_rmse_thr, float max_correspondence_distance, float* R, float* T, float* rmse,
+                                int32_t* iterations, uint8_t* converged, float* edge_rmse, int32_t* edge_count, void* ws, size_t ws_bytes,
+                                void* stream) {
+  return scene_entry(P, normals, view_seg, V, n_points, scene_seg, S, edges, E, row_budget, max_views, fixed, init_R, init_T, max_iterations,
+                     relative_rmse_thr, max_correspondence_distance, R, T, rmse, iterations, converged, edge_rmse, edge_count, false, 0, 0.f,
+                     ws, ws_bytes, stream);
+}
+extern "C" int rap_scene_refine_robust(const float* P, const float* normals, const int32_t* view_seg, int32_t V, int64_t n_points,
+                                       const int32_t* scene_seg, int32_t S, const int32_t* edges, int32_t E, int64_t row_budget,
+                                       int32_t max_views, const uint8_t* fixed, const float* init_R, const float* init_T,
+                                       int32_t max_iterations, float relative_rmse_thr, float max_correspondence_distance, float* R, float* T,
+                                       float* rmse, int32_t* iterations, uint8_t* converged, float* edge_rmse, int32_t* edge_count, int32_t loss,
+                                       float loss_scale, void* ws, size_t ws_bytes, void* stream) {
+  return scene_entry(P, normals, view_seg, V, n_points, scene_seg, S, edges, E, row_budget, max_views, fixed, init_R, init_T, max_iterations,
+                     relative_rmse_thr, max_correspondence_distance, R, T, rmse, iterations, converged, edge_rmse, edge_count, true, loss,
+                     loss_scale, ws, ws_bytes, stream);
 }

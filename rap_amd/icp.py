@@ -37,9 +37,29 @@ def _check_estimation(estimation):
         raise ValueError(f"estimation must be one of {ESTIMATIONS}, got {estimation!r}")
 
 
+LOSSES = {"huber": 1, "cauchy": 2, "tukey": 3}      # the RAP_LOSS_* codes of include/rapflow.h (0: none)
+
+
+def _check_loss(loss, loss_scale):
+    """-> (RAP_LOSS_* code, scale) of a robust call, or None for the plain one"""
+    if loss is None:
+        if loss_scale is not None:
+            raise ValueError("loss_scale is only used with a loss")
+        return None
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be None or one of {tuple(LOSSES)}, got {loss!r}")
+    if loss_scale is None:
+        raise ValueError(f"loss={loss!r} needs a loss_scale, in the units of the clouds")
+    k = float(loss_scale)
+    if not (k > 0.0 and k < float("inf")):
+        raise ValueError(f"loss_scale must be a positive finite number, got {loss_scale!r}")
+    return LOSSES[loss], k
+
+
 def icp_packed(X, x_seg, Y, y_seg, init_R=None, init_T=None, max_iterations: int = 100, relative_rmse_thr: float = 1e-6,
                max_correspondence_distance: float | None = None, return_Xt: bool = True, search: str = "brute",
-               estimation: str = "point_to_point", y_normals=None) -> ICPSolution:
+               estimation: str = "point_to_point", y_normals=None, loss: str | None = None, loss_scale: float | None = None,
+               return_weights: bool = False):
     """K problems on packed clouds: problem k aligns ``X[xs:xs+xn]`` to ``Y[ys:ys+yn]`` with ``(xs, xn) = x_seg[k]``,
     ``(ys, yn) = y_seg[k]``.  X (NX,3), Y (NY,3) fp32; x_seg, y_seg (K,2) int32 device tensors whose rows need not be contiguous or
     ordered (the x segments must not overlap); init_R (K,3,3) / init_T (K,3) or None.  Semantics, stopping rules and the treatment of
@@ -53,10 +73,21 @@ def icp_packed(X, x_seg, Y, y_seg, init_R=None, init_T=None, max_iterations: int
     None: estimated in the same call from Y's own segments (``estimate_normals_packed`` with 20 neighbours, no radius, no viewpoint --
     the sign of a normal does not enter the residual; y segments may repeat, but segments that overlap without being equal can leave
     rows without a normal: pass ``y_normals`` then).  The reported rmse is then the point-to-plane residual of the transform that
-    ENTERED the last iteration, one update behind the returned R, T."""
+    ENTERED the last iteration, one update behind the returned R, T.
+
+    ``loss`` (``"huber"``, ``"cauchy"`` or ``"tukey"``) with ``loss_scale`` (its scale k > 0, in the units of the clouds) weights every
+    point-to-plane residual by that robust loss in each Gauss-Newton step (``rap_icp_plane_robust`` / ``rap_icp_plane_grid_robust``:
+    which pairs count is unchanged, the rmse becomes sqrt(sum 2 rho / n), and a problem whose every weight is zero stops as one without
+    pairs does).  ``return_weights=True`` returns ``(ICPSolution, weights)``, weights (NX,) fp32: the weight every row of X had in the
+    last iteration its problem ran -- 0 for a row that was gated out or matched a row without a usable normal, 1 for every counted
+    row without a loss; rows outside every segment hold 0.  Both are point-to-plane only: weighting the Kabsch solve of
+    ``estimation="point_to_point"`` is not built, and asking for it raises ValueError."""
     _check_search(search)
     _check_estimation(estimation)
     plane = estimation == "point_to_plane"
+    robust = _check_loss(loss, loss_scale)
+    if (robust is not None or return_weights) and not plane:
+        raise ValueError("loss and return_weights need estimation='point_to_plane' (a weighted point-to-point solve is not built)")
     if y_normals is not None and not plane:
         raise ValueError("y_normals is only used by estimation='point_to_plane'")
     _require_cuda(X, "X")
@@ -71,6 +102,7 @@ def icp_packed(X, x_seg, Y, y_seg, init_R=None, init_T=None, max_iterations: int
     if int(max_iterations) <= 0:
         raise ValueError("max_iterations must be positive")
     empty_X = X if X.shape[0] == 0 and return_Xt else None
+    n_x_rows = X.shape[0]
     if X.shape[0] == 0:                                                  # the C ABI wants non-empty arrays; every segment clamps to nothing
         X = torch.zeros((1, 3), dtype=torch.float32, device=device)
         xs = torch.zeros_like(xs)
@@ -101,16 +133,22 @@ def icp_packed(X, x_seg, Y, y_seg, init_R=None, init_T=None, max_iterations: int
         raise ValueError("max_correspondence_distance must be positive (None: no gate)")
     lib = _lib.load()
     grid = search == "grid"
-    name = ("rap_icp_plane" if plane else "rap_icp") + ("_grid" if grid else "")
+    weighted = robust is not None or return_weights                     # the plain call stays on the entry points it always used
+    name = ("rap_icp_plane" if plane else "rap_icp") + ("_grid" if grid else "") + ("_robust" if weighted else "")
     fn, query = getattr(lib, name), getattr(lib, name + "_workspace_bytes")
     ws = workspace(device, query(NX, NY, K) if grid else query(NX, K))
     clouds = (_lib.ptr(X), _lib.ptr(xs), _lib.ptr(Y), _lib.ptr(ys)) + ((_lib.ptr(Yn),) if plane else ())
+    weights = torch.zeros((NX,), dtype=torch.float32, device=device) if return_weights else None
+    extra = (robust[0] if robust else 0, robust[1] if robust else 0.0, _lib.ptr(weights)) if weighted else ()
     with torch.cuda.device(device):
         rc = fn(*clouds, K, NX, NY, _lib.ptr(iR), _lib.ptr(iT), int(max_iterations),
                 float(relative_rmse_thr), gate, _lib.ptr(R), _lib.ptr(T), _lib.ptr(rmse), _lib.ptr(iters), _lib.ptr(conv),
-                _lib.ptr(Xt), _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
+                _lib.ptr(Xt), *extra, _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
     _lib.check(rc, name)
-    return ICPSolution(conv.bool(), rmse, empty_X if Xt is None else Xt, R, T, iters)
+    sol = ICPSolution(conv.bool(), rmse, empty_X if Xt is None else Xt, R, T, iters)
+    if return_weights:
+        return sol, (weights[:0] if empty_X is not None or n_x_rows == 0 else weights)
+    return sol
 
 
 def nearest_neighbors_packed(X, x_seg, Y, y_seg, R=None, T=None, max_distance: float | None = None):
@@ -200,7 +238,8 @@ def _lengths(lengths, K, N, device):
 
 def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100, relative_rmse_thr: float = 1e-6,
                             max_correspondence_distance: float | None = None, x_lengths=None, y_lengths=None,
-                            search: str = "brute", estimation: str = "point_to_point", Y_normals=None) -> ICPSolution:
+                            search: str = "brute", estimation: str = "point_to_point", Y_normals=None, loss: str | None = None,
+                            loss_scale: float | None = None, return_weights: bool = False):
     """ICP of X onto Y (point-to-point by default): padded batches ``X (K,N,3)``, ``Y (K,M,3)`` with optional ``x_lengths`` /
     ``y_lengths`` (K,), or
     ``(N,3)`` / ``(M,3)`` for one problem.  ``init_transform = (R, T)`` with R (K,3,3) or (3,3), T (K,3) or (3,) in the row-vector
@@ -209,9 +248,13 @@ def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100
     the points whose neighbour lies within that distance in each fit.  Returns an ``ICPSolution``; ``Xt`` has X's shape (padding rows
     unchanged).  One ``rap_icp`` call, no host synchronisation.  ``search="grid"`` finds the same neighbours through a uniform-grid
     index over Y (``rap_icp_grid``): the same bits, and far less work on large clouds.  ``estimation="point_to_plane"``: the
-    point-to-plane estimator of ``icp_packed`` with ``Y_normals`` (K,M,3) or (M,3), estimated from Y where None."""
+    point-to-plane estimator of ``icp_packed`` with ``Y_normals`` (K,M,3) or (M,3), estimated from Y where None.  ``loss`` /
+    ``loss_scale`` / ``return_weights``: the robust losses of ``icp_packed`` (point-to-plane only; a weighted point-to-point solve is
+    not built); with ``return_weights`` the result is ``(ICPSolution, weights)``, weights of X's shape without its last axis."""
     _check_search(search)
     _check_estimation(estimation)
+    if (_check_loss(loss, loss_scale) is not None or return_weights) and estimation != "point_to_plane":
+        raise ValueError("loss and return_weights need estimation='point_to_plane' (a weighted point-to-point solve is not built)")
     if Y_normals is not None and estimation != "point_to_plane":
         raise ValueError("Y_normals is only used by estimation='point_to_plane'")
     _require_cuda(X, "X")
@@ -233,7 +276,10 @@ def iterative_closest_point(X, Y, init_transform=None, max_iterations: int = 100
     if Y_normals is not None and tuple(Y_normals.shape) != tuple(Y.shape):
         raise ValueError(f"Y_normals must have Y's shape {tuple(Y.shape)}, got {tuple(Y_normals.shape)}")
     sol = icp_packed(Xb, x_seg, Yb, y_seg, iR, iT, max_iterations, relative_rmse_thr, max_correspondence_distance, search=search,
-                     estimation=estimation, y_normals=Y_normals)
+                     estimation=estimation, y_normals=Y_normals, loss=loss, loss_scale=loss_scale, return_weights=return_weights)
+    if return_weights:
+        sol, weights = sol
+        return sol._replace(Xt=sol.Xt.reshape(X.shape)), weights.reshape(X.shape[:-1])
     return sol._replace(Xt=sol.Xt.reshape(X.shape))
 
 

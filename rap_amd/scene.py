@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from .flow_model import _f32c, _require_cuda, workspace
-from .icp import _part_offsets
+from .icp import _check_loss, _part_offsets
 
 SceneRefinement = collections.namedtuple("SceneRefinement", ["R", "T", "rmse", "iterations", "converged", "edge_rmse", "edge_count"])
 SceneRefinement.__doc__ = """Result of a scene refinement, every field a device tensor: R (V,3,3) and T (V,3) with world = x @ R + T (row
@@ -56,7 +56,7 @@ def _all_pairs(scene_seg, V, max_views):
 
 def refine_scene_packed(points, view_seg, scene_seg, R=None, T=None, edges=None, normals=None, fixed=None, max_iterations: int = 30,
                         relative_rmse_thr: float = 1e-6, max_correspondence_distance: float | None = None, max_views: int = MAX_VIEWS,
-                        row_budget: int | None = None) -> SceneRefinement:
+                        row_budget: int | None = None, loss: str | None = None, loss_scale: float | None = None) -> SceneRefinement:
     """Joint point-to-plane refinement of S scenes on packed clouds (``rap_scene_refine``: the algorithm, the rules for tables and the
     limits are in include/rapflow.h).  ``points`` (N,3) fp32, every view in its own frame; ``view_seg`` (V,2) int32 (start, len) rows,
     views must not overlap; ``scene_seg`` (S,2) int32 (first view, number of views); ``R`` (V,3,3) / ``T`` (V,3) the starting poses in
@@ -66,8 +66,11 @@ def refine_scene_packed(points, view_seg, scene_seg, R=None, T=None, edges=None,
     whose pose is not a variable, None: the first view of every scene (a scene without a fixed view is legal: the minimum-norm step
     resolves the gauge).  A scene with more than ``max_views`` (2 .. 16) views is left out (rmse NaN).  ``row_budget``: upper bound on
     the rows of the source views summed over the edges, None: ``N * (max_views - 1)``, which all ordered pairs cannot exceed.
-    No host synchronisation.  -> ``SceneRefinement``."""
+    ``loss`` (``"huber"``, ``"cauchy"`` or ``"tukey"``) with ``loss_scale`` (its scale k > 0, in the units of the clouds) weights every
+    residual by that robust loss (``rap_scene_refine_robust``: rmse and edge_rmse become sqrt(sum 2 rho / n), and a scene whose every
+    weight is zero stops as one without pairs does).  No host synchronisation.  -> ``SceneRefinement``."""
     _check_knobs(max_iterations, max_correspondence_distance, max_views, row_budget)
+    robust = _check_loss(loss, loss_scale)
     _require_cuda(points, "points")
     device = points.device
     P = _f32c(points.reshape(-1, 3))
@@ -112,16 +115,17 @@ def refine_scene_packed(points, view_seg, scene_seg, R=None, T=None, edges=None,
     ermse = torch.empty((E,), dtype=torch.float32, device=device)
     ecount = torch.empty((E,), dtype=torch.int32, device=device)
     lib = _lib.load()
-    nbytes = lib.rap_scene_refine_workspace_bytes(N, V, S, E, budget, mv)
+    name = "rap_scene_refine" if robust is None else "rap_scene_refine_robust"      # the plain call stays on the entry point it always used
+    nbytes = getattr(lib, name + "_workspace_bytes")(N, V, S, E, budget, mv)
     if nbytes == 0:
         raise ValueError(f"rap_scene_refine does not take these sizes: {N} points, {V} views, {S} scenes, {E} edges, row budget {budget}")
     ws = workspace(device, nbytes)
     with torch.cuda.device(device):
-        rc = lib.rap_scene_refine(_lib.ptr(P), _lib.ptr(Pn), _lib.ptr(vs), V, N, _lib.ptr(ss), S, _lib.ptr(ed), E, budget, mv, _lib.ptr(fx),
+        rc = getattr(lib, name)(_lib.ptr(P), _lib.ptr(Pn), _lib.ptr(vs), V, N, _lib.ptr(ss), S, _lib.ptr(ed), E, budget, mv, _lib.ptr(fx),
                                   _lib.ptr(iR), _lib.ptr(iT), int(max_iterations), float(relative_rmse_thr), gate, _lib.ptr(Ro), _lib.ptr(To),
-                                  _lib.ptr(rmse), _lib.ptr(iters), _lib.ptr(conv), _lib.ptr(ermse), _lib.ptr(ecount), _lib.ptr(ws),
-                                  ws.numel(), _lib.current_stream(device))
-    _lib.check(rc, "rap_scene_refine")
+                                  _lib.ptr(rmse), _lib.ptr(iters), _lib.ptr(conv), _lib.ptr(ermse), _lib.ptr(ecount), *(robust or ()),
+                                  _lib.ptr(ws), ws.numel(), _lib.current_stream(device))
+    _lib.check(rc, name)
     return SceneRefinement(Ro, To, rmse, iters, conv.bool(), ermse, ecount)
 
 
@@ -144,16 +148,18 @@ def _registration_tables(pointclouds, points_per_part, anchor_parts, cu_seqlens_
 
 def refine_registration(pointclouds, points_per_part, rotations, translations, anchor_parts=None, cu_seqlens_batch=None, normals=None,
                         edges=None, max_iterations: int = 30, relative_rmse_thr: float = 1e-6,
-                        max_correspondence_distance: float | None = None, max_views: int = MAX_VIEWS, row_budget: int | None = None):
+                        max_correspondence_distance: float | None = None, max_views: int = MAX_VIEWS, row_budget: int | None = None,
+                        loss: str | None = None, loss_scale: float | None = None):
     """Polish the poses of a registered batch on its own clouds: ``pointclouds`` (TP,3) packed (with ``cu_seqlens_batch``) or (B,N,3),
     the condition clouds, every part in its own frame; ``points_per_part`` (B,P); ``rotations`` (B,P,3,3) and ``translations`` (B,P,3)
     in the sampler's convention registered = cond @ R^T + t -- what ``fit_transformations`` returns and ``save_transformation_files``
     takes.  Every sample is one scene, every part one view (P <= ``max_views``, else the sample is left out: its poses come back
     unchanged and its rmse is NaN); the flagged non-empty parts of ``anchor_parts`` (B,P) stay fixed, the first non-empty part where
     none is flagged.  ``edges`` (E,2): directed pairs of view numbers ``b * P + p``, None: all ordered pairs of a sample.  The other
-    knobs are ``refine_scene_packed``'s.  -> (rotations (B,P,3,3), translations (B,P,3), rmse (B,)) in the same convention; empty parts
-    keep their (zero) rows.  One ``rap_scene_refine`` call, no host synchronisation."""
+    knobs, ``loss`` and ``loss_scale`` included, are ``refine_scene_packed``'s.  -> (rotations (B,P,3,3), translations (B,P,3), rmse (B,)) in the same convention; empty parts
+    keep their (zero) rows.  One ``rap_scene_refine`` (with a loss: ``rap_scene_refine_robust``) call, no host synchronisation."""
     _check_knobs(max_iterations, max_correspondence_distance, max_views, row_budget)
+    _check_loss(loss, loss_scale)
     _require_cuda(pointclouds, "pointclouds")
     device = pointclouds.device
     B, P = points_per_part.shape
@@ -162,5 +168,6 @@ def refine_registration(pointclouds, points_per_part, rotations, translations, a
     T = _f32c(translations.to(device).reshape(B * P, 3))
     sol = refine_scene_packed(pointclouds.reshape(-1, 3), view_seg, scene_seg, R, T, edges=edges, normals=normals, fixed=fixed,
                               max_iterations=max_iterations, relative_rmse_thr=relative_rmse_thr,
-                              max_correspondence_distance=max_correspondence_distance, max_views=max_views, row_budget=row_budget)
+                              max_correspondence_distance=max_correspondence_distance, max_views=max_views, row_budget=row_budget,
+                              loss=loss, loss_scale=loss_scale)
     return sol.R.transpose(1, 2).reshape(B, P, 3, 3).contiguous(), sol.T.reshape(B, P, 3), sol.rmse

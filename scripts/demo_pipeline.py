@@ -38,8 +38,13 @@ def main():
     ap.add_argument("--refine", action="store_true",
                     help="polish the selected poses on the views' own clouds before they are written: joint multi-view point-to-plane "
                          "refinement, every sample one scene (rap_amd.refine_registration, DESIGN.md 7.9)")
+    ap.add_argument("--loss", default=None, choices=["huber", "cauchy", "tukey"],
+                    help="with --refine: weight every point-to-plane residual by this robust loss (needs --loss-scale)")
+    ap.add_argument("--loss-scale", type=float, default=None, help="the scale k of --loss, in the normalised units of the clouds")
     ap.add_argument("--out", default="/tmp/rap_demo")
     args = ap.parse_args()
+    if (args.loss is None) != (args.loss_scale is None) or (args.loss and not args.refine):
+        ap.error("--loss and --loss-scale go together, and with --refine")
     dev = torch.device("cuda:0")
     sync = torch.cuda.synchronize
     inp = S.make_inputs([[args.points] * args.views for _ in range(args.pairs)], seed=7)
@@ -109,9 +114,10 @@ def main():
         t0 = time.perf_counter()
         rot_sel, trans_sel, refine_rmse = rap_amd.refine_registration(data["pointclouds"], data["points_per_part"], rot_sel.to(dev), trans_sel.to(dev),
                                                                       cu_seqlens_batch=data["cu_seqlens"],
-                                                                      max_correspondence_distance=0.05)
+                                                                      max_correspondence_distance=0.05, loss=args.loss, loss_scale=args.loss_scale)
         sync()
-        extra = {"refine_seconds": time.perf_counter() - t0, "refine_rmse": refine_rmse.cpu().tolist()}
+        extra = {"refine_seconds": time.perf_counter() - t0, "refine_rmse": refine_rmse.cpu().tolist(), "refine_loss": args.loss,
+                 "refine_loss_scale": args.loss_scale}
 
     # 4. transform files of the rigidity-selected generation (evaluator.py:383-490); synthetic GT = identity
     gt = {"rotations": torch.eye(3).expand(B, P, 3, 3).contiguous(), "translations": torch.zeros(B, P, 3), "scales": inp["scales"],

@@ -11,6 +11,10 @@ section 7, row 4).  Prints one JSON line per workload; --out FILE also writes th
 --estimation point_to_plane times rap_icp_plane / rap_icp_plane_grid on the same clouds with the analytic normals of the surface (the
 iterations after the fourth or so run at the fixed point: the same work, which is what a per-iteration time needs).  --normals-points N
 adds a line for the normal estimation (rap_estimate_normals, 20 neighbours within 0.5) of one cloud of N points of the same surface.
+
+--loss {huber,cauchy,tukey,all} (point-to-plane only) times the robust entry points (rap_icp_plane_robust / rap_icp_plane_grid_robust) at
+--loss-scale.  Every workload is then timed with loss none through the plain entry point first, in the same process, and each robust
+line carries "ratio_to_none": its median over that one.  There is no threshold: the number to read is the ratio.
 """
 from __future__ import annotations
 
@@ -64,8 +68,13 @@ def main():
     ap.add_argument("--search", choices=["brute", "grid"], default="brute")
     ap.add_argument("--estimation", choices=["point_to_point", "point_to_plane"], default="point_to_point")
     ap.add_argument("--normals-points", type=int, default=0, help="also time the normal estimation of one cloud of this many points")
+    ap.add_argument("--loss", choices=["none", "huber", "cauchy", "tukey", "all"], default="none")
+    ap.add_argument("--loss-scale", type=float, default=0.01)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.loss != "none" and a.estimation != "point_to_plane":
+        ap.error("--loss needs --estimation point_to_plane")
+    losses = [None] + (["huber", "cauchy", "tukey"] if a.loss == "all" else [] if a.loss == "none" else [a.loss])
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
     import rap_amd
@@ -75,15 +84,25 @@ def main():
         K, n = WORKLOADS[name]
         X, Y, Yn = make_problems(torch, K, n)
         extra = dict(estimation=a.estimation, Y_normals=Yn) if a.estimation == "point_to_plane" else {}
-        call = lambda: rap_amd.iterative_closest_point(X, Y, max_iterations=a.iterations, relative_rmse_thr=float("-inf"), search=a.search, **extra)
-        sol, gpu = time_calls(torch, call, a.warmup, a.calls)
-        assert int(sol.iterations.min()) == a.iterations and not bool(sol.converged.any()), "a problem stopped early"
-        med = statistics.median(gpu)
-        pairs = a.iterations * K * n * n
-        lines.append(json.dumps({"workload": name, "search": a.search, "estimation": a.estimation, "problems": K, "points": n, "iterations": a.iterations, "calls": len(gpu), "warmup": a.warmup,
-                                 "gpu_ms": {"median": med, "p10": pct(gpu, 0.1), "p90": pct(gpu, 0.9)}, "ms_per_iteration": med / a.iterations,
-                                 "pair_distances_per_s": pairs / (med * 1e-3), "mean_rmse": float(sol.rmse.mean())}))
-        print(lines[-1], flush=True)
+        base = None
+        for loss in losses:
+            robust = dict(loss=loss, loss_scale=a.loss_scale) if loss else {}
+            call = lambda: rap_amd.iterative_closest_point(X, Y, max_iterations=a.iterations, relative_rmse_thr=float("-inf"), search=a.search,
+                                                           **extra, **robust)
+            sol, gpu = time_calls(torch, call, a.warmup, a.calls)
+            assert int(sol.iterations.min()) == a.iterations and not bool(sol.converged.any()), "a problem stopped early"
+            med = statistics.median(gpu)
+            pairs = a.iterations * K * n * n
+            row = {"workload": name, "search": a.search, "estimation": a.estimation, "problems": K, "points": n, "iterations": a.iterations, "calls": len(gpu), "warmup": a.warmup,
+                   "gpu_ms": {"median": med, "p10": pct(gpu, 0.1), "p90": pct(gpu, 0.9)}, "ms_per_iteration": med / a.iterations,
+                   "pair_distances_per_s": pairs / (med * 1e-3), "mean_rmse": float(sol.rmse.mean())}
+            if len(losses) > 1:
+                base = med if loss is None else base
+                row.update({"loss": loss or "none", "loss_scale": a.loss_scale if loss else None,
+                            "entry_point": "rap_icp_plane" + ("_grid" if a.search == "grid" else "") + ("_robust" if loss else ""),
+                            "ratio_to_none": med / base})
+            lines.append(json.dumps(row))
+            print(lines[-1], flush=True)
     if a.normals_points > 0:
         P = make_problems(torch, 1, a.normals_points)[1][0]
         nrm, gpu = time_calls(torch, lambda: rap_amd.estimate_point_normals(P, k_neighbors=20, radius=0.5), a.warmup, a.calls)

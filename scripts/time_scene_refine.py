@@ -7,6 +7,9 @@ Per call: GPU time (HIP events around the call) after --warmup calls, the median
 found.  As context, in the same session, the P - 1 pairwise point-to-plane ICPs of every other view against the first on the grid index
 (one icp_packed call of P - 1 problems, the same number of iterations): what a user could do before, which ignores every overlap but
 the anchor's.  There is no threshold: the call is new.  Prints one JSON line per workload; --out FILE also writes them.
+
+--loss {huber,cauchy,tukey,all} also times rap_scene_refine_robust at --loss-scale on every workload, after the plain call and in the same
+process: one more line per loss, with "ratio_to_none" = its median over the plain call's.
 """
 from __future__ import annotations
 
@@ -71,8 +74,11 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--gate", type=float, default=0.05)
+    ap.add_argument("--loss", choices=["none", "huber", "cauchy", "tukey", "all"], default="none")
+    ap.add_argument("--loss-scale", type=float, default=0.01)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    losses = ["huber", "cauchy", "tukey"] if a.loss == "all" else [] if a.loss == "none" else [a.loss]
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
     import rap_amd
@@ -100,6 +106,18 @@ def main():
                                  "pairwise_against_anchor": {"problems": V - 1, "gpu_ms": stats(gpu_pair), "mean_rmse": float(pair.rmse.mean())},
                                  "threshold": None}))
         print(lines[-1], flush=True)
+        for loss in losses:
+            rob, gpu_r = time_calls(torch, lambda: rap_amd.refine_scene_packed(P, seg, scenes, R0, T0, normals=N, max_iterations=a.iterations,
+                                                                              relative_rmse_thr=ninf, max_correspondence_distance=a.gate, max_views=V,
+                                                                              loss=loss, loss_scale=a.loss_scale), a.warmup, a.calls)
+            assert int(rob.iterations[0]) == a.iterations and not bool(rob.converged[0]), "the scene stopped early"
+            med_r = statistics.median(gpu_r)
+            lines.append(json.dumps({"workload": f"{V}x{n}", "views": V, "points_per_view": n, "edges": V * (V - 1), "iterations": a.iterations,
+                                     "gate": a.gate, "loss": loss, "loss_scale": a.loss_scale, "entry_point": "rap_scene_refine_robust",
+                                     "calls": len(gpu_r), "warmup": a.warmup, "gpu_ms": stats(gpu_r), "ms_per_iteration": med_r / a.iterations,
+                                     "rmse": float(rob.rmse[0]), "pairs_last_iteration": int(rob.edge_count.sum()), "ratio_to_none": med_r / med,
+                                     "threshold": None}))
+            print(lines[-1], flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
