@@ -13,7 +13,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "librapflow.so")
 SOURCES = ["api.hip", "api_ops.hip", "gemm_f32.hip", "attn_f32.hip", "norm.hip", "embed.hip", "adaln.hip", "sampler_kernels.hip",
            "procrustes.hip", "gemm_h16.hip", "attn_h16.hip", "norm_h16.hip", "rigidity.hip", "transforms.hip", "overlap.hip", "spinnet.hip", "nn_metrics.hip", "part_acc.hip", "pair_metrics.hip", "icp.hip", "nn_grid.hip", "nn_knn.hip", "orient.hip", "icp_plane.hip", "normals.hip", "submaps.hip", "fps.hip", "fps_grid.hip", "voxel.hip", "collate.hip", "outlier.hip", "voxel_sort.hip", "attn_x2.hip", "x2_pack.hip", "scene_refine.hip"]
-HEADERS = ["common.h", "kernels.h", "kabsch.h", "nn_tile.h", "nn_grid.h", "nn_grid_search.h", "sym_solve.h", "icp.h", "robust_loss.h", "icp_plane_finish.inc", "scene_refine_sums.inc", "assign.h", "fps_grid.h", "half.h", "lds_dma.h", "softcap.h", "attn_f32_body.inc", "attn_h16_body.inc", "attn_x2_body.inc", "gemm_h16_epilogue.h", os.path.join("..", "..", "include", "rapflow.h")]
+HEADERS = ["common.h", "kernels.h", "kabsch.h", "nn_tile.h", "nn_grid.h", "nn_grid_search.h", "sym_solve.h", "icp.h", "robust_loss.h", "icp_plane_finish.inc", "scene_refine_sums.inc", "assign.h", "fps_grid.h", "half.h", "lds_dma.h", "softcap.h", "attn_tile.h", "attn_f32_body.inc", "attn_h16_body.inc", "attn_x2_body.inc", "gemm_h16_epilogue.h", os.path.join("..", "..", "include", "rapflow.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -559,11 +559,11 @@ static CallPlan plan_call(const CallShape& s, int force_dtype = -1) {
   const bool f32 = dtype == RAP_DT_F32, x2 = p.x2 = dtype == RAP_DT_F32X2;
   const bool half = dtype == RAP_DT_BF16 || dtype == RAP_DT_F16;
   p.h16_stream = half && s.resid_dtype == RAP_DT_F16;
-  // query rows per attention work item: 256, or 64 / 128 for few-token calls of the 16-bit modes (attention_h16_block_queries)
+  // query rows per attention work item: 256, or 64 / 128 for few-token calls of the 16-bit modes (attention_h16_plan)
   // (a capped model: the one form the soft-capped kernels have -- full-size items, one key group)
   p.capped = s.softcap > 0.f;
-  p.attn_bq = (half && !p.capped) ? attention_h16_block_queries(dtype, (long)T) : RAP_ATTN_BQ;
-  p.attn_kg = (half && !p.capped) ? attention_h16_key_groups(dtype, (long)T) : 1;
+  p.attn_bq = RAP_ATTN_BQ; p.attn_kg = 1;
+  if (half && !p.capped) attention_h16_plan((long)T, &p.attn_bq, &p.attn_kg);
   p.max_items_batch = (int)(s.TP / p.attn_bq) + s.B + 1;
   p.max_items_part = (int)(s.TP / p.attn_bq) + s.nseg_part + 1;
   // ff2: the one layer GEMM with K >= 1024.  Reserved by SHAPE alone (tuning key 6 only gates the launch), so that the size

@@ -5,6 +5,7 @@
 #include "half.h"
 #include "kernels.h"
 #include "fps_grid.h"
+#include "softcap.h"
 
 #include <cmath>
 #include <new>
@@ -64,23 +65,35 @@ extern "C" int rap_geglu_interleave(const float* W, const float* b, float* Wp, f
 
 // [work items | sanitised copy of the caller's cu_seqlens]: the kernel-level attention entry points index with the copy only (ADVICE r05:
 // an entry above TP in the caller's table made seg_start + q run past the planes; the model path has sanitised its tables since round 5)
-// (work items reserved at the smallest granularity, 64 rows: tuning key 20's forced item sizes reach rap_attention_h16 too)
-static size_t attn_items_bytes(int64_t TP, int32_t nseg) { return align_up(((size_t)(TP / 64) + (size_t)nseg + 1) * sizeof(AttnWorkItem), 256); }
-extern "C" size_t rap_attention_workspace_bytes(int64_t TP, int32_t nseg) {
-  return attn_items_bytes(TP, nseg) + align_up(((size_t)nseg + 1) * sizeof(int32_t), 256);
+// (work items reserved at the smallest granularity, 64 rows: tuning key 20's forced item sizes reach rap_attention_h16 too).
+// The split-KV forms (splits > 1) put their partial planes behind the two tables:
+// [partial O: splits x TP x heads x 64 floats | (max, row sum): splits x TP x heads x 2 floats] (the fp32 form keeps its row sums in the
+// first half of the last plane)
+struct AttnWs { AttnWorkItem* items; int max_items; int32_t* cu_s; float *part_o, *part_ml; size_t total; };
+static AttnWs carve_attn(int64_t TP, int32_t nseg, int32_t heads, int32_t splits, void* base) {
+  AttnWs p{}; Carver c(base);
+  p.items = (AttnWorkItem*)c.take(((size_t)(TP / 64) + (size_t)nseg + 1) * sizeof(AttnWorkItem));
+  p.cu_s = (int32_t*)c.take(((size_t)nseg + 1) * sizeof(int32_t));
+  if (splits > 1) {
+    p.part_o = (float*)c.take((size_t)splits * (size_t)TP * (size_t)heads * 64 * sizeof(float));
+    p.part_ml = (float*)c.take((size_t)splits * (size_t)TP * (size_t)heads * 2 * sizeof(float));
+  }
+  p.total = c.total();
+  return p;
 }
+extern "C" size_t rap_attention_workspace_bytes(int64_t TP, int32_t nseg) { return carve_attn(TP, nseg, 0, 1, nullptr).total; }
 // What the attention entry points start with, after their own pointer checks: the segment-table and workspace checks (tp_max: the
-// entry point's limit on TP), the clamped, non-decreasing copy of cu_seqlens inside ws, and from it the work list at the head of ws with
-// bq query rows per item (0: the fp32 kernel's own granularity; the list then holds room for 256-row items).  -> *max_items for the launch
-// need: what ws must hold when the entry point puts more behind the two tables (the split forms' partial planes); 0 = the tables alone
+// entry point's limit on TP), the carved workspace (heads, splits: the split forms' partial planes), the clamped, non-decreasing copy of
+// cu_seqlens inside it, and from that the work list with bq query rows per item (0: the fp32 kernel's own granularity; the list then
+// holds room for 256-row items) and w->max_items for the launch
 static int attn_begin(hipStream_t stream, const int32_t* cu_seqlens, int32_t nseg, int64_t TP, int64_t tp_max, void* ws, size_t ws_bytes,
-                      int bq, int* max_items, size_t need = 0) {
+                      int bq, AttnWs* w, int32_t heads = 0, int32_t splits = 1) {
   if (!cu_seqlens || nseg < 0 || TP < 0 || TP > tp_max) return RAP_ERR_INVALID;
-  if (!ws || ws_bytes < (need ? need : rap_attention_workspace_bytes(TP, nseg))) return RAP_ERR_WORKSPACE;
-  *max_items = (int)(TP / (bq ? bq : RAP_ATTN_BQ)) + nseg + 1;
-  int32_t* cu_s = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(ws) + attn_items_bytes(TP, nseg));
-  const int rc = launch_sanitize_cu(stream, cu_seqlens, nseg + 1, (long)TP, cu_s);
-  return rc ? rc : launch_build_attn_worklist(stream, cu_s, nseg, (AttnWorkItem*)ws, *max_items, bq);
+  *w = carve_attn(TP, nseg, heads, splits, ws);
+  if (!ws || ws_bytes < w->total) return RAP_ERR_WORKSPACE;
+  w->max_items = (int)(TP / (bq ? bq : RAP_ATTN_BQ)) + nseg + 1;
+  const int rc = launch_sanitize_cu(stream, cu_seqlens, nseg + 1, (long)TP, w->cu_s);
+  return rc ? rc : launch_build_attn_worklist(stream, w->cu_s, nseg, w->items, w->max_items, bq);
 }
 
 // the work list of one attention launch as rap_sample / rap_dit_forward build it: one {seg_start, seg_len, q0, 0} item per
@@ -97,49 +110,38 @@ extern "C" int rap_attention_f32(const float* qkv_headmajor, const int32_t* cu_s
                                  void* stream_) {
   if (!qkv_headmajor || !out) return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  int rc, max_items;
-  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 0, &max_items))) return rc;
-  return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, nullptr, nullptr, 1);
+  AttnWs w;
+  if (int rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 0, &w)) return rc;
+  return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, w.items, w.max_items, logit_bound, nullptr, nullptr, 1);
 }
 
-// the soft-capped kernels of a model with rap_model_set_softcap (one launch form each: 256-row items, unsplit)
-static bool softcap_ok(float c) { return c > 0.f && c < 3.0e38f; }      // (NaN fails both)
+// the soft-capped kernels of a model with rap_model_set_softcap (one launch form each: 256-row items, unsplit; softcap_ok: softcap.h)
 extern "C" int rap_attention_f32_softcap(const float* qkv_headmajor, const int32_t* cu_seqlens, int32_t nseg, float* out, int64_t TP,
                                          int32_t heads, float softcap, void* ws, size_t ws_bytes, void* stream_) {
   if (!qkv_headmajor || !out || heads <= 0 || !softcap_ok(softcap)) return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  int rc, max_items;
-  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 0, &max_items))) return rc;
-  return launch_attention_f32_softcap(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, softcap);
+  AttnWs w;
+  if (int rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 0, &w)) return rc;
+  return launch_attention_f32_softcap(stream, qkv_headmajor, out, (int)TP, heads, w.items, w.max_items, softcap);
 }
 
-// The split-KV forms few-token model calls run (attention_f32_splits / attention_x2_splits pick them there), for the parity tests:
-// ws = [work items | sanitised cu_seqlens | partial O: splits x TP x heads x 64 floats | (max, row sum): splits x TP x heads x 2 floats]
-// (the fp32 form keeps its row sums in the first half of the last plane)
+// The split-KV forms few-token model calls run (attention_f32_splits / attention_x2_splits pick them there), for the parity tests
+// (workspace: carve_attn)
 static bool attn_splits_ok(int32_t splits) { return splits == 1 || splits == 2 || splits == 4; }
-static size_t attn_part_o_bytes(int64_t TP, int32_t heads, int32_t splits) { return (size_t)splits * (size_t)TP * (size_t)heads * 64 * sizeof(float); }
 extern "C" size_t rap_attention_split_workspace_bytes(int64_t TP, int32_t nseg, int32_t heads, int32_t splits) {
   if (TP < 0 || nseg < 0 || heads <= 0 || !attn_splits_ok(splits)) return 0;
-  const size_t base = rap_attention_workspace_bytes(TP, nseg);
-  if (splits == 1) return base;
-  return base + attn_part_o_bytes(TP, heads, splits) + align_up((size_t)splits * (size_t)TP * (size_t)heads * 2 * sizeof(float), 256);
+  return carve_attn(TP, nseg, heads, splits, nullptr).total;
 }
 extern "C" int rap_attention_f32_split(const float* qkv_headmajor, const int32_t* cu_seqlens, int32_t nseg, float* out, int64_t TP,
                                        int32_t heads, const float* logit_bound, int32_t splits, void* ws, size_t ws_bytes, void* stream_) {
   if (!qkv_headmajor || !out || heads <= 0 || !attn_splits_ok(splits) || (splits > 1 && !logit_bound)) return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  int rc, max_items;
-  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 0, &max_items,
-                       rap_attention_split_workspace_bytes(TP, nseg, heads, splits))))
-    return rc;
+  AttnWs w;
+  if (int rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 0, &w, heads, splits)) return rc;
   if (splits == 1)
-    return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, nullptr, nullptr, 1);
-  char* base = reinterpret_cast<char*>(ws);
-  const int32_t* cu_s = reinterpret_cast<const int32_t*>(base + attn_items_bytes(TP, nseg));
-  float* part_o = reinterpret_cast<float*>(base + rap_attention_workspace_bytes(TP, nseg));
-  float* part_l = reinterpret_cast<float*>(reinterpret_cast<char*>(part_o) + attn_part_o_bytes(TP, heads, splits));
-  return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, part_o, part_l,
-                              splits, cu_s, nseg);
+    return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, w.items, w.max_items, logit_bound, nullptr, nullptr, 1);
+  return launch_attention_f32(stream, qkv_headmajor, out, (int)TP, heads, w.items, w.max_items, logit_bound, w.part_o, w.part_ml, splits,
+                              w.cu_s, nseg);
 }
 
 // The launchers below take the row count as an int and answer RAP_OK to an empty call before they look at anything else: the entry
@@ -250,11 +252,12 @@ extern "C" int rap_attention_h16(int32_t dtype, const uint16_t* qk, const uint16
   // 256-row work items, two stages -- unless tuning key 20 FORCES an item size / key groups (64, 128, 66, 130: the A/B values), which
   // then applies here as it does to a model call of the same row count (so the few-token kernels have kernel-level tests)
   const long rows = attention_h16_forced() ? (long)align_up((size_t)TP, 256) : 0;
-  const int bq = attention_h16_block_queries(dtype, rows), kg = attention_h16_key_groups(dtype, rows);
+  int bq, kg;
+  attention_h16_plan(rows, &bq, &kg);
   hipStream_t stream = (hipStream_t)stream_;
-  int rc, max_items;
-  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, bq, &max_items))) return rc;
-  return launch_attention_h16(stream, dtype, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, logit_bound, 0, bq, kg);
+  AttnWs w;
+  if (int rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, bq, &w)) return rc;
+  return launch_attention_h16(stream, dtype, qk, vt, vt_nblk, out, (int)TP, heads, w.items, w.max_items, logit_bound, 0, bq, kg);
 }
 extern "C" int rap_attention_h16_softcap(int32_t dtype, const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens,
                                          int32_t nseg, uint16_t* out, int64_t TP, int32_t heads, float softcap, void* ws, size_t ws_bytes,
@@ -262,9 +265,9 @@ extern "C" int rap_attention_h16_softcap(int32_t dtype, const uint16_t* qk, cons
   if (!qk || !vt || !out || heads <= 0 || !softcap_ok(softcap) || (dtype != RAP_DT_BF16 && dtype != RAP_DT_F16) || (int64_t)vt_nblk * 64 < TP)
     return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  int rc, max_items;
-  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 256, &max_items))) return rc;
-  return launch_attention_h16_softcap(stream, dtype, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, softcap);
+  AttnWs w;
+  if (int rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 8, ws, ws_bytes, 256, &w)) return rc;
+  return launch_attention_h16_softcap(stream, dtype, qk, vt, vt_nblk, out, (int)TP, heads, w.items, w.max_items, softcap);
 }
 extern "C" int rap_layernorm_mod_h16(int32_t dtype, const float* x, uint16_t* out, int64_t TP, int32_t d, const float* mod,
                                      int64_t mod_stride, const int32_t* token_row, void* stream) {
@@ -340,36 +343,30 @@ extern "C" int rap_x2_attention(const uint16_t* qk, const uint16_t* vt, int32_t 
                                 uint16_t* out, int64_t TP, int32_t heads, void* ws, size_t ws_bytes, void* stream_) {
   if (!qk || !vt || !out) return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  int rc, max_items;
-  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &max_items))) return rc;
-  return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items);
+  AttnWs w;
+  if (int rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &w)) return rc;
+  return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, w.items, w.max_items);
 }
 extern "C" int rap_x2_attention_softcap(const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens, int32_t nseg,
                                         uint16_t* out, int64_t TP, int32_t heads, float softcap, void* ws, size_t ws_bytes, void* stream_) {
   if (!qk || !vt || !out || heads <= 0 || !softcap_ok(softcap) || (int64_t)vt_nblk * 64 < TP) return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  int rc, max_items;
-  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &max_items))) return rc;
-  return launch_attention_x2_softcap(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, softcap);
+  AttnWs w;
+  if (int rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &w)) return rc;
+  return launch_attention_x2_softcap(stream, qk, vt, vt_nblk, out, (int)TP, heads, w.items, w.max_items, softcap);
 }
-// the same over `splits` key ranges per work item (workspace layout: see rap_attention_f32_split)
+// the same over `splits` key ranges per work item (workspace layout: carve_attn)
 extern "C" int rap_x2_attention_split(const uint16_t* qk, const uint16_t* vt, int32_t vt_nblk, const int32_t* cu_seqlens, int32_t nseg,
                                       uint16_t* out, int64_t TP, int64_t n_tokens, int32_t heads, int32_t splits, void* ws, size_t ws_bytes,
                                       void* stream_) {
   if (!qk || !vt || !out || heads <= 0 || !attn_splits_ok(splits) || n_tokens < 0 || n_tokens > TP || (int64_t)vt_nblk * 64 < TP)
     return RAP_ERR_INVALID;
   hipStream_t stream = (hipStream_t)stream_;
-  int rc, max_items;
-  if ((rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &max_items,
-                       rap_attention_split_workspace_bytes(TP, nseg, heads, splits))))
-    return rc;
-  if (splits == 1) return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items);
-  char* base = reinterpret_cast<char*>(ws);
-  const int32_t* cu_s = reinterpret_cast<const int32_t*>(base + attn_items_bytes(TP, nseg));
-  float* part_o = reinterpret_cast<float*>(base + rap_attention_workspace_bytes(TP, nseg));
-  float* part_ml = reinterpret_cast<float*>(reinterpret_cast<char*>(part_o) + attn_part_o_bytes(TP, heads, splits));
-  return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, (const AttnWorkItem*)ws, max_items, part_o, part_ml, splits,
-                             (int)n_tokens, cu_s, nseg);
+  AttnWs w;
+  if (int rc = attn_begin(stream, cu_seqlens, nseg, TP, 0x7fffffffLL / 16, ws, ws_bytes, 256, &w, heads, splits)) return rc;
+  if (splits == 1) return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, w.items, w.max_items);
+  return launch_attention_x2(stream, qk, vt, vt_nblk, out, (int)TP, heads, w.items, w.max_items, w.part_o, w.part_ml, splits, (int)n_tokens,
+                             w.cu_s, nseg);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -26,7 +26,7 @@
 //  * grid = work items x heads with head = blockIdx % H (blockIdx % 8 is the XCD on MI355X: each XCD's
 //    L2 then serves the K/V of one head).
 #include "kernels.h"
-#include "softcap.h"
+#include "attn_tile.h"
 
 // Measured and NOT kept (round 3, call 22): K / V tiles by LDS-DMA (global_load_lds_dwordx4, 256-byte K rows with a slot ^ (row & 15) swizzle)
 // instead of through staging registers -- bit-identical output, 196 instead of 228-242 VGPRs, and exactly the same speed (141.7 vs
@@ -38,22 +38,6 @@
 #define VLD 64
 // scheduling fence: VALU (0x2), SALU (0x4) and transcendental (0x400) instructions may cross; DS, MFMA, VMEM may not
 #define ATTN_FENCE __builtin_amdgcn_sched_barrier(0x406);
-
-__device__ __forceinline__ float xhalf_max(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xhalf_sum(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-#define ATTN_DEFER_THR 11.5f   // = 8 in natural-log units: the online softmax rescales only when a row maximum grows by more than e^8
-__device__ __forceinline__ float amax3(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
 
 // NW = waves per block (4: 256 queries, two blocks per CU; 8: 512 queries, one block per CU).  With NW = 8 the
 // two waves that share a SIMD (w and w+4) belong to the SAME block and get different static priorities: with equal
@@ -239,10 +223,7 @@ int launch_attention_f32(hipStream_t stream, const float* qkv, float* out, int T
     unsigned dyn = 0;
     if (attention_f32_one_per_cu(max_items, heads, splits)) {
       dyn = 16384;
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_f32_kernel<4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, dyn) != hipSuccess) {
-        rap_set_last_hip_error((int)hipGetLastError());
-        return RAP_ERR_HIP;
-      }
+      if (int rc = rap_allow_dyn_lds(attention_f32_kernel<4, true, true>, dyn)) return rc;
     }
     hipLaunchKernelGGL((attention_f32_kernel<4, true, true>), dim3(max_items * heads, splits), dim3(256), dyn, stream, qkv, out, TP,
                        heads, items, bound, part_o, part_l);
@@ -264,7 +245,7 @@ int launch_attention_f32(hipStream_t stream, const float* qkv, float* out, int T
 int launch_attention_f32_softcap(hipStream_t stream, const float* qkv, float* out, int TP, int heads, const AttnWorkItem* items,
                                  int max_items, float softcap) {
   if (max_items <= 0 || TP <= 0) return RAP_OK;
-  if (heads <= 0 || !(softcap > 0.f) || !(softcap < 3.0e38f)) return RAP_ERR_INVALID;
+  if (heads <= 0 || !softcap_ok(softcap)) return RAP_ERR_INVALID;
   hipLaunchKernelGGL((attention_f32_softcap_kernel<4>), dim3(max_items * heads), dim3(256), 0, stream, qkv, out, TP, heads, items, softcap);
   RAP_LAUNCH_CHECK();
   return RAP_OK;

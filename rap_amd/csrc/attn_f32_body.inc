@@ -1,7 +1,5 @@
 // The body of attention_f32_kernel and attention_f32_softcap_kernel (attn_f32.hip), included once into each: the names NW, BOUNDED, SPLIT,
-// CAP (compile-time) and qkv, out, TP, heads, items, bound, part_o, part_l, cap are the including kernel's.  Text inclusion, not a
-// __device__ __forceinline__ template: hipcc allocates registers and orders commutative operands differently for an inlined body, and the
-// uncapped kernels keep their device code of before instruction for instruction (scripts/kernel_asm_diff.py).
+// CAP (compile-time) and qkv, out, TP, heads, items, bound, part_o, part_l, cap are the including kernel's.  Text inclusion: see attn_tile.h.
   __shared__ __attribute__((aligned(16))) float smem[2 * AKV * KLD + 2 * AKV * VLD];
   float* Ks = smem;                    // [2][64][68]
   float* Vs = smem + 2 * AKV * KLD;    // [2][64][64]
@@ -175,16 +173,14 @@
         } else {
         // ---- online softmax (lane-local except one cross-half max, a VALU v_permlane32_swap).  Round 3: row maximum through
         // v_max3_f32 (8 instead of 15 instructions per 16 scores; hipcc also prepends a canonicalising v_max to every
-        // MFMA-output operand of fmaxf) and a DEFERRED rescale, as the 16-bit kernel has had since r01: the running reference
-        // m of a row moves only when a row of the wave outgrows it by more than 2^11.5 (e^8), so in the steady state a
-        // sub-tile costs no alpha, no 32 multiplies of O and no l * alpha -- p = 2^(s - m) <= 2^11.5 and every sum stays far
-        // inside fp32; softmax is invariant to the reference.  Same function, different rounding pattern.
+        // MFMA-output operand of fmaxf) and a DEFERRED rescale, as the 16-bit kernel has had since r01 (ATTN_DEFER_THR, attn_tile.h).
+        // Same function, different rounding pattern.
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
-          float mx = amax3(st[qt][0], st[qt][1], st[qt][2]);
+          float mx = attn_max3(st[qt][0], st[qt][1], st[qt][2]);
 #pragma unroll
-          for (int r = 3; r < 15; r += 2) mx = amax3(mx, st[qt][r], st[qt][r + 1]);
-          mx = xhalf_max(fmaxf(mx, st[qt][15]));
+          for (int r = 3; r < 15; r += 2) mx = attn_max3(mx, st[qt][r], st[qt][r + 1]);
+          mx = attn_xhalf_max(fmaxf(mx, st[qt][15]));
           if (__builtin_amdgcn_ballot_w64(mx > mrun[qt] + ATTN_DEFER_THR) != 0) {       // wave-uniform
             const float mnew = fmaxf(mrun[qt], mx);
             const float alpha = __builtin_amdgcn_exp2f(mrun[qt] - mnew);
@@ -243,7 +239,7 @@
 #pragma unroll
   for (int qt = 0; qt < 2; ++qt) {
     const int q = qw0 + qt * 32 + l31;
-    const float ltot = xhalf_sum(lsum[qt]);
+    const float ltot = attn_xhalf_sum(lsum[qt]);
     const float inv = SPLIT ? 1.0f : (bound_ok ? 1.0f / ltot : __builtin_nanf(""));
     if (q < len) {
       float* op = (SPLIT ? part_o + (size_t)blockIdx.y * TP * dmodel : out) + (size_t)(it.seg_start + q) * dmodel + head * 64;

@@ -28,30 +28,15 @@
 #include "half.h"
 #include "kernels.h"
 #include "lds_dma.h"
-#include "softcap.h"
+#include "attn_tile.h"
 
 #define HKV 64
 #define HLD 72   // LDS row stride in 16-bit elements (144 B)
 
-__device__ __forceinline__ float h_xhalf_max(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float h_xhalf_sum(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// OPT: bit 0 = row maximum through v_max3_f32, bit 1 = deferred rescale (threshold DEFER_THR in the base-2 exponent) -- together the
+// OPT: bit 0 = row maximum through v_max3_f32, bit 1 = deferred rescale (threshold ATTN_DEFER_THR in the base-2 exponent) -- together the
 // ONLINE softmax; bit 3 = bounded softmax, bit 4 (with bit 3, bf16) = q arrives pre-scaled and the offset is dropped (see below).
 // (The timing-only ablation switches, the persistent / rotated / 512-query forms and the in-kernel time stamps of rounds 1-2 are in
 // the history at 72efb73; their results are in docs/DESIGN_r01_r02.md section 4.4.)
-#define DEFER_THR 11.5f   // = 8 in natural-log units: P <= e^8
-__device__ __forceinline__ float hmax3(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
 // DMA (round 3, the default): K / V^T tiles go global -> LDS directly (global_load_lds_dwordx4, two 1 KB pieces per wave and tile: no
 // staging registers, no ds_write_b128, no s_waitcnt in front of them -- round 2's instruction-mix microbenchmark priced the
 // register-staged stream at 16-20 % of this loop).  The DMA writes LDS lane-linearly, so rows are 128 bytes without padding and
@@ -63,6 +48,15 @@ __device__ __forceinline__ float hmax3(float a, float b, float c) {
 // wall).  NS = 4: a ring of four K / V^T stages, tiles requested three ahead, counted vmcnt.  bq = query rows per work item (64 / 128
 // instead of 256: the waves whose rows lie beyond bq only stage -- every wave still issues two pieces per tile): 4 / 2 times the blocks,
 // each with a quarter / half of the MFMA work per tile.  Same per-query arithmetic in the same order: bit-identical results.
+
+// The Q fragments have landed with the first tiles (vmcnt(0)) -- tell the compiler (a use of every fragment), or it waits for them with
+// vmcnt(3..0) inside the key loop, where those waits would drain the DMA pieces of the NEXT tile it does not know about
+#define HATT_Q_LANDED(qf)                                                                                                           \
+  _Pragma("unroll") for (int s_ = 0; s_ < 4; ++s_) {                                                                                \
+    uint4 q_ = __builtin_bit_cast(uint4, qf[s_]);                                                                                   \
+    asm volatile("" : "+v"(q_.x), "+v"(q_.y), "+v"(q_.z), "+v"(q_.w));                                                              \
+    qf[s_] = __builtin_bit_cast(T8, q_);                                                                                            \
+  }
 template <int DT, int OPT, bool DMA, int NS = 2>
 __global__ __launch_bounds__(512, 2) void attention_h16_kernel(const u16* __restrict__ qk, const u16* __restrict__ vt, int vt_nblk,
                                                                u16* __restrict__ out, int TP, int heads,
@@ -98,57 +92,26 @@ template <int DT, int OPT, int KG>
 __global__ __launch_bounds__(512, 2) void attention_h16_kgroup_kernel(const u16* __restrict__ qk, const u16* __restrict__ vt, int vt_nblk,
                                                                       u16* __restrict__ out, int TP, int heads,
                                                                       const AttnWorkItem* __restrict__ items, const float* __restrict__ bound) {
-  typedef typename H16<DT>::T8 T8;
   static_assert(KG == 2 || KG == 4, "two or four key groups");
   constexpr int QW = 8 / KG;                 // query waves of the block (work item = 32 QW rows)
   constexpr int NSTG = 8 / KG;               // stages of KG tiles: 8 tile slots of K and 8 of V^T = 128 KB
   constexpr int TILE = HKV * 64;             // 16-bit elements of one K (or V^T) tile, 128-byte rows, slots XOR-swizzled
   constexpr int MERGE_OFF = 8 * 32 * HLD * 2;   // bytes: the merge records start behind the 8 output slabs
   static_assert(MERGE_OFF + (KG - 1) * QW * 34 * 64 * 4 <= 16 * TILE * 2, "merge records must fit");
-  extern __shared__ __attribute__((aligned(16))) u16 smem_kg[];
-  u16* Ks = smem_kg;                 // [8 slots][64 keys][64]
-  u16* Vs = smem_kg + 8 * TILE;      // [8 slots][64 d][64]   (columns = vt_pos of the key)
+  extern __shared__ __attribute__((aligned(16))) u16 smem[];
+  u16* Ks = smem;                 // [8 slots][64 keys][64]
+  u16* Vs = smem + 8 * TILE;      // [8 slots][64 d][64]   (columns = vt_pos of the key)
+  // the work item, every tile's arithmetic and the row stores are the text of attn_h16_body.inc (its parts 1-3), which reads these names:
+  // the LDS-DMA tile layout, no cap, bq rows per work item
+  constexpr bool DMA = true, CAP = false;
+  constexpr int LDR = 64, bq = 32 * QW;
+  const float cap = 0.f;
+#define HATT_PART 1
+#include "attn_h16_body.inc"
 
-  const int tid = threadIdx.x;
-  const int head = blockIdx.x % heads;
-  const AttnWorkItem it = items[blockIdx.x / heads];
-  const int len = it.seg_len;
-  if (len <= 0) return;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int hi = lane >> 5, l31 = lane & 31;
-  const int seg0 = it.seg_start, seg1 = it.seg_start + len;
-  const int qwv = wave % QW, grp = wave / QW;
-
-  const u16* Qg = qk + (size_t)head * TP * 64;
-  const u16* Kg = qk + (size_t)(heads + head) * TP * 64;
-  const u16* Vg = vt + (size_t)head * vt_nblk * (64 * 64);
-
-  const int qw0 = it.q0 + qwv * 32;
-  const bool has_rows = qw0 < len;
-
-  T8 qf[4];
-  {
-    int q = qw0 + l31;
-    q = q < len ? q : len - 1;
-    const u16* qp = Qg + (size_t)(seg0 + q) * 64 + 8 * hi;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qf[s] = __builtin_bit_cast(T8, *reinterpret_cast<const uint4*>(qp + 16 * s));
-  }
-  f32x16 o0, o1;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { o0[r] = 0.f; o1[r] = 0.f; }
-  float mrun = (OPT & 16) ? 0.f : (OPT & 8) ? bound[head] * 8.0f : -1e30f, lsum = 0.f;
-  const float c = 0.125f * 1.44269504088896340736f;
-
-  const int b_first = seg0 >> 6;
-  const int ntile = ((seg1 - 1) >> 6) - b_first + 1;
   const int nstep = (ntile + KG - 1) / KG;
-  // staging as in the kernel above: wave w owns rows 8w .. 8w+7 of every K tile and every V^T tile of a step (2 KG pieces of 1 KB per step).
+  // staging as in the kernel above (drow, dls, lds_k, lds_v): wave w owns rows 8w .. 8w+7 of every K tile and every V^T tile of a step (2 KG pieces of 1 KB per step).
   // A step beyond the segment's last tile re-requests that tile: every step issues the same number of pieces, so the counted wait holds.
-  const int drow = wave * 8 + (lane >> 3);
-  const int dls = ((tid & 7) ^ ((drow >> 1) & 7)) * 8;
-  const unsigned lds_k = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) u16*)Ks + (unsigned)wave * 1024u);
-  const unsigned lds_v = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) u16*)Vs + (unsigned)wave * 1024u);
 #define HKG_DMA_STEP(J)                                                                               \
   {                                                                                                   \
     _Pragma("unroll") for (int gg_ = 0; gg_ < KG; ++gg_) {                                            \
@@ -166,87 +129,17 @@ __global__ __launch_bounds__(512, 2) void attention_h16_kgroup_kernel(const u16*
   for (int s_ = 0; s_ < NSTG - 1; ++s_)
     if (s_ < nstep) HKG_DMA_STEP(s_)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-  for (int s = 0; s < 4; ++s) { uint4 q_ = __builtin_bit_cast(uint4, qf[s]); asm volatile("" : "+v"(q_.x), "+v"(q_.y), "+v"(q_.z), "+v"(q_.w)); qf[s] = __builtin_bit_cast(T8, q_); }
+  HATT_Q_LANDED(qf)
   __syncthreads();
 
-  const int swz = (l31 >> 1) & 7;
   for (int j = 0; j < nstep; ++j) {
     const bool ahead = (j + NSTG - 1) < nstep;
     if (ahead) HKG_DMA_STEP(j + NSTG - 1)
     const int t = j * KG + grp;
-    if (has_rows && t < ntile) {
+    if (wave_active && t < ntile) {
       const int cur = (j % NSTG) * KG + grp;
-      f32x16 s0, s1;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
-      const u16* kp = Ks + cur * TILE + l31 * 64;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const int ko = ((2 * s + hi) ^ swz) * 8;
-        const T8 k0 = __builtin_bit_cast(T8, *reinterpret_cast<const uint4*>(kp + ko));
-        const T8 k1 = __builtin_bit_cast(T8, *reinterpret_cast<const uint4*>(kp + 32 * 64 + ko));
-        s0 = H16<DT>::mfma(k0, qf[s], s0);
-        s1 = H16<DT>::mfma(k1, qf[s], s1);
-      }
-      const int tile0 = (b_first + t) * 64;
-      if (tile0 < seg0 || tile0 + 64 > seg1) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kg = tile0 + mfma32_crow(r, hi);
-          s0[r] = (kg >= seg0 && kg < seg1) ? s0[r] : -1e30f;
-          s1[r] = (kg + 32 >= seg0 && kg + 32 < seg1) ? s1[r] : -1e30f;
-        }
-      }
-      if (!(OPT & 8)) {        // online softmax: v_max3 row maxima, deferred rescale (as above)
-        float ma = hmax3(s0[0], s0[1], s0[2]), mb = hmax3(s1[0], s1[1], s1[2]);
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) { ma = hmax3(ma, s0[r], s0[r + 1]); mb = hmax3(mb, s1[r], s1[r + 1]); }
-        const float mx = h_xhalf_max(hmax3(ma, mb, fmaxf(s0[15], s1[15])));
-        if (!__all((mx - mrun) * c <= DEFER_THR)) {
-          const float mnew = fmaxf(mrun, mx);
-          const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * c);
-          mrun = mnew;
-          lsum *= alpha;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
-        }
-      }
-      {
-        const f32x2 c2 = {c, c};
-        const f32x2 nmc2 = {-mrun * c, -mrun * c};
-        f32x2 ps2 = {0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          f32x2 a = {s0[2 * k], s0[2 * k + 1]};
-          f32x2 b = {s1[2 * k], s1[2 * k + 1]};
-          if (!(OPT & 16)) {
-            a = __builtin_elementwise_fma(a, c2, nmc2);
-            b = __builtin_elementwise_fma(b, c2, nmc2);
-          }
-          a.x = __builtin_amdgcn_exp2f(a.x); a.y = __builtin_amdgcn_exp2f(a.y);
-          b.x = __builtin_amdgcn_exp2f(b.x); b.y = __builtin_amdgcn_exp2f(b.y);
-          s0[2 * k] = a.x; s0[2 * k + 1] = a.y;
-          s1[2 * k] = b.x; s1[2 * k + 1] = b.y;
-          ps2 += a + b;
-        }
-        lsum += ps2.x + ps2.y;
-      }
-      const u16* vp = Vs + cur * TILE + l31 * 64;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const int rb = 8 * (ks & 1);
-        T8 pb;
-        if ((ks >> 1) == 0)
-          pb = h16_pack8<DT>(s0[rb + 0], s0[rb + 1], s0[rb + 2], s0[rb + 3], s0[rb + 4], s0[rb + 5], s0[rb + 6], s0[rb + 7]);
-        else
-          pb = h16_pack8<DT>(s1[rb + 0], s1[rb + 1], s1[rb + 2], s1[rb + 3], s1[rb + 4], s1[rb + 5], s1[rb + 6], s1[rb + 7]);
-        const int vo = ((2 * ks + hi) ^ swz) * 8;
-        const T8 v0 = __builtin_bit_cast(T8, *reinterpret_cast<const uint4*>(vp + vo));
-        const T8 v1 = __builtin_bit_cast(T8, *reinterpret_cast<const uint4*>(vp + 32 * 64 + vo));
-        o0 = H16<DT>::mfma(v0, pb, o0);
-        o1 = H16<DT>::mfma(v1, pb, o1);
-      }
+#define HATT_PART 2
+#include "attn_h16_body.inc"
     }
     if (NSTG > 2 && ahead) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * KG * (NSTG - 2)) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -256,20 +149,20 @@ __global__ __launch_bounds__(512, 2) void attention_h16_kgroup_kernel(const u16*
 
   // ---- the KG partials of a query meet in LDS (the K / V^T slots are free: every wave is past the last barrier).  Record of a wave:
   // 34 values per lane (o0, o1, l, m), value-major, so that a wave's 64 lanes write / read 256 contiguous bytes.
-  float* rec = reinterpret_cast<float*>(reinterpret_cast<char*>(smem_kg) + MERGE_OFF);
-  if (grp > 0 && has_rows) {
-    float* wr = rec + (size_t)((grp - 1) * QW + qwv) * (34 * 64) + lane;
+  float* rec = reinterpret_cast<float*>(reinterpret_cast<char*>(smem) + MERGE_OFF);
+  if (grp > 0 && wave_active) {
+    float* wr = rec + (size_t)((grp - 1) * QW + qwave) * (34 * 64) + lane;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { wr[r * 64] = o0[r]; wr[(16 + r) * 64] = o1[r]; }
     wr[32 * 64] = lsum;
     wr[33 * 64] = mrun;
   }
   __syncthreads();
-  if (grp > 0 || !has_rows) return;
+  if (grp > 0 || !wave_active) return;
   if (OPT & 8) {               // bounded softmax: one fixed offset for every group -- plain sums, in group order
 #pragma unroll
     for (int g = 1; g < KG; ++g) {
-      const float* rd = rec + (size_t)((g - 1) * QW + qwv) * (34 * 64) + lane;
+      const float* rd = rec + (size_t)((g - 1) * QW + qwave) * (34 * 64) + lane;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { o0[r] += rd[r * 64]; o1[r] += rd[(16 + r) * 64]; }
       lsum += rd[32 * 64];
@@ -278,39 +171,22 @@ __global__ __launch_bounds__(512, 2) void attention_h16_kgroup_kernel(const u16*
     float mg[KG], mall = mrun;
     mg[0] = mrun;
 #pragma unroll
-    for (int g = 1; g < KG; ++g) { mg[g] = rec[(size_t)((g - 1) * QW + qwv) * (34 * 64) + 33 * 64 + lane]; mall = fmaxf(mall, mg[g]); }
+    for (int g = 1; g < KG; ++g) { mg[g] = rec[(size_t)((g - 1) * QW + qwave) * (34 * 64) + 33 * 64 + lane]; mall = fmaxf(mall, mg[g]); }
     const float a0 = __builtin_amdgcn_exp2f((mg[0] - mall) * c);
     lsum *= a0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o0[r] *= a0; o1[r] *= a0; }
 #pragma unroll
     for (int g = 1; g < KG; ++g) {
-      const float* rd = rec + (size_t)((g - 1) * QW + qwv) * (34 * 64) + lane;
+      const float* rd = rec + (size_t)((g - 1) * QW + qwave) * (34 * 64) + lane;
       const float ag = __builtin_amdgcn_exp2f((mg[g] - mall) * c);
 #pragma unroll
       for (int r = 0; r < 16; ++r) { o0[r] = fmaf(rd[r * 64], ag, o0[r]); o1[r] = fmaf(rd[(16 + r) * 64], ag, o1[r]); }
       lsum = fmaf(rd[32 * 64], ag, lsum);
     }
   }
-  const float inv = 1.0f / h_xhalf_sum(lsum);
-  u16* slab = smem_kg + wave * (32 * HLD);
-  u16* wp = slab + l31 * HLD + 4 * hi;
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    *reinterpret_cast<uint2*>(wp + 8 * g) =
-        h16_pack4<DT>(o0[4 * g + 0] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-    *reinterpret_cast<uint2*>(wp + 32 + 8 * g) =
-        h16_pack4<DT>(o1[4 * g + 0] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_wave_barrier();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int row = (lane >> 3) + 8 * i, piece = lane & 7;
-    const uint4 v = *reinterpret_cast<const uint4*>(slab + row * HLD + piece * 8);
-    if (qw0 + row < len)
-      *reinterpret_cast<uint4*>(out + (size_t)(seg0 + qw0 + row) * (heads * 64) + head * 64 + piece * 8) = v;
-  }
+#define HATT_PART 3
+#include "attn_h16_body.inc"
 }
 
 // Kernel choice per LAUNCH (round 3): per-head logit bounds supplied (the caller guarantees q.k/8 <= bound[h] <= 40) -> the bounded,
@@ -340,7 +216,7 @@ rap_tuning_t g_rap_attn_h16_dma = 1;      // tuning key 13: K / V^T tiles by LDS
 //   groups (the first form of round 6: bit-identical to round 5);  64 / 128: that item size + ring for every call of at most 8 192 rows (A/B);
 //   66 / 130: 64-row items x 4 key groups / 128-row items x 2 key groups for every call of at most 8 192 rows (A/B)
 rap_tuning_t g_rap_attn_h16_small = 1;
-static void attention_h16_plan(long rows, int* bq, int* kg) {
+void attention_h16_plan(long rows, int* bq, int* kg) {
   const int mode = g_rap_attn_h16_small;
   *bq = 256; *kg = 1;
   if (!mode || !g_rap_attn_h16_dma || rows <= 0 || rows > 8192) return;
@@ -354,8 +230,6 @@ static void attention_h16_plan(long rows, int* bq, int* kg) {
   if (mode == 2) return;
   if (rows <= 2048) { *bq = 64; *kg = 4; } else { *kg = 2; }
 }
-int attention_h16_block_queries(int, long rows) { int bq, kg; attention_h16_plan(rows, &bq, &kg); return bq; }
-int attention_h16_key_groups(int, long rows) { int bq, kg; attention_h16_plan(rows, &bq, &kg); return kg; }
 bool attention_h16_forced() { const int m = g_rap_attn_h16_small; return m == 64 || m == 128 || m == 66 || m == 130; }
 
 // the model path asks before it runs qk-norm: pre-scaled q only feeds the bounded bf16 kernel
@@ -371,11 +245,7 @@ template <int DT, int OPT, int KG>
 static int launch_kgroup(hipStream_t stream, const u16* qk, const u16* vt, int vt_nblk, u16* out, int TP, int heads, const AttnWorkItem* items,
                          int max_items, const float* bound) {
   // more than the 64 KB a kernel may use without asking; set per launch (as attn_x2.hip does): the attribute belongs to the current device
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_h16_kgroup_kernel<DT, OPT, KG>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                          HKG_LDS_BYTES) != hipSuccess) {
-    rap_set_last_hip_error((int)hipGetLastError());
-    return RAP_ERR_HIP;
-  }
+  if (int rc = rap_allow_dyn_lds(attention_h16_kgroup_kernel<DT, OPT, KG>, HKG_LDS_BYTES)) return rc;
   hipLaunchKernelGGL((attention_h16_kgroup_kernel<DT, OPT, KG>), dim3(max_items * heads), dim3(512), HKG_LDS_BYTES, stream, qk, vt, vt_nblk, out, TP,
                      heads, items, bound);
   return RAP_OK;
@@ -425,7 +295,7 @@ int launch_attention_h16(hipStream_t stream, int dtype, const u16* qk, const u16
 int launch_attention_h16_softcap(hipStream_t stream, int dtype, const u16* qk, const u16* vt, int vt_nblk, u16* out, int TP, int heads,
                                  const AttnWorkItem* items, int max_items, float softcap) {
   if (max_items <= 0 || TP <= 0) return RAP_OK;
-  if (heads <= 0 || vt_nblk * 64 < TP || !(softcap > 0.f) || !(softcap < 3.0e38f)) return RAP_ERR_INVALID;
+  if (heads <= 0 || vt_nblk * 64 < TP || !softcap_ok(softcap)) return RAP_ERR_INVALID;
   const dim3 grid(max_items * heads);
 #define HATT_CAP_LAUNCH(DTV)                                                                                                              \
   {                                                                                                                                       \

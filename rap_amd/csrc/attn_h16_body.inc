@@ -1,9 +1,13 @@
 // The body of attention_h16_kernel and attention_h16_softcap_kernel (attn_h16.hip), included once into each: the names DT, OPT, DMA, NS,
-// CAP (compile-time) and qk, vt, vt_nblk, out, TP, heads, items, bound, bq, cap are the including kernel's.  Text inclusion, not a
-// __device__ __forceinline__ template: see attn_f32_body.inc.
-// CAP: the fp32 scores q.k become 8 cap * tanh(q.k / (8 cap)), so that the exponent's FMA (x log2(e) / 8) sees cap * tanh(s / cap) of the
-// logit s = q.k / 8.
-  typedef typename H16<DT>::T8 T8;
+// CAP (compile-time) and qk, vt, vt_nblk, out, TP, heads, items, bound, bq, cap are the including kernel's.  Text inclusion: see
+// attn_tile.h.  CAP: ATTN_SOFTCAP there.
+// attention_h16_kgroup_kernel has its own LDS layout, K / V^T stream, key loop and merge, and takes the rest from here, one part per
+// inclusion (#define HATT_PART n in front of each; undefined = the whole body):
+//   1 = the work item, the Q fragments, the softmax state, the staging coordinates   (reads QW = query waves of the block, Ks, Vs)
+//   2 = one key tile: S^T, softmax, O^T += V^T P^T   (reads cur = the tile's LDS slot, t = its index in the segment, Ks, Vs, LDR)
+//   3 = normalise and store whole rows through the wave's slab   (reads smem)
+#ifndef HATT_PART
+  constexpr int QW = 8;                 // every wave has its own 32 query rows
   constexpr int LDR = DMA ? 64 : HLD;   // LDS row stride in 16-bit elements: 128 B swizzled (DMA) or 144 B padded
   static_assert(NS == 2 || (DMA && NS == 4), "two stages, or the four-stage LDS-DMA ring");
   // (at the full configuration -- two blocks per CU cover each other -- a ring of THREE stages was measured in r03 call 21: 1 132 vs
@@ -13,7 +17,10 @@
   __shared__ __attribute__((aligned(16))) u16 smem[SMEM_ELEMS];
   u16* Ks = smem;                    // [NS][64 keys][LDR]
   u16* Vs = smem + NS * HKV * LDR;   // [NS][64 d][LDR]   (columns = vt_pos of the key)
+#endif
 
+#if !defined(HATT_PART) || HATT_PART == 1
+  typedef typename H16<DT>::T8 T8;
   const int tid = threadIdx.x;
   const int head = blockIdx.x % heads;
   const AttnWorkItem it = items[blockIdx.x / heads];
@@ -22,13 +29,16 @@
   const int lane = tid & 63, wave = tid >> 6;
   const int hi = lane >> 5, l31 = lane & 31;
   const int seg0 = it.seg_start, seg1 = it.seg_start + len;
+  const int qwave = wave % QW;          // the wave's 32 query rows within the work item ...
+  [[maybe_unused]] const int grp = wave / QW;      // ... and its key group (0 here: the key-group kernel's)
 
   const u16* Qg = qk + (size_t)head * TP * 64;
   const u16* Kg = qk + (size_t)(heads + head) * TP * 64;
   const u16* Vg = vt + (size_t)head * vt_nblk * (64 * 64);
 
-  const int qw0 = it.q0 + wave * 32;
-  const bool wave_active = wave * 32 < bq && qw0 < len;   // waves beyond the work item's rows / the segment still help stage K/V
+  const int qw0 = it.q0 + qwave * 32;
+  // waves beyond the work item's rows / the segment still help stage K/V (QW < 8: the item is 32 QW rows, every query wave lies inside)
+  const bool wave_active = (QW < 8 || wave * 32 < bq) && qw0 < len;
 
   // ---- Q fragments (B operand of S^T): qf[s] = Q[q][16s + 8hi .. +7]
   T8 qf[4];
@@ -55,6 +65,14 @@
 
   const int b_first = seg0 >> 6;
   const int ntile = ((seg1 - 1) >> 6) - b_first + 1;
+  // ---- LDS-DMA (DMA = true): wave w stages rows 8w .. 8w+7 of the K tile and of the V^T tile; lane -> (row 8w + lane/8, physical slot lane%8)
+  const int drow = (tid >> 6) * 8 + ((tid & 63) >> 3);
+  const int dls = ((tid & 7) ^ ((drow >> 1) & 7)) * 8;              // logical slot (in elements) this lane fetches
+  const unsigned lds_k = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) u16*)Ks + (unsigned)(tid >> 6) * 1024u);
+  const unsigned lds_v = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) u16*)Vs + (unsigned)(tid >> 6) * 1024u);
+#endif
+
+#ifndef HATT_PART
   // ---- register staging (DMA = false): 512 threads, one 16-byte chunk of K and one of V^T per thread per tile
   const int srow = tid >> 3, sch = (tid & 7) * 8;
   const int soff = srow * HLD + sch;
@@ -70,11 +88,6 @@
 #define HATT_STORE(BUF)                                                                              \
   *reinterpret_cast<uint4*>(Ks + (BUF) * (HKV * HLD) + soff) = rk;                                   \
   *reinterpret_cast<uint4*>(Vs + (BUF) * (HKV * HLD) + soff) = rv;
-  // ---- LDS-DMA (DMA = true): wave w stages rows 8w .. 8w+7 of the K tile and of the V^T tile; lane -> (row 8w + lane/8, physical slot lane%8)
-  const int drow = (tid >> 6) * 8 + ((tid & 63) >> 3);
-  const int dls = ((tid & 7) ^ ((drow >> 1) & 7)) * 8;              // logical slot (in elements) this lane fetches
-  const unsigned lds_k = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) u16*)Ks + (unsigned)(tid >> 6) * 1024u);
-  const unsigned lds_v = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) u16*)Vs + (unsigned)(tid >> 6) * 1024u);
 #define HATT_DMA(T, BUF)                                                                             \
   {                                                                                                  \
     const int blk_ = b_first + (T);                                                                  \
@@ -89,10 +102,7 @@
     for (int s_ = 0; s_ < NS - 1; ++s_)
       if (s_ < ntile) { HATT_DMA(s_, s_) }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // the Q fragments have landed too -- tell the compiler (a use of every fragment), or it waits for them with vmcnt(3..0) inside
-    // the key loop, where those waits would drain the DMA pieces of the NEXT tile it does not know about
-#pragma unroll
-    for (int s = 0; s < 4; ++s) { uint4 q_ = __builtin_bit_cast(uint4, qf[s]); asm volatile("" : "+v"(q_.x), "+v"(q_.y), "+v"(q_.z), "+v"(q_.w)); qf[s] = __builtin_bit_cast(T8, q_); }
+    HATT_Q_LANDED(qf)
   } else {
     HATT_LOAD(0)
     HATT_STORE(0)
@@ -106,6 +116,8 @@
     if (DMA) { if (ahead) { HATT_DMA(t + NS - 1, (t + NS - 1) & (NS - 1)) } } else if (more) { HATT_LOAD(t + 1) }
 
     if (wave_active) {
+#endif
+#if !defined(HATT_PART) || HATT_PART == 2
       // ---- S^T = K Q^T : two 32-key sub-tiles x 32 queries
       f32x16 s0, s1;
 #pragma unroll
@@ -120,71 +132,11 @@
         s0 = H16<DT>::mfma(k0, qf[s], s0);
         s1 = H16<DT>::mfma(k1, qf[s], s1);
       }
-      if constexpr (CAP) {      // in front of the key mask: tanh(-1e30) would un-mask a key
-        const float inv = 0.125f / cap, capK = 8.0f * cap, capM2K = -16.0f * cap;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s0[r] = softcap_ktanh(s0[r] * inv, capK, capM2K);
-          s1[r] = softcap_ktanh(s1[r] * inv, capK, capM2K);
-        }
-      }
-      // ---- mask keys outside the segment (first / last tile only)
-      const int tile0 = (b_first + t) * 64;
-      if (tile0 < seg0 || tile0 + 64 > seg1) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kg = tile0 + mfma32_crow(r, hi);
-          s0[r] = (kg >= seg0 && kg < seg1) ? s0[r] : -1e30f;
-          s1[r] = (kg + 32 >= seg0 && kg + 32 < seg1) ? s1[r] : -1e30f;
-        }
-      }
-      // ---- softmax, lane-local except one cross-half max (online form only)
-      if (!(OPT & 8)) {
-        float mx;
-        if (OPT & 1) {
-          float ma = hmax3(s0[0], s0[1], s0[2]), mb = hmax3(s1[0], s1[1], s1[2]);   // two independent v_max3_f32 chains
-#pragma unroll
-          for (int r = 3; r < 15; r += 2) { ma = hmax3(ma, s0[r], s0[r + 1]); mb = hmax3(mb, s1[r], s1[r + 1]); }
-          mx = hmax3(ma, mb, fmaxf(s0[15], s1[15]));
-        } else {
-          mx = fmaxf(s0[0], s1[0]);
-#pragma unroll
-          for (int r = 1; r < 16; ++r) mx = fmaxf(mx, fmaxf(s0[r], s1[r]));
-        }
-        mx = h_xhalf_max(mx);
-        // deferred rescale (OPT bit 1): keep the running maximum as long as no row of the wave grew by more than DEFER_THR in the
-        // exponent (P <= 2^DEFER_THR: no overflow in bf16 / fp16 / the fp32 sums); O and l are rescaled only then.
-        // Textbook order: the decision precedes this tile's exponentials and follows the previous tile's P*V.
-        if (!(OPT & 2) || !__all((mx - mrun) * c <= DEFER_THR)) {
-          const float mnew = fmaxf(mrun, mx);
-          const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * c);
-          mrun = mnew;
-          lsum *= alpha;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
-        }
-      }
-      {
-        // exponent FMA and the row sum on the packed fp32 pipe (v_pk_fma_f32 / v_pk_add_f32: two lanes' worth per issue slot)
-        const f32x2 c2 = {c, c};
-        const f32x2 nmc2 = {-mrun * c, -mrun * c};
-        f32x2 ps2 = {0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          f32x2 a = {s0[2 * k], s0[2 * k + 1]};
-          f32x2 b = {s1[2 * k], s1[2 * k + 1]};
-          if (!(OPT & 16)) {
-            a = __builtin_elementwise_fma(a, c2, nmc2);
-            b = __builtin_elementwise_fma(b, c2, nmc2);
-          }
-          a.x = __builtin_amdgcn_exp2f(a.x); a.y = __builtin_amdgcn_exp2f(a.y);
-          b.x = __builtin_amdgcn_exp2f(b.x); b.y = __builtin_amdgcn_exp2f(b.y);
-          s0[2 * k] = a.x; s0[2 * k + 1] = a.y;
-          s1[2 * k] = b.x; s1[2 * k + 1] = b.y;
-          ps2 += a + b;
-        }
-        lsum += ps2.x + ps2.y;
-      }
+      // ---- soft cap, key mask, softmax (lane-local except one cross-half max, online form only), exponentials and row sum: attn_tile.h
+      if constexpr (CAP) ATTN_SOFTCAP(s0, s1, cap)
+      ATTN_MASK_KEYS(s0, s1, (b_first + t) * 64, seg0, seg1, hi)
+      ATTN_ONLINE_RESCALE(OPT, s0, s1, o0, o1, mrun, lsum, c)
+      ATTN_EXP_ROWSUM(OPT, s0, s1, mrun, lsum, c)
       // ---- O^T += V^T P^T : key step ks contracts the keys held in registers 8(ks&1)..+7 of sub-tile ks>>1
       const u16* vp = Vs + cur * (HKV * LDR) + l31 * LDR + (DMA ? 0 : 8 * hi);
 #pragma unroll
@@ -201,6 +153,8 @@
         o0 = H16<DT>::mfma(v0, pb, o0);
         o1 = H16<DT>::mfma(v1, pb, o1);
       }
+#endif
+#ifndef HATT_PART
     }
 
     if (more && !DMA) { HATT_STORE(cur ^ 1) }
@@ -212,9 +166,11 @@
   }
 
   if (!wave_active) return;
+#endif
+#if !defined(HATT_PART) || HATT_PART == 3
   // ---- normalise and store: lane owns query l31; register r of tile e is d = 32e + crow(r, hi): groups of 4 contiguous d.
   // every wave of the block is past the last tile's barrier: the K / V^T buffers are free.  Slab of this wave: [32 queries][72]
-  const float inv = 1.0f / h_xhalf_sum(lsum);
+  const float inv = 1.0f / attn_xhalf_sum(lsum);
   u16* slab = smem + wave * (32 * HLD);
   u16* wp = slab + l31 * HLD + 4 * hi;
 #pragma unroll
@@ -233,3 +189,5 @@
     if (qw0 + row < len)
       *reinterpret_cast<uint4*>(out + (size_t)(seg0 + qw0 + row) * (heads * 64) + head * 64 + piece * 8) = v;
   }
+#endif
+#undef HATT_PART

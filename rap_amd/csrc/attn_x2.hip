@@ -22,26 +22,11 @@
 #include "half.h"
 #include "kernels.h"
 #include "lds_dma.h"
-#include "softcap.h"
+#include "attn_tile.h"
 
 #define XKV 64
 #define XSUB (64 * 64)         // 16-bit elements of one sub-tile (8 KB)
 #define XLD 72                 // row stride of the output slab (144 B)
-#define X_DEFER_THR 11.5f
-
-__device__ __forceinline__ float x_xhalf_max(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float x_xhalf_sum(float v) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float x_max3(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
 
 // WPE = waves per SIMD the register allocation aims at: 2 (144 VGPRs, one block per CU) or 4 (128 VGPRs and 5 spilled, two blocks per CU
 // -- the 64 KB of LDS allow both); tuning key 16 picks (A/B on the GPU: profiles/r05_*).
@@ -139,11 +124,7 @@ int launch_attention_x2(hipStream_t stream, const u16* qk, const u16* vt, int vt
   static_assert(8 * 32 * XLD * 2 <= LDS, "output slabs must fit the stages");
   if (splits > 1) {
     if (!part_o || !part_ml) return RAP_ERR_INVALID;
-    const void* fn = reinterpret_cast<const void*>(attention_x2_kernel<2, true>);
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-      rap_set_last_hip_error((int)hipGetLastError());
-      return RAP_ERR_HIP;
-    }
+    if (int rc = rap_allow_dyn_lds(attention_x2_kernel<2, true>, LDS)) return rc;
     hipLaunchKernelGGL((attention_x2_kernel<2, true>), dim3(max_items * heads, splits), dim3(512), LDS, stream, qk, vt, vt_nblk, out, TP, heads, items,
                        part_o, part_ml);
     RAP_LAUNCH_CHECK();
@@ -158,11 +139,7 @@ int launch_attention_x2(hipStream_t stream, const u16* qk, const u16* vt, int vt
   }
   float* const no = nullptr;
   const bool two = g_rap_attn_x2_wpe == 4;
-  const void* fn = two ? reinterpret_cast<const void*>(attention_x2_kernel<4>) : reinterpret_cast<const void*>(attention_x2_kernel<2>);
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-    rap_set_last_hip_error((int)hipGetLastError());
-    return RAP_ERR_HIP;
-  }
+  if (int rc = rap_allow_dyn_lds(two ? attention_x2_kernel<4> : attention_x2_kernel<2>, LDS)) return rc;
   if (two) hipLaunchKernelGGL(attention_x2_kernel<4>, dim3(max_items * heads), dim3(512), LDS, stream, qk, vt, vt_nblk, out, TP, heads, items, no, no);
   else hipLaunchKernelGGL(attention_x2_kernel<2>, dim3(max_items * heads), dim3(512), LDS, stream, qk, vt, vt_nblk, out, TP, heads, items, no, no);
   RAP_LAUNCH_CHECK();
@@ -173,12 +150,9 @@ int launch_attention_x2(hipStream_t stream, const u16* qk, const u16* vt, int vt
 int launch_attention_x2_softcap(hipStream_t stream, const u16* qk, const u16* vt, int vt_nblk, u16* out, int TP, int heads,
                                 const AttnWorkItem* items, int max_items, float softcap) {
   if (max_items <= 0 || TP <= 0) return RAP_OK;
-  if (heads <= 0 || vt_nblk * 64 < TP || !(softcap > 0.f) || !(softcap < 3.0e38f)) return RAP_ERR_INVALID;
+  if (heads <= 0 || vt_nblk * 64 < TP || !softcap_ok(softcap)) return RAP_ERR_INVALID;
   constexpr int LDS = 2 * 4 * XSUB * 2;      // 64 KB
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x2_softcap_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-    rap_set_last_hip_error((int)hipGetLastError());
-    return RAP_ERR_HIP;
-  }
+  if (int rc = rap_allow_dyn_lds(attention_x2_softcap_kernel<2>, LDS)) return rc;
   hipLaunchKernelGGL(attention_x2_softcap_kernel<2>, dim3(max_items * heads), dim3(512), LDS, stream, qk, vt, vt_nblk, out, TP, heads, items, softcap);
   RAP_LAUNCH_CHECK();
   return RAP_OK;

@@ -1,6 +1,6 @@
 // The body of attention_x2_kernel and attention_x2_softcap_kernel (attn_x2.hip), included once into each: the names SPLIT, CAP
-// (compile-time) and qk, vt, vt_nblk, out, TP, heads, items, part_o, part_ml, cap are the including kernel's.  Text inclusion, not a
-// __device__ __forceinline__ template: see attn_f32_body.inc.  CAP: as in attn_h16_body.inc.
+// (compile-time) and qk, vt, vt_nblk, out, TP, heads, items, part_o, part_ml, cap are the including kernel's.  Text inclusion: see attn_tile.h.
+// CAP: as in attn_h16_body.inc.
   typedef x2_t8 T8;
   extern __shared__ __attribute__((aligned(1024))) u16 smem[];   // [2 stages][K c0 | K c1 | V c0 | V c1] = 64 KB; the 8 output slabs at the end
   const int tid = threadIdx.x;
@@ -100,58 +100,11 @@
         s0 = H16<RAP_DT_F16>::mfma(k0h, qh[s], s0);
         s1 = H16<RAP_DT_F16>::mfma(k1h, qh[s], s1);
       }
-      if constexpr (CAP) {      // in front of the key mask: tanh(-1e30) would un-mask a key
-        const float inv = 0.125f / cap, capK = 8.0f * cap, capM2K = -16.0f * cap;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          s0[r] = softcap_ktanh(s0[r] * inv, capK, capM2K);
-          s1[r] = softcap_ktanh(s1[r] * inv, capK, capM2K);
-        }
-      }
-      // ---- mask keys outside the segment (first / last tile only)
-      const int tile0 = (b_first + t) * 64;
-      if (tile0 < seg0 || tile0 + 64 > seg1) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int kg = tile0 + mfma32_crow(r, hi);
-          s0[r] = (kg >= seg0 && kg < seg1) ? s0[r] : -1e30f;
-          s1[r] = (kg + 32 >= seg0 && kg + 32 < seg1) ? s1[r] : -1e30f;
-        }
-      }
-      // ---- online softmax, lane-local except one cross-half max; deferred rescale (P <= 2^X_DEFER_THR fits fp16)
-      {
-        float ma = x_max3(s0[0], s0[1], s0[2]), mb = x_max3(s1[0], s1[1], s1[2]);
-#pragma unroll
-        for (int r = 3; r < 15; r += 2) { ma = x_max3(ma, s0[r], s0[r + 1]); mb = x_max3(mb, s1[r], s1[r + 1]); }
-        float mx = x_max3(ma, mb, fmaxf(s0[15], s1[15]));
-        mx = x_xhalf_max(mx);
-        if (!__all((mx - mrun) * c <= X_DEFER_THR)) {
-          const float mnew = fmaxf(mrun, mx);
-          const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * c);
-          mrun = mnew;
-          lsum *= alpha;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
-        }
-      }
-      {
-        const f32x2 c2 = {c, c};
-        const f32x2 nmc2 = {-mrun * c, -mrun * c};
-        f32x2 ps2 = {0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          f32x2 a = {s0[2 * k], s0[2 * k + 1]};
-          f32x2 b = {s1[2 * k], s1[2 * k + 1]};
-          a = __builtin_elementwise_fma(a, c2, nmc2);
-          b = __builtin_elementwise_fma(b, c2, nmc2);
-          a.x = __builtin_amdgcn_exp2f(a.x); a.y = __builtin_amdgcn_exp2f(a.y);
-          b.x = __builtin_amdgcn_exp2f(b.x); b.y = __builtin_amdgcn_exp2f(b.y);
-          s0[2 * k] = a.x; s0[2 * k + 1] = a.y;
-          s1[2 * k] = b.x; s1[2 * k + 1] = b.y;
-          ps2 += a + b;
-        }
-        lsum += ps2.x + ps2.y;
-      }
+      // ---- soft cap, key mask, online softmax with v_max3 row maxima and deferred rescale (P <= 2^ATTN_DEFER_THR fits fp16): attn_tile.h
+      if constexpr (CAP) ATTN_SOFTCAP(s0, s1, cap)
+      ATTN_MASK_KEYS(s0, s1, (b_first + t) * 64, seg0, seg1, hi)
+      ATTN_ONLINE_RESCALE(3, s0, s1, o0, o1, mrun, lsum, c)
+      ATTN_EXP_ROWSUM(3, s0, s1, mrun, lsum, c)
       // ---- O^T += V^T P^T (three products): key step ks contracts the keys held in registers 8(ks&1)..+7 of sub-tile ks>>1 =
       //      in-block positions 16 ks + 8 hi .. +7 -> V^T chunk ks >> 1, in-chunk 16 (ks & 1) + 8 hi
 #pragma unroll
@@ -194,14 +147,14 @@
         *reinterpret_cast<float4*>(po + 32 + 8 * g) = float4{o1[4 * g + 0], o1[4 * g + 1], o1[4 * g + 2], o1[4 * g + 3]};
       }
     }
-    const float lall = x_xhalf_sum(lsum);
+    const float lall = attn_xhalf_sum(lsum);
     if (q < len && hi == 0) *reinterpret_cast<float2*>(part_ml + (((size_t)blockIdx.y * TP + (size_t)(seg0 + q)) * heads + head) * 2) = float2{mrun, lall};
     return;
   }
   // ---- normalise, split and store.  Lane owns query l31; register r of tile e is head dim 32 e + crow(r, hi) (groups of 4 contiguous
   // dims), i.e. tile e IS chunk e of this head.  Every wave is past the last tile's barrier: the stages are free.  Slab of this wave:
   // [32 queries][72]: 32 heads | 32 tails of one chunk, written and drained once per chunk (LDS operations of a wave execute in order).
-  const float inv = 1.0f / x_xhalf_sum(lsum);
+  const float inv = 1.0f / attn_xhalf_sum(lsum);
   u16* slab = smem + wave * (32 * XLD);
   u16* wp = slab + l31 * XLD + 4 * hi;
   const size_t orow = (size_t)heads * 128;

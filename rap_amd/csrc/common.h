@@ -30,14 +30,18 @@ typedef std::atomic<int> rap_tuning_t;
 
 void rap_set_last_hip_error(int e);
 
-// Launch of a kernel that takes its one parameter struct by value and needs more than the default 64 KB of dynamic LDS: raise the
-// kernel's limit (per device and cheap, so set unconditionally: a process may drive several GPUs), launch, check.
+// A kernel that asks for dynamic LDS beyond what it may use without asking (64 KB in all): raise its limit.  Per device and cheap, so
+// set in front of every such launch: a process may drive several GPUs.
+template <typename K>
+static int rap_allow_dyn_lds(K* kern, int lds_bytes) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) == hipSuccess) return RAP_OK;
+  rap_set_last_hip_error((int)hipGetLastError());
+  return RAP_ERR_HIP;
+}
+// ... and the whole launch of one that takes its one parameter struct by value: raise the limit, launch, check.
 template <typename P>
 static int rap_launch_dyn_lds(void (*kern)(P), dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const P& p) {
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) {
-    rap_set_last_hip_error((int)hipGetLastError());
-    return RAP_ERR_HIP;
-  }
+  if (int rc = rap_allow_dyn_lds(kern, lds_bytes)) return rc;
   hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, p);
   RAP_LAUNCH_CHECK();
   return RAP_OK;

@@ -3,6 +3,9 @@
 #pragma once
 #include "common.h"
 
+// host: the caps the entry points and the launchers accept -- positive and finite (NaN fails both comparisons)
+static inline bool softcap_ok(float c) { return c > 0.f && c < 3.0e38f; }
+
 // K * tanh(x) in fp32 on v_exp_f32 / v_rcp_f32, no library call; m2K = -2 K (wave-uniform, formed once per kernel).
 //  * |x| >= 1/4:  K (1 - 2 / (1 + e^2x)) as ONE fma on the reciprocal.  The ends are clean: e^2x = +inf gives rcp = 0 and the result K,
 //    e^2x = 0 gives rcp(1) = 1 and the result -K, both exactly; no intermediate is NaN for any finite x.  Error: about an ulp of 1

@@ -1,7 +1,8 @@
-"""CPU: the workspace queries of the nearest-neighbour and ICP entry points are host arithmetic, and their values are pinned.
+"""CPU: the workspace queries of the nearest-neighbour, ICP and attention entry points are host arithmetic, and their values are pinned.
 
 A caller sizes one allocation from these numbers, so a refactor of the carve code must not move them.  The expected values were recorded
-from the library before the search and ICP code was folded (nn_tile.h, one carve function for the four ICP forms)."""
+from the library before the search and ICP code was folded (nn_tile.h, one carve function for the four ICP forms); the attention sizes
+are written out as the formulas of their layout, which held before the attention carve was moved onto Carver."""
 import pytest
 
 from rap_amd import _lib
@@ -46,3 +47,43 @@ def test_refused_arguments_give_zero(name):
         a = list(_args(sig, 257, 3, 3))
         a[pos] = lowest
         assert q(*a) > 0, (name, a)
+
+
+# ---- the kernel-level attention workspaces: [work items | sanitised cu_seqlens | partial O planes | (m, l) plane], every piece 256-aligned
+ATTN_TP = [0, 1, 63, 64, 65, 255, 256, 4097, 262144]
+ATTN_NSEG = [0, 1, 63, 64, 65535]
+
+
+def _up256(n):
+    return (n + 255) // 256 * 256
+
+
+def _attn_tables(TP, nseg):
+    return _up256((TP // 64 + nseg + 1) * 16) + _up256((nseg + 1) * 4)
+
+
+def test_attention_workspace_bytes():
+    q = _lib.load().rap_attention_workspace_bytes
+    for TP in ATTN_TP:
+        for nseg in ATTN_NSEG:
+            assert q(TP, nseg) == _attn_tables(TP, nseg), (TP, nseg)
+
+
+@pytest.mark.parametrize("splits", [1, 2, 4])
+def test_attention_split_workspace_bytes(splits):
+    q = _lib.load().rap_attention_split_workspace_bytes
+    for TP in ATTN_TP:
+        for nseg in ATTN_NSEG:
+            for heads in (1, 8, 16):
+                planes = splits * TP * heads * 256 + _up256(splits * TP * heads * 8) if splits > 1 else 0
+                assert q(TP, nseg, heads, splits) == _attn_tables(TP, nseg) + planes, (TP, nseg, heads, splits)
+
+
+def test_attention_split_workspace_refusals_give_zero():
+    q = _lib.load().rap_attention_split_workspace_bytes
+    assert q(4097, 63, 8, 2) > 0
+    for heads in (0, -1):
+        assert q(4097, 63, heads, 2) == 0
+    for splits in (0, 3, 5):
+        assert q(4097, 63, 8, splits) == 0
+    assert q(-1, 63, 8, 2) == 0 and q(4097, -1, 8, 2) == 0 and q(-1, 63, 8, 1) == 0 and q(4097, -1, 8, 1) == 0
